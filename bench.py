@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- render + recon-loss + backward images/s of the MI355X path (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of B images: render forward (+ fused recon_data forward) -> recon_data
@@ -9,10 +9,17 @@ backward -> render backward, gradients to vertices, textures, lights, bg, distan
 resident in HBM, and every step does all of that work on a full batch.  Workload at every N: BASELINE config 2 (template
 smpl_uv_642, B=48 per GPU, 128x128, texture 256x128, no_mask).
 
+A plain run measures the headline alone: set-up, --settle-seconds of run-in, W warmup steps, ONE timed region of exactly K steps
+(--reps 1), then the result line.  --full adds everything else listed below (the other legs, the per-kernel roofline, the
+trainer-shaped step, the CPU baseline) and times every figure as the MEDIAN of --reps repetitions (default 9 there).
+--dump-outputs DIR writes what the headline's last timed step computed (image, face_idx, face normals, imnormal, loss and the eight
+input gradients) as DIR/<name>.npy in float32; inputs are seeded, so two builds run with the same arguments compare output for output.
+
 What the ONE JSON line (rank 0) reports, all on the same workload (every timed figure is the MEDIAN of --reps repetitions of --steps
 steps, each repetition bracketed by barrier + synchronize: the driver's short --steps reproduces the long run):
   value               K steps strictly one after the other on ONE stream, C ABI, recon_data folded into the render kernels, imnormal
                       materialised as the reference does (networks.py:320): "one B=48 batch at a time", the metric as BASELINE.json words it.
+                      (The only figure of a plain run, with ms_per_step, loss and, N > 1, the gradient all-reduce it overlaps.)
   value_four_streams  the same steps enqueued round-robin on --streams HIP streams (default 4): successive steps are independent batches
                       (the reference's trainer issues four renders per iteration, trainer.py:276,345,347,367) and their kernels overlap.
   value_without_imnormal  `value` without the visualise-only imnormal output.
@@ -156,6 +163,29 @@ def cpu_model():
     return "unknown"
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs budget, .npy headers included
+
+
+def dump_outputs(dirpath, arrays):
+    """arrays: [(name, tensor)] of one step's outputs -> dirpath/<name>.npy in float32 (face_idx is exact there: < 2^24 faces).  Beyond the
+    budget every array is cut to the same fraction of its elements, a fixed sample seeded by its name (flattened, ascending indices)."""
+    import zlib
+
+    import numpy as np
+    import torch
+    host = [(n, t.detach().to("cpu", torch.float32).contiguous().numpy()) for n, t in arrays if t is not None]
+    total = sum(a.nbytes for _, a in host)
+    room = DUMP_BYTES - 256 * len(host)
+    os.makedirs(dirpath, exist_ok=True)
+    for n, a in host:
+        if total > room:
+            keep = max(1, int(a.size * room / total))
+            idx = np.sort(np.random.default_rng(zlib.crc32(n.encode())).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, n + ".npy"), a)
+    sys.stderr.write("bench: wrote %d arrays to %s%s\n" % (len(host), dirpath, " (sampled)" if total > room else ""))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -166,7 +196,11 @@ def main():
                     help="what `value` times.  eager: C-ABI calls per step on --streams streams; hipgraph: the step replayed as one HIP "
                          "graph; torch: the DiffRender autograd API (same as value_api)")
     ap.add_argument("--streams", type=int, default=4, help="HIP streams the independent steps are enqueued on round-robin (value_four_streams)")
-    ap.add_argument("--reps", type=int, default=9, help="repetitions of the timed region of --steps steps; the MEDIAN is reported")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region of --steps steps; the MEDIAN is reported (default 1; 9 with --full)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline too: four-stream, option and autograd-API legs, "
+                    "un-fused chain, per-kernel roofline, trainer-shaped config-3 step, CPU baseline (off: set up, warm up, time --steps steps, report)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline's last timed step computed to DIR/<name>.npy (float32, "
+                    "at most 64 MB in all: a fixed, seeded sample of each array beyond that)")
     ap.add_argument("--shim-steps", type=int, default=30, help="steps of the un-fused kaolin-shaped operator chain timed for value_shim (0 disables)")
     ap.add_argument("--ddp-encoder", type=int, default=1, help="N > 1: all-reduce the REAL gradient buffer of trainer_step.AttributeNet (after one "
                     "DistributedDataParallel step of it, checked) instead of a synthetic buffer of --grad-mb megabytes")
@@ -183,6 +217,9 @@ def main():
     ap.add_argument("--trainer-steps", type=int, default=8, help="trainer-shaped config-3 steps timed for value_config3 (0 disables; N=1 only)")
     ap.add_argument("--grad-mb", type=float, default=None, help="fp32 gradient bytes all-reduced per step over RCCL (default 135 when N>1, else 0)")
     args = ap.parse_args()
+    full = args.full
+    if args.reps is None:
+        args.reps = 9 if full else 1
 
     import numpy as np
     import torch
@@ -219,7 +256,8 @@ def main():
     tpath = os.path.join(ROOT, "tests", "golden", "templates", name + ".npz")
     dr = pkg.DiffRender(tpath, S, ratio=ratio, emit_imnormal=True)
     H, W = dr.render_height, dr.image_size
-    nstreams = max(1, args.streams) if args.mode == "eager" else 1
+    # a plain N=1 run times the one-stream leg only; N > 1 keeps the streams, whose step rate sets the all-reduce cadence below
+    nstreams = max(1, args.streams) if args.mode == "eager" and (full or world > 1) else 1
     nrot = max(1, args.rotate)
 
     def make_batch(seed):
@@ -274,7 +312,7 @@ def main():
     steps_ = [stepmod.RenderLossStep(dr, batches[s_][0][0], batches[s_][0][1], no_mask=True, fused=not args.unfused, emit_imnormal=True)
               for s_ in range(nstreams)]
     step = steps_[0]
-    step_noimn = stepmod.RenderLossStep(dr, batches[0][0][0], batches[0][0][1], no_mask=True, fused=not args.unfused, emit_imnormal=False)
+    step_noimn = stepmod.RenderLossStep(dr, batches[0][0][0], batches[0][0][1], no_mask=True, fused=not args.unfused, emit_imnormal=False) if full else None
 
     # ---- the gradient all-reduce a data-parallel trainer adds to every step (N > 1) ---------------------------------------------
     grad_mb = args.grad_mb if args.grad_mb is not None else (135.0 if world > 1 else 0.0)
@@ -338,9 +376,11 @@ def main():
         sched1.step()
 
     # the DiffRender autograd path (what trainer.py calls): imnormal materialised, workspace from the per-object pool
-    dr_api = pkg.DiffRender(tpath, S, ratio=ratio)
-    leaves_rot = [{k: batches[0][r_][0][k].clone().requires_grad_(True) for k in stepmod.LEAVES} for r_ in range(nrot)]
+    use_api = full or args.mode == "torch"
+    dr_api = pkg.DiffRender(tpath, S, ratio=ratio) if use_api else None
+    leaves_rot = [{k: batches[0][r_][0][k].clone().requires_grad_(True) for k in stepmod.LEAVES} for r_ in range(nrot)] if use_api else None
     ctr2 = [0]
+    api_last = [None]                                            # (rgbs, attributes, loss, leaves) of the latest one_api: --dump-outputs in --mode torch
 
     def one_api():
         k = ctr2[0] % nrot; ctr2[0] += 1
@@ -348,8 +388,11 @@ def main():
         for v in lv.values():
             v.grad = None
         a = dict(batches[0][k][0]); a.update(lv)
-        rgbs, _ = dr_api.render(no_mask=True, **a)
-        dr_api.recon_data(rgbs, batches[0][k][1], no_mask=True).backward()
+        rgbs, out_ = dr_api.render(no_mask=True, **a)
+        loss_ = dr_api.recon_data(rgbs, batches[0][k][1], no_mask=True)
+        loss_.backward()
+        if args.dump_outputs:
+            api_last[0] = (rgbs, out_, loss_, lv)
 
     def one_api_fused():                                         # the same step through DiffRender.render_recon (loss folded into the render kernels)
         k = ctr2[0] % nrot; ctr2[0] += 1
@@ -390,16 +433,37 @@ def main():
         every_k = max(1, int(np.ceil(1.25 * (e3 / 10) / (ew / 200)))) if args.grad_every is None else max(1, args.grad_every)
         reducer.launched = 0
         sched.start(every_k)
-    for _ in range(args.warmup):
-        one()
-    if reducer is not None:
-        reducer.wait()
-        sched.start(every_k)                                     # the first timed step launches a reduction
-    elapsed, elapsed_all = timed_median(lambda: one(), args.steps)
-    launched_timed = reducer.launched if reducer is not None else 0
-    if reducer is not None:
-        reducer.wait(); torch.cuda.synchronize(dev)
-    loss_value = float(step.loss) if args.mode != "torch" else None
+    def dump_step():
+        """--dump-outputs: what the caller of the timed path receives from its last step (rank 0)."""
+        if not args.dump_outputs or rank != 0:
+            return
+        torch.cuda.synchronize(dev)
+        if args.mode == "torch":
+            rgbs, out_, loss_, lv = api_last[0]
+            arrays = [("rgba", rgbs.permute(0, 2, 3, 1)), ("face_idx", dr_api.last_face_idx), ("face_normals", out_["face_normals"]),
+                      ("imnormal", out_["imnormal"]), ("loss", loss_)] + [("grad_" + k, lv[k].grad) for k in stepmod.LEAVES]
+        else:
+            arrays = [("rgba", step.rgba), ("face_idx", step.face_idx), ("face_normals", step.face_normals), ("imnormal", step.imnormal),
+                      ("loss", step.loss)] + [("grad_" + k, step.grads[k]) for k in stepmod.LEAVES]
+        dump_outputs(args.dump_outputs, arrays)
+
+    # the multi-stream leg (eager: value_four_streams) is --full only; in the other modes it is the headline
+    elapsed = elapsed_all = None
+    launched_timed = 0
+    loss_value = None
+    if full or args.mode != "eager":
+        for _ in range(args.warmup):
+            one()
+        if reducer is not None:
+            reducer.wait()
+            sched.start(every_k)                                 # the first timed step launches a reduction
+        elapsed, elapsed_all = timed_median(lambda: one(), args.steps)
+        launched_timed = reducer.launched if reducer is not None else 0
+        if reducer is not None:
+            reducer.wait(); torch.cuda.synchronize(dev)
+        loss_value = float(step.loss) if args.mode != "torch" else None
+        if args.mode != "eager":
+            dump_step()
 
     one_stream = api_value = api_fused_value = shim_value = no_imn_value = api_undeferred_value = options_ab = four_streams_hinted = None
     api_st_values = {}
@@ -408,12 +472,19 @@ def main():
     if args.mode == "eager":
         if reducer is not None:
             sched1.start(every_k)
-        for _ in range(min(args.warmup, 20)):
+        for _ in range(min(args.warmup, 20) if full else args.warmup):
             one_single()
+        launched0 = reducer.launched if reducer is not None else 0
         e1, e1_all = timed_median(one_single, args.steps)
         one_stream = round(world * B * args.steps / e1, 1)
         if reducer is not None:
+            if not full:
+                launched_timed = reducer.launched - launched0
             reducer.wait(); sched1.off()
+        if not full:
+            loss_value = float(step.loss)
+        dump_step()
+    if args.mode == "eager" and full:
         ctr3 = [0]
 
         def one_noimn():
@@ -471,7 +542,7 @@ def main():
             ew_, _ = timed_median(one_ww, args.steps, reps=3)
             four_streams_hinted = round(B * args.steps / ew_, 1)
             del st_w
-    if args.api_steps > 0:
+    if full and args.api_steps > 0:
         # Run-in: the FIRST autograd flavour measured in a process used to carry ~80 us of host time per step for its first few hundred steps
         # (measured, profiles/tools/api_noise.py: 175-186 us against 100-108 us from the second pass on, whichever flavour comes first: the
         # engine's thread, the caching allocator's size classes, the host's clocks) -- r05's driver line read 226 us for value_api and 89 us
@@ -511,7 +582,7 @@ def main():
         for fl in names:
             host_us_per_step[fl] = min(host_rounds[fl])
         host_us_per_step["rounds"] = {"images_per_s": api_rounds, "host_us": host_rounds, "statistic": "value_api* = best of three interleaved rounds; host_us = the smallest"}
-    if args.shim_steps > 0 and rank == 0:
+    if full and args.shim_steps > 0 and rank == 0:
         # the un-fused kaolin-shaped operator chain in the reference's order (networks.py:278-317): ~40 launches per render, float atomics
         try:
             chain = importlib.import_module("3d-magic-mirror_amd.shim_chain")
@@ -537,7 +608,7 @@ def main():
 
     # ---- per-kernel durations (HIP events recorded by the library around each launch, same stream) ------------
     roofline, kernels_us = None, {}
-    if rank == 0 and args.profile_steps > 0:
+    if full and rank == 0 and args.profile_steps > 0:
         step.enable_profiling()
         acc = {}
         for i in range(args.profile_steps + 3):
@@ -603,7 +674,7 @@ def main():
 
     # ---- trainer-shaped config-3 step (BASELINE config 3): encoder -> 4 renders -> recon_data -> regularisers -> backward -> Adam
     config3 = None
-    if rank == 0 and world == 1 and args.trainer_steps > 0:
+    if full and rank == 0 and world == 1 and args.trainer_steps > 0:
         try:
             ts = importlib.import_module("3d-magic-mirror_amd.trainer_step")
             config3 = ts.bench(dev, steps=args.trainer_steps, warmup=3)
@@ -612,7 +683,7 @@ def main():
 
     # ---- CPU baseline: the oracle's step (C restatement of the kaolin DIB-R semantics) on the host cores ----------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
         inp = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in att0.items()}
@@ -660,7 +731,7 @@ def main():
             "metric": "render+loss+bwd images/sec at B=%d %dx%d, ~%.1fk faces" % (B, H, W, dr.num_faces / 1000.0),
             "value": round(total_images / head, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(head / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": full,
             "value_is_b48_one_stream": args.mode == "eager",
             "ranks_seen": ranks_seen, "dist_backend": dist_backend,
             "value_per_gpu": round(total_images / head / world, 1),     # the N=1-equivalent figure of an N > 1 line (weak scaling: divide by the N=1 line's value)
@@ -668,8 +739,9 @@ def main():
                        "spread_pct_of_median": spread(e1_all if args.mode == "eager" else elapsed_all)},
             "config": {"workload": "%s: template %s (V=%d,F=%d), B=%d per GPU, %dx%d, texture %dx%d, no_mask, fwd+loss+bwd to all "
                                    "8 inputs" % (args.config, name, dr.num_vertices, dr.num_faces, B, H, W, Ht, Wt),
-                       "value_is": {"eager": "one B=%d batch at a time on one HIP stream (C ABI, fused loss, imnormal materialised); %d independent "
-                                             "steps in flight on %d streams = value_four_streams; the DiffRender autograd API = value_api*" % (B, nstreams, nstreams),
+                       "value_is": {"eager": "one B=%d batch at a time on one HIP stream (C ABI, fused loss, imnormal materialised)" % B
+                                             + ("; %d independent steps in flight on %d streams = value_four_streams; the DiffRender autograd API = "
+                                                "value_api*" % (nstreams, nstreams) if full else ""),
                                     "hipgraph": "one step replayed as a HIP graph on one stream",
                                     "torch": "the DiffRender autograd API on one stream"}[args.mode],
                        "mode": args.mode, "streams": nstreams, "fused_loss": not args.unfused,
@@ -683,8 +755,8 @@ def main():
                                           "rccl_max_channels": os.environ.get("NCCL_MAX_NCHANNELS"),
                                           "policy": "one reduction in flight at all times, back to back on a side stream, concurrent with the render "
                                                     "streams: K = ceil(1.25 x reduction alone / step alone), agreed on from max-over-ranks timings"}},
-            "value_one_stream": one_stream, "value_four_streams": round(total_images / elapsed, 1) if args.mode == "eager" else None,
-            "ms_per_step_four_streams": round(elapsed / args.steps * 1e3, 4) if args.mode == "eager" else None,
+            "value_one_stream": one_stream, "value_four_streams": round(total_images / elapsed, 1) if args.mode == "eager" and full else None,
+            "ms_per_step_four_streams": round(elapsed / args.steps * 1e3, 4) if args.mode == "eager" and full else None,
             "value_without_imnormal": no_imn_value,
             "value_four_streams_hinted": four_streams_hinted,
             "options_ab": options_ab,

@@ -51,10 +51,34 @@ def test_template_prep_matches_reference_init(pkg, name, ell, ratio):
         assert set(lnb[loff[vid]:loff[vid + 1]].tolist()) == set(np.flatnonzero(L[vid].numpy() > 0).tolist())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/template"), reason="reference tree not present")
+# OBJ text of a template fixture, laid out like the reference's own template files: "a/b" corners (sphere, ellipsoid; the ellipsoid's
+# "v" records end in a blank), a header with mtllib / usemtl, "vn" records and "a/b/c" corners (smpl_uv_642), "a/b/c" corners naming no
+# "vn" record and a doubled separator (smpl_uv)
+OBJ_STYLES = {"sphere": {}, "ellipsoid": {"v_tail": " "}, "smpl_uv_642": {"header": True, "vn": True, "corner": "abc"},
+              "smpl_uv": {"header": True, "corner": "abc", "sep": ["  ", " "]}}
+
+
+def write_template_obj(name, path):
+    """Writes tests/golden/templates/<name>.npz as an OBJ file (shortest float32 decimals, 1-based indices); returns the path."""
+    m = load_template_npz(name)
+    st = OBJ_STYLES[name]
+    num = lambda x: np.format_float_positional(np.float32(x), unique=True, trim="0")
+    out = ["# template mesh %s\n" % name, "mtllib %s.obj.mtl\n" % name, "usemtl material_0\n", "\n"] if st.get("header") else []
+    out += ["v %s %s %s%s\n" % (num(a), num(b), num(c), st.get("v_tail", "")) for a, b, c in m["vertices"]]
+    if st.get("vn"):
+        out += ["vn 0 0 1\n"] * len(m["vertices"])
+    out += ["vt %s %s\n" % (num(a), num(b)) for a, b in m["uvs"]]
+    sep = st.get("sep", [" ", " "])
+    for f, t in zip(m["faces"] + 1, m["face_uvs_idx"] + 1):
+        c = ["%d/%d/%d" % (f[k], t[k], f[k]) if st.get("corner") == "abc" else "%d/%d" % (f[k], t[k]) for k in range(3)]
+        out.append("f " + c[0] + sep[1] + c[1] + sep[0] + c[2] + "\n")
+    path.write_text("".join(out))
+    return str(path)
+
+
 @pytest.mark.parametrize("name", ["sphere", "smpl_uv_642", "ellipsoid"])
-def test_obj_parser_reproduces_template_fixture(pkg, name):
-    m = pkg.obj_io.import_mesh("/root/reference/template/%s.obj" % name)
+def test_obj_parser_reproduces_template_fixture(pkg, name, tmp_path):
+    m = pkg.obj_io.import_mesh(write_template_obj(name, tmp_path / (name + ".obj")))
     z = load_template_npz(name)
     np.testing.assert_array_equal(m.vertices.numpy(), z["vertices"])
     np.testing.assert_array_equal(m.faces.numpy(), z["faces"])
@@ -92,16 +116,15 @@ def test_recon_data_matches_reference(oracle, contour):
         np.testing.assert_allclose(dpred.transpose(0, 2, 3, 1), z["recon_data_c%g__d_pred_nhwc" % contour], rtol=1e-4, atol=1e-9)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/template"), reason="reference tree not present")
 @pytest.mark.parametrize("name", ["sphere", "smpl_uv_642", "ellipsoid", "smpl_uv"])
-def test_template_helpers_against_independent_restatements(pkg, name):
+def test_template_helpers_against_independent_restatements(pkg, name, tmp_path):
     """The three kaolin helpers DiffRender.__init__ calls (import_mesh, uniform_laplacian, generate_perspective_projection; networks.py:172-249)
     are this repo's own code in the template fixtures too (tools/make_golden.py mints through them: kaolin is not in the image).  Here each is
     checked against a second, differently built restatement that shares no code with the first: a regular-expression OBJ reader, a
-    scipy.sparse adjacency, the pinhole formula written out."""
+    scipy.sparse adjacency, the pinhole formula written out.  The OBJ text is written from the template's fixture (write_template_obj)."""
     import re
     import scipy.sparse as sp
-    path = "/root/reference/template/%s.obj" % name
+    path = write_template_obj(name, tmp_path / (name + ".obj"))
     # -- OBJ: v / vt / f a/b[/c] records, 1-based indices
     vs, vts, fs, fts = [], [], [], []
     for line in open(path):
