@@ -5,3 +5,4 @@ from . import mesh_reg, obj_io, template, texture_flow, synthetic  # noqa: F401
 from .diff_render import DiffRender, deep_copy  # noqa: F401
 from .obj_io import import_mesh, save_mesh  # noqa: F401
 from .texture_flow import sample_texture  # noqa: F401
+from .ssim import MS_SSIM, SSIM, ms_ssim, recon_scores, ssim  # noqa: F401

@@ -116,8 +116,23 @@ class MMMaskIouDesc(ctypes.Structure):
     _fields_ = [("B", c_i), ("N", c_i), ("lhs", c_p), ("rhs", c_p), ("sums", c_p), ("loss", c_p)]
 
 
+SSIM_MAX_WIN = 31                     # MM_SSIM_MAX_WIN
+SSIM_NONNEG = 1                       # MM_SSIM_NONNEG
+
+
+class MMSsimDesc(ctypes.Structure):
+    _fields_ = [("N", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("x", c_p), ("x_strides", ctypes.c_int64 * 4),
+                ("y", c_p), ("y_strides", ctypes.c_int64 * 4), ("win_size", c_i), ("win", c_f * SSIM_MAX_WIN), ("C1", c_f), ("C2", c_f),
+                ("flags", c_i), ("ssim", c_p), ("cs", c_p), ("mean_c", c_p), ("mean_all", c_p),
+                ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class MMSsimGrads(ctypes.Structure):
+    _fields_ = [("grad_ssim", c_p), ("grad_cs", c_p), ("grad_x", c_p), ("grad_y", c_p)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
-ABI_VERSION = 6
+ABI_VERSION = 7
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
 OPT_CULL_STRICT, OPT_SOFT_SKIP_CULLED, OPT_BBOX_HALF_OPEN, OPT_BARY_ONE_MINUS, OPT_SH_ORDER_XYZ = 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8
 OPT_BBOX_MIN_CLOSED_MAX_OPEN = 1 << 9
@@ -133,7 +148,8 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_prepare_vertices_query_workspace", "mm_prepare_vertices_forward", "mm_prepare_vertices_backward",
            "mm_face_normals_forward", "mm_face_normals_backward", "mm_dibr_query_workspace", "mm_dibr_rasterization_forward",
            "mm_dibr_rasterization_backward", "mm_texture_mapping_forward", "mm_texture_mapping_backward", "mm_texture_mapping_backward_query_workspace", "mm_sh_lighting_forward",
-           "mm_sh_lighting_backward", "mm_mask_iou_forward", "mm_mask_iou_backward", "mm_struct_size",
+           "mm_sh_lighting_backward", "mm_mask_iou_forward", "mm_mask_iou_backward", "mm_ssim_query_workspace", "mm_ssim_forward",
+           "mm_ssim_backward", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -205,6 +221,10 @@ def lib():
     L.mm_sh_lighting_backward.argtypes = [P(MMShDesc), P(MMShGrads), c_p]
     L.mm_mask_iou_forward.argtypes = [P(MMMaskIouDesc), c_p]
     L.mm_mask_iou_backward.argtypes = [P(MMMaskIouDesc), c_p, c_p, c_p, c_p]
+    L.mm_ssim_query_workspace.restype = ctypes.c_size_t
+    L.mm_ssim_query_workspace.argtypes = [P(MMSsimDesc)]
+    L.mm_ssim_forward.argtypes = [P(MMSsimDesc), c_p]
+    L.mm_ssim_backward.argtypes = [P(MMSsimDesc), P(MMSsimGrads), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -218,7 +238,7 @@ def lib():
         raise RuntimeError("libmm_render.so has ABI version %d, this binding mirrors version %d" % (L.mm_abi_version(), ABI_VERSION))
     mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
-               MMMaskIouDesc)
+               MMMaskIouDesc, MMSsimDesc, MMSsimGrads)
     for i, cls in enumerate(mirrors):
         if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

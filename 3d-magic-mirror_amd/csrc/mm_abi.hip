@@ -25,6 +25,9 @@ int launch_att_fwd(const MMAttLossDesc*, hipStream_t);
 int launch_att_bwd(const MMAttLossDesc*, const MMAttLossGrads*, hipStream_t);
 int launch_texflow_fwd(const MMTexFlowDesc*, hipStream_t);
 int launch_texflow_bwd(const MMTexFlowDesc*, const MMTexFlowGrads*, hipStream_t);
+size_t ssim_workspace_bytes(const MMSsimDesc*);
+int launch_ssim_fwd(const MMSsimDesc*, hipStream_t);
+int launch_ssim_bwd(const MMSsimDesc*, const MMSsimGrads*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -276,6 +279,42 @@ int mm_texture_flow_backward(const MMTexFlowDesc* d, const MMTexFlowGrads* g, mm
     return mm::launch_texflow_bwd(d, g, (hipStream_t)stream);
 }
 
+static bool ssim_shape_ok(const MMSsimDesc* d) {
+    if (d->N <= 0 || d->C <= 0 || d->H <= 0 || d->W <= 0 || d->H > 65535 || d->W > 65535) return false;
+    if (d->win_size < 1 || d->win_size > MM_SSIM_MAX_WIN || d->win_size % 2 == 0) return false;
+    // one workgroup per 64x16 tile of every plane: the grid stays below 2^31 workgroups
+    return (int64_t)d->N * d->C * ((d->H + 15) / 16) * ((d->W + 63) / 64) <= 0x7fffffff;
+}
+
+size_t mm_ssim_query_workspace(const MMSsimDesc* d) {
+    if (!d || !ssim_shape_ok(d)) return 0;
+    return mm::ssim_workspace_bytes(d);
+}
+
+static int check_ssim(const MMSsimDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (!ssim_shape_ok(d)) return MM_ERR_BAD_SHAPE;
+    if (!d->x || !d->y) return MM_ERR_NULL_POINTER;
+    if (!d->workspace || d->workspace_bytes < mm::ssim_workspace_bytes(d)) return MM_ERR_WORKSPACE;
+    return MM_OK;
+}
+
+int mm_ssim_forward(const MMSsimDesc* d, mm_stream_t stream) {
+    const int st = check_ssim(d);
+    if (st != MM_OK) return st;
+    if (!d->ssim) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_ssim_fwd(d, (hipStream_t)stream);
+}
+
+int mm_ssim_backward(const MMSsimDesc* d, const MMSsimGrads* g, mm_stream_t stream) {
+    const int st = check_ssim(d);
+    if (st != MM_OK) return st;
+    if (!g || (!g->grad_ssim && !g->grad_cs) || (!g->grad_x && !g->grad_y)) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_ssim_bwd(d, g, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -343,6 +382,7 @@ size_t mm_struct_size(int which) {
         case 9: return sizeof(MMPrepareDesc);   case 10: return sizeof(MMPrepareGrads); case 11: return sizeof(MMDibrDesc);
         case 12: return sizeof(MMDibrGrads);    case 13: return sizeof(MMTexMapDesc);   case 14: return sizeof(MMTexMapGrads);
         case 15: return sizeof(MMShDesc);       case 16: return sizeof(MMShGrads);      case 17: return sizeof(MMMaskIouDesc);
+        case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);
         default: return 0;
     }
 }

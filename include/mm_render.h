@@ -464,6 +464,46 @@ int mm_mask_iou_forward(const MMMaskIouDesc* desc, mm_stream_t stream);
 int mm_mask_iou_backward(const MMMaskIouDesc* desc, const float* grad_loss, float* grad_lhs, float* grad_rhs, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * SSIM: pytorch_msssim._ssim, the reference's evaluation metric (trainer.py:771-795, 911-935; test.py:428-457), as one fused pass
+ * per (n, c) plane.  The window is separable: the same 1-D taps along H, then along W, in *valid* mode; a dimension shorter than the
+ * window is not filtered (upstream's skip rule), so Ho = H - win_size + 1 (or H), Wo likewise, P = Ho*Wo.  Per output pixel:
+ *     cs_map = (2 sxy + C2) / (sx2 + sy2 + C2),  ssim_map = (2 mx my + C1) / (mx^2 + my^2 + C1) * cs_map
+ * and the per-channel values are the means of both maps over the plane.  Deterministic (fixed-order reductions, no float atomics);
+ * an image's values do not depend on the other images of the batch.  Two launches per call, each direction.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_SSIM_MAX_WIN 31          /* largest win_size */
+#define MM_SSIM_NONNEG 1            /* flags: relu on the per-channel ssim before mean_c / mean_all (pytorch_msssim's nonnegative_ssim) */
+typedef struct MMSsimDesc {
+    int32_t N, C, H, W;             /* sides <= 65535 */
+    const float* x;                 /* (N,C,H,W) at x + n*x_strides[0] + c*x_strides[1] + h*x_strides[2] + w*x_strides[3] (elements) */
+    int64_t x_strides[4];
+    const float* y;                 /* the same for Y */
+    int64_t y_strides[4];
+    int32_t win_size;               /* odd, 1..MM_SSIM_MAX_WIN */
+    float win[MM_SSIM_MAX_WIN];     /* the 1-D taps, first win_size used */
+    float C1, C2;                   /* (K1*data_range)^2, (K2*data_range)^2 */
+    int32_t flags;                  /* MM_SSIM_* */
+    float* ssim;                    /* (N,C) per-channel ssim (before MM_SSIM_NONNEG), written by the forward; required */
+    float* cs;                      /* (N,C) per-channel cs, or NULL */
+    float* mean_c;                  /* (N) mean over C of the per-channel ssim (after MM_SSIM_NONNEG), or NULL */
+    float* mean_all;                /* (1) mean over N and C (the same), or NULL */
+    void* workspace;                /* mm_ssim_query_workspace bytes; scratch of either direction, nothing carried between them */
+    size_t workspace_bytes;
+} MMSsimDesc;
+typedef struct MMSsimGrads {
+    const float* grad_ssim;         /* (N,C) dL/d(per-channel ssim, before MM_SSIM_NONNEG), or NULL */
+    const float* grad_cs;           /* (N,C) dL/d(per-channel cs), or NULL; not both NULL */
+    float* grad_x;                  /* (N,C,H,W) dense, overwritten, or NULL */
+    float* grad_y;                  /* the same for Y, or NULL; not both NULL */
+} MMSsimGrads;
+/* bytes of workspace for forward and backward of this shape; 0 for a bad shape */
+size_t mm_ssim_query_workspace(const MMSsimDesc* desc);
+/* Writes ssim (and cs, mean_c, mean_all where given).  Outputs and ssim's desc fields are ignored by the backward, which recomputes
+ * the moments from x and y. */
+int mm_ssim_forward(const MMSsimDesc* desc, mm_stream_t stream);
+int mm_ssim_backward(const MMSsimDesc* desc, const MMSsimGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -484,13 +524,15 @@ const char* mm_last_error_detail(void);
 /* Layout guard for bindings that mirror the structs by hand (ctypes, cgo, JNI): sizeof of struct #which as the library was
  * compiled, 0 for an unknown id.  Ids: 0 MMRenderDesc, 1 MMRenderGrads, 2 MMReconDesc, 3 MMMeshRegDesc, 4 MMMeshRegGrads,
  * 5 MMAttLossDesc, 6 MMAttLossGrads, 7 MMTexFlowDesc, 8 MMTexFlowGrads, 9 MMPrepareDesc, 10 MMPrepareGrads, 11 MMDibrDesc,
- * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc. */
+ * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
+ * 19 MMSsimGrads. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
- * MM_OPT_BBOX_MIN_CLOSED_MAX_OPEN; 4: MMRenderDesc.geometry_only / status_flag, MMPrepareDesc.proj_device, MMTexMapGrads.workspace, mm_chamfer_nearest, mm_build_vertex_corner_csr_device; 5: MMRenderDesc.fused_contour; 6: MMRenderDesc.fused_totals, mm_recon_data_totals; still 6: the hint bit MM_OPT_MANY_IN_FLIGHT, which changes no result and no layout).  Bindings must refuse a library whose
+ * MM_OPT_BBOX_MIN_CLOSED_MAX_OPEN; 4: MMRenderDesc.geometry_only / status_flag, MMPrepareDesc.proj_device, MMTexMapGrads.workspace, mm_chamfer_nearest, mm_build_vertex_corner_csr_device; 5: MMRenderDesc.fused_contour; 6: MMRenderDesc.fused_totals, mm_recon_data_totals; still 6: the hint bit MM_OPT_MANY_IN_FLIGHT, which changes no result and no layout; 7: MMSsimDesc, MMSsimGrads,
+ * mm_ssim_query_workspace / mm_ssim_forward / mm_ssim_backward, struct ids 18 and 19).  Bindings must refuse a library whose
  * version differs from what they mirror. */
-#define MM_ABI_VERSION 6
+#define MM_ABI_VERSION 7
 int mm_abi_version(void);
 
 #ifdef __cplusplus
