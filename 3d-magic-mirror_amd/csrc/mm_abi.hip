@@ -17,6 +17,7 @@ int launch_recon_bwd(const MMReconDesc*, hipStream_t);
 const float* recon_totals(const MMReconDesc*);
 int launch_nn(int, int, int, const float*, const float*, float*, int32_t*, hipStream_t);
 int launch_nn_both(int, int, int, const float*, const float*, float*, int32_t*, float*, int32_t*, hipStream_t);
+int launch_chamfer_bwd(int, int, int, const float*, const float*, const int32_t*, const int32_t*, const float*, float*, float*, hipStream_t);
 size_t reg_workspace_bytes(const MMMeshRegDesc*);
 int launch_reg_fwd(const MMMeshRegDesc*, hipStream_t);
 int launch_reg_bwd(const MMMeshRegDesc*, const MMMeshRegGrads*, hipStream_t);
@@ -168,6 +169,7 @@ int mm_nearest_neighbour(int32_t B, int32_t N, int32_t M, const float* x, const 
                          mm_stream_t stream) {
     if (!x || !y || !dist || !idx) return MM_ERR_NULL_POINTER;
     if (B <= 0 || N <= 0 || M <= 0) return MM_ERR_BAD_SHAPE;
+    if (B > 65535) return MM_ERR_UNSUPPORTED;                     // (batch rows are the grid's y dimension)
     mm::clear_stale_error();
     return mm::launch_nn(B, N, M, x, y, dist, idx, (hipStream_t)stream);
 }
@@ -179,6 +181,15 @@ int mm_chamfer_nearest(int32_t B, int32_t N, int32_t M, const float* x, const fl
     if (B > 65535) return MM_ERR_UNSUPPORTED;
     mm::clear_stale_error();
     return mm::launch_nn_both(B, N, M, x, y, dist_x, idx_x, dist_y, idx_y, (hipStream_t)stream);
+}
+
+int mm_chamfer_backward(int32_t B, int32_t N, int32_t M, const float* x, const float* y, const int32_t* idx_x, const int32_t* idx_y,
+                        const float* grad_loss, float* grad_x, float* grad_y, mm_stream_t stream) {
+    if (!x || !y || !idx_x || !idx_y || !grad_loss || !grad_x || !grad_y) return MM_ERR_NULL_POINTER;
+    if (B <= 0 || N <= 0 || M <= 0) return MM_ERR_BAD_SHAPE;
+    if (B > 65535) return MM_ERR_UNSUPPORTED;
+    mm::clear_stale_error();
+    return mm::launch_chamfer_bwd(B, N, M, x, y, idx_x, idx_y, grad_loss, grad_x, grad_y, (hipStream_t)stream);
 }
 
 static int check_reg(const MMMeshRegDesc* d, bool backward) {

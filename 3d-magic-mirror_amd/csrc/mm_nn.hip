@@ -173,4 +173,62 @@ int launch_nn_both(int B, int N, int M, const float* x, const float* y, float* d
     return launch_nn_pair(B, N, M, x, y, dx, ix, dy, iy, true, s);
 }
 
+// ---- backward of the chamfer loss  L = mean_b [ mean_i |x_i - y_{ix_i}|^2 + mean_j |y_j - x_{iy_j}|^2 ]  (chamfer.py) ----------------------
+//   dx_i = wx (x_i - y_{ix_i}) - wy sum_{j : iy_j = i} (y_j - x_i),   dy_j = wy (y_j - x_{iy_j}) - wx sum_{i : ix_i = j} (x_i - y_j),
+//   wx = 2g / (B N), wy = 2g / (B M), g = dL read from device memory (no host synchronisation).
+// One wave per 64 TARGET points (the first nxb workgroups of a row take x's points, the others y's).  The wave walks the other direction's
+// index array of its own row in ascending order, 64 sources at a time (one per lane, a coalesced load); a ballot marks the sources whose
+// nearest target is one of the wave's 64, and those alone are visited, lowest lane first, their point handed to the target's lane by
+// v_readlane.  So every target sums the terms that name it in ascending source index, in a fixed order and without float atomics (the
+// gather's scatter_add this replaces accumulated in order of arrival), and a row depends on itself only.  Work per wave: one ballot per
+// 64 sources plus one visit per source that names one of its targets.
+#define MM_NN_BWD_T 64
+
+__global__ __launch_bounds__(MM_NN_BWD_T) void nn_chamfer_bwd_kernel(int B, int N, int M, const float* __restrict__ x, const float* __restrict__ y,
+                                                                     const int32_t* __restrict__ idx_x, const int32_t* __restrict__ idx_y,
+                                                                     const float* __restrict__ grad_loss, float* __restrict__ grad_x,
+                                                                     float* __restrict__ grad_y, int nxb) {
+    const int b = blockIdx.y, lane = (int)threadIdx.x;
+    const bool fx = (int)blockIdx.x < nxb;
+    const int Nt = fx ? N : M, No = fx ? M : N;                   // target points / points of the other cloud
+    const int t0 = ((int)blockIdx.x - (fx ? 0 : nxb)) * MM_NN_BWD_T, t = t0 + lane;
+    const float* __restrict__ ts = (fx ? x : y) + (size_t)b * Nt * 3;
+    const float* __restrict__ os = (fx ? y : x) + (size_t)b * No * 3;
+    const int32_t* __restrict__ own = (fx ? idx_x : idx_y) + (size_t)b * Nt;     // the nearest other point of every target
+    const int32_t* __restrict__ src = (fx ? idx_y : idx_x) + (size_t)b * No;     // the nearest target of every other point
+    float* __restrict__ gt = (fx ? grad_x : grad_y) + (size_t)b * Nt * 3;
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    if (t < Nt) { tx = ts[(size_t)t * 3]; ty = ts[(size_t)t * 3 + 1]; tz = ts[(size_t)t * 3 + 2]; }
+    float sx = 0.f, sy = 0.f, sz = 0.f;                           // sum over the other points whose nearest target is t, ascending
+    for (int j0 = 0; j0 < No; j0 += MM_NN_BWD_T) {
+        const int j = j0 + lane;
+        const int dst = j < No ? src[j] - t0 : -1;                // this lane's source: its target's lane in this wave, if any
+        const bool hit = dst >= 0 && dst < MM_NN_BWD_T;
+        float px = 0.f, py = 0.f, pz = 0.f;
+        if (hit) { px = os[(size_t)j * 3]; py = os[(size_t)j * 3 + 1]; pz = os[(size_t)j * 3 + 2]; }
+        for (unsigned long long m = __ballot(hit); m; m &= m - 1) {                // (wave-uniform: ascending source lanes)
+            const int k = __builtin_ctzll(m);
+            const int dk = __builtin_amdgcn_readlane(dst, k);
+            const float qx = lane_value(px, k), qy = lane_value(py, k), qz = lane_value(pz, k);
+            if (lane == dk) { sx += qx - tx; sy += qy - ty; sz += qz - tz; }
+        }
+    }
+    if (t < Nt) {
+        const float g2 = 2.f * grad_loss[0];
+        const float wt = g2 / (float)((long long)B * Nt), wo = g2 / (float)((long long)B * No);
+        const int o = min(max(own[t], 0), No - 1);                // (indices come from the search, always in range; clamped so a bad one reads in bounds)
+        const float* __restrict__ p = os + (size_t)o * 3;
+        gt[(size_t)t * 3] = wt * (tx - p[0]) - wo * sx;
+        gt[(size_t)t * 3 + 1] = wt * (ty - p[1]) - wo * sy;
+        gt[(size_t)t * 3 + 2] = wt * (tz - p[2]) - wo * sz;
+    }
+}
+
+int launch_chamfer_bwd(int B, int N, int M, const float* x, const float* y, const int32_t* ix, const int32_t* iy, const float* grad_loss,
+                       float* gx, float* gy, hipStream_t s) {
+    const int nxb = (N + MM_NN_BWD_T - 1) / MM_NN_BWD_T, nyb = (M + MM_NN_BWD_T - 1) / MM_NN_BWD_T;
+    hipLaunchKernelGGL(nn_chamfer_bwd_kernel, dim3(nxb + nyb, B), dim3(MM_NN_BWD_T), 0, s, B, N, M, x, y, ix, iy, grad_loss, gx, gy, nxb);
+    return launch_ok("chamfer_backward");
+}
+
 }  // namespace mm

@@ -218,8 +218,9 @@ const float* mm_recon_data_totals(const MMReconDesc* desc);
 
 /* --------------------------------------------------------------------------------------------------------------------
  * Nearest neighbour of every point of x (B,N,3) in y (B,M,3): squared distance (B,N) and index (B,N) int32, lowest index
- * on ties.  The O(N*M) half of pytorch3d.loss.chamfer_distance (knn_points, K=1) that DiffRender.recon_att(chamfer=True)
- * needs (networks.py:342,356); the differentiable tail is a gather.
+ * on ties; NaN distances never win, and a query with no finite distance gets index 0 and distance +inf.  B <= 65535.  The
+ * O(N*M) half of pytorch3d.loss.chamfer_distance (knn_points, K=1) that DiffRender.recon_att(chamfer=True) needs
+ * (networks.py:342,356); the differentiable tail is mm_chamfer_backward below.
  * ------------------------------------------------------------------------------------------------------------------ */
 int mm_nearest_neighbour(int32_t B, int32_t N, int32_t M, const float* x, const float* y, float* dist, int32_t* idx,
                          mm_stream_t stream);
@@ -227,6 +228,14 @@ int mm_nearest_neighbour(int32_t B, int32_t N, int32_t M, const float* x, const 
  * nearest y (dist_x, idx_x: (B,N)) and for every y its nearest x (dist_y, idx_y: (B,M)).  Same results as two calls above. */
 int mm_chamfer_nearest(int32_t B, int32_t N, int32_t M, const float* x, const float* y, float* dist_x, int32_t* idx_x,
                        float* dist_y, int32_t* idx_y, mm_stream_t stream);
+/* Gradient of the chamfer loss  L = mean_b [ mean_i |x_i - y_{idx_x,i}|^2 + mean_j |y_j - x_{idx_y,j}|^2 ]  with the indices
+ * mm_chamfer_nearest wrote (in range: [0,M) and [0,N)):
+ *   grad_x_i = wx (x_i - y_{idx_x,i}) - wy sum_{j : idx_y,j = i} (y_j - x_i),   grad_y_j = wy (y_j - x_{idx_y,j}) - wx sum_{i : idx_x,i = j} (x_i - y_j),
+ * wx = 2g / (B N), wy = 2g / (B M), g = *grad_loss (one float in device memory, read by the kernel).  grad_x (B,N,3), grad_y (B,M,3)
+ * are overwritten.  Every sum is taken in ascending source index, without atomics: bitwise reproducible, and a batch row's result
+ * does not depend on the other rows.  Like the two searches above: B <= 65535 (MM_ERR_UNSUPPORTED otherwise). */
+int mm_chamfer_backward(int32_t B, int32_t N, int32_t M, const float* x, const float* y, const int32_t* idx_x, const int32_t* idx_y,
+                        const float* grad_loss, float* grad_x, float* grad_y, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
  * Mesh regularisers: replaces DiffRender.calc_reg_loss / calc_reg_edge / calc_reg_depth /
@@ -530,9 +539,9 @@ size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
  * MM_OPT_BBOX_MIN_CLOSED_MAX_OPEN; 4: MMRenderDesc.geometry_only / status_flag, MMPrepareDesc.proj_device, MMTexMapGrads.workspace, mm_chamfer_nearest, mm_build_vertex_corner_csr_device; 5: MMRenderDesc.fused_contour; 6: MMRenderDesc.fused_totals, mm_recon_data_totals; still 6: the hint bit MM_OPT_MANY_IN_FLIGHT, which changes no result and no layout; 7: MMSsimDesc, MMSsimGrads,
- * mm_ssim_query_workspace / mm_ssim_forward / mm_ssim_backward, struct ids 18 and 19).  Bindings must refuse a library whose
- * version differs from what they mirror. */
-#define MM_ABI_VERSION 7
+ * mm_ssim_query_workspace / mm_ssim_forward / mm_ssim_backward, struct ids 18 and 19; 8: mm_chamfer_backward, and mm_nearest_neighbour
+ * refuses B > 65535 as mm_chamfer_nearest does).  Bindings must refuse a library whose version differs from what they mirror. */
+#define MM_ABI_VERSION 8
 int mm_abi_version(void);
 
 #ifdef __cplusplus

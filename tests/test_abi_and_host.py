@@ -253,6 +253,37 @@ def test_next_row_entry_points_validate_before_any_gpu_work(pkg):
         pkg.sample_texture(torch.zeros(1, 3, 8, 8), torch.zeros(1, 2, 8, 8))
 
 
+def test_chamfer_entry_points_validate_before_any_gpu_work(pkg):
+    """mm_nearest_neighbour, mm_chamfer_nearest and mm_chamfer_backward refuse null pointers, empty or negative sizes and a batch
+    beyond the grid's y limit (B > 65535) on the host, with their status and before any launch (host buffers stand in for device
+    pointers: none of them may reach a kernel)."""
+    N = pkg._native
+    L = N.lib()
+    fb = (ctypes.c_float * 64)()
+    ib = (ctypes.c_int32 * 64)()
+    f, i = ctypes.cast(fb, ctypes.c_void_p), ctypes.cast(ib, ctypes.c_void_p)
+
+    def calls(B, Nn, M, null=None):
+        def p(k, v):
+            return None if k == null else v
+        return {
+            "mm_nearest_neighbour": lambda: L.mm_nearest_neighbour(B, Nn, M, p(0, f), p(1, f), p(2, f), p(3, i), None),
+            "mm_chamfer_nearest": lambda: L.mm_chamfer_nearest(B, Nn, M, p(0, f), p(1, f), p(2, f), p(3, i), p(4, f), p(5, i), None),
+            "mm_chamfer_backward": lambda: L.mm_chamfer_backward(B, Nn, M, p(0, f), p(1, f), p(2, i), p(3, i), p(4, f), p(5, f), p(6, f), None),
+        }
+    nptr = {"mm_nearest_neighbour": 4, "mm_chamfer_nearest": 6, "mm_chamfer_backward": 7}
+    for name, n in nptr.items():
+        for k in range(n):
+            assert calls(2, 9, 9, null=k)[name]() == -1, (name, k)                  # MM_ERR_NULL_POINTER
+        assert calls(0, 0, 0, null=0)[name]() == -1, name                           # (pointers are checked first)
+        for B, Nn, M in ((0, 9, 9), (2, 0, 9), (2, 9, 0), (-1, 9, 9), (2, -5, 9), (2, 9, -5)):
+            assert calls(B, Nn, M)[name]() == -2, (name, B, Nn, M)                  # MM_ERR_BAD_SHAPE
+        assert calls(65536, 9, 9)[name]() == -5, name                               # MM_ERR_UNSUPPORTED: batch rows are grid y
+        assert calls(1 << 20, 1, 1)[name]() == -5, name
+    assert L.mm_last_error_detail().decode() == ""                                  # nothing was launched
+    assert "mm_chamfer_backward" in N.EXPORTS
+
+
 def test_workspace_query_and_status_validation(pkg):
     """The render workspace is right-sized (round 3: the texture-gradient records are packed per image, no per-tile capacities) and
     mm_render_status validates its arguments on the host before it touches the device."""

@@ -4,6 +4,7 @@ import ctypes
 import importlib
 import inspect
 import os
+import re
 import sys
 
 import numpy as np
@@ -110,15 +111,18 @@ def test_taps_are_the_fp32_construction_bit_for_bit():
 
 
 # ---- ABI mirror and argument checks --------------------------------------------------------------------------------------------
-def test_ssim_symbols_and_structs_are_mirrored():
+def test_ssim_symbols_and_structs_are_mirrored_at_the_headers_abi():
+    """The SSIM symbols and structs (ABI 7) are mirrored, by a binding and a library at exactly the header's MM_ABI_VERSION (not a
+    literal: later additions to the ABI bump it)."""
     N = importlib.import_module("3d-magic-mirror_amd._native")
     lib = N.lib()
     for name in ("mm_ssim_query_workspace", "mm_ssim_forward", "mm_ssim_backward"):
         assert name in N.EXPORTS and hasattr(lib, name)
-    assert N.ABI_VERSION == lib.mm_abi_version() == 7
+    hdr = open(os.path.join(ROOT, "include", "mm_render.h")).read()
+    hdr_version = int(re.search(r"#define MM_ABI_VERSION (\d+)", hdr).group(1))
+    assert N.ABI_VERSION == lib.mm_abi_version() == hdr_version >= 7
     assert lib.mm_struct_size(18) == ctypes.sizeof(N.MMSsimDesc) > 0
     assert lib.mm_struct_size(19) == ctypes.sizeof(N.MMSsimGrads) > 0
-    hdr = open(os.path.join(ROOT, "include", "mm_render.h")).read()
     assert "#define MM_SSIM_MAX_WIN %d" % N.SSIM_MAX_WIN in hdr and "#define MM_SSIM_NONNEG %d" % N.SSIM_NONNEG in hdr
 
 
