@@ -254,41 +254,38 @@ def check(status, what):
                                                             " [" + detail + "]" if detail else ""))
 
 
-_EXT = False
+_EXT = None
 
 
 def torch_ext():
-    """The optional C++ host path (lib/mm_torch_ext.so, built by build_native.build_torch_ext): the module, or None if it is not there or
-    MM_NO_TORCH_EXT is set (then diff_render.py issues the same ABI calls from Python).  Never built lazily: 30 s of g++ do not belong in a
-    first render call; __graft_entry__.build() builds it."""
+    """The C++ autograd nodes of the class API (lib/mm_torch_ext.so from csrc/mm_torch_ext.cpp; diff_render.py has no other host path).
+    Loaded like lib(): a missing module, or one older than its sources, is built first (build_native.build_torch_ext: host compiler only,
+    file lock, atomic publish); a failed build or load, or a module whose MMRenderDesc is not this binding's, raises -- never a stale module."""
     global _EXT
-    if _EXT is False:
-        _EXT = None
-        from . import build_native as bn
-        if not os.environ.get("MM_NO_TORCH_EXT") and os.path.exists(bn.EXT) and bn.ext_needs_build():
-            # (r06: a header edit without a rebuild left the class API on its Python path, three times the host time per step, without a word)
-            import warnings
-            warnings.warn("lib/mm_torch_ext.so is older than its sources (csrc/mm_torch_ext.cpp, include/mm_render.h): the autograd API uses its "
-                          "slower Python host path. Rebuild with `python __graft_entry__.py`.", RuntimeWarning, stacklevel=2)
-        if not os.environ.get("MM_NO_TORCH_EXT") and os.path.exists(bn.EXT) and not bn.ext_needs_build():
-            import importlib.machinery
-            import importlib.util
-            try:
-                loader = importlib.machinery.ExtensionFileLoader("mm_torch_ext", bn.EXT)
-                mod = importlib.util.module_from_spec(importlib.util.spec_from_loader("mm_torch_ext", loader))
-                loader.exec_module(mod)
-                if mod.desc_bytes() == ctypes.sizeof(MMRenderDesc):
-                    _EXT = mod
-            except Exception:                                      # a stale binary of another torch build: use the Python path
-                _EXT = None
-    return _EXT
+    if _EXT is not None:
+        return _EXT
+    import importlib.machinery
+    import importlib.util
+    from . import build_native as bn
+    try:
+        path = bn.build_torch_ext()
+        loader = importlib.machinery.ExtensionFileLoader("mm_torch_ext", path)
+        mod = importlib.util.module_from_spec(importlib.util.spec_from_loader("mm_torch_ext", loader))
+        loader.exec_module(mod)
+    except Exception as e:
+        raise RuntimeError("lib/mm_torch_ext.so could not be built or loaded (%s): rebuild it with `python __graft_entry__.py`" % e)
+    if mod.desc_bytes() != ctypes.sizeof(MMRenderDesc):
+        raise RuntimeError("lib/mm_torch_ext.so was built against an MMRenderDesc of %d bytes, this binding's is %d: rebuild it with "
+                           "`python __graft_entry__.py`" % (mod.desc_bytes(), ctypes.sizeof(MMRenderDesc)))
+    _EXT = mod
+    return mod
 
 
 _ADDR = {}
 
 
 def fn_addr(name):
-    """address of an exported function of the library, for the C++ host path"""
+    """address of an exported function of the library, for the C++ autograd nodes (torch_ext)"""
     a = _ADDR.get(name)
     if a is None:
         a = _ADDR[name] = ctypes.cast(getattr(lib(), name), ctypes.c_void_p).value

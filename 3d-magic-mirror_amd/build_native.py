@@ -108,8 +108,8 @@ def ext_needs_build():
 
 
 def build_torch_ext(force=False, verbose=False):
-    """The optional host-side fast path of the autograd API (csrc/mm_torch_ext.cpp): host compiler only, ~30 s, same lock / atomic publish
-    as the library.  Plumbing above the C ABI -- diff_render.py works without it (Python path, same calls)."""
+    """The C++ autograd nodes of the class API (csrc/mm_torch_ext.cpp): host compiler only, ~30 s, same lock / atomic publish as the
+    library.  Plumbing above the C ABI; diff_render.py has no other host path (_native.torch_ext builds it when missing or stale)."""
     import fcntl
     import sysconfig
     import tempfile

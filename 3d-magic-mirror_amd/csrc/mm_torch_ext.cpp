@@ -1,11 +1,11 @@
-// mm_torch_ext.cpp -- optional host-side fast path of the autograd API (DiffRender.render / recon_data / render_recon).
+// mm_torch_ext.cpp -- the autograd nodes of the class API (DiffRender.render / render_geometry / recon_data / render_recon).
 //
 // The C ABI of libmm_render.so stays the boundary; this file is PLUMBING above it, compiled with the host compiler only (no device
 // code, no HIP headers): one C++ call per autograd node allocates the outputs with ATen, fills the descriptor and enqueues the
-// library's launches on the stream it is given -- what 3d-magic-mirror_amd/diff_render.py otherwise does with ~40 Python / ctypes
-// statements per node (0.2-0.4 ms of host time per step against 0.12 ms of GPU time at B=48, 128x128).  Function addresses of the
-// library come from the ctypes handle, so there is no link-time coupling and no second copy of the library.  If this module is not
-// built, diff_render.py uses its Python path: same calls, same results.
+// library's launches on torch's current stream -- no Python in any backward (0.12 ms of GPU time per step at B=48, 128x128 leaves
+// no room for ~40 Python / ctypes statements per node).  Function addresses of the library come from the ctypes handle, so there is
+// no link-time coupling and no second copy of the library.  diff_render.py has no other host path: _native.torch_ext() builds this
+// module if it is missing or stale, and raises if it cannot.
 #include <torch/extension.h>
 #include <torch/csrc/autograd/custom_function.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // device guard + current stream of a ROCm build of torch (host headers only)
@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <unordered_map>
 #include <vector>
 #include "../../include/mm_render.h"
@@ -63,6 +64,7 @@ typedef int (*render_fwd_t)(const MMRenderDesc*, void*);
 typedef int (*render_bwd_t)(const MMRenderDesc*, const MMRenderGrads*, void*);
 typedef int (*recon_t)(const MMReconDesc*, void*);
 typedef size_t (*recon_ws_t)(const MMReconDesc*);
+typedef int (*render_status_t)(const MMRenderDesc*, void*, int32_t*);
 
 const float* fptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 float* mptr(at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
@@ -132,7 +134,8 @@ std::vector<at::Tensor> render_forward(int64_t f_fwd, int64_t f_loss, const std:
 }
 
 // gradients of vertices, textures, lights, bg (undefined unless no_mask), azimuths, elevations, distances, biases
-std::vector<at::Tensor> render_backward(int64_t f_bwd, const std::string& proto, at::Tensor vertices, at::Tensor textures, at::Tensor lights,
+// f_status: mm_render_status, or 0 -- DiffRender.check_texture_records (a diagnostic: it synchronises the stream)
+std::vector<at::Tensor> render_backward(int64_t f_bwd, int64_t f_status, const std::string& proto, at::Tensor vertices, at::Tensor textures, at::Tensor lights,
                                         c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations, at::Tensor distances,
                                         at::Tensor biases, at::Tensor face_idx, at::Tensor fn, c10::optional<at::Tensor> gt,
                                         c10::optional<at::Tensor> rgba_fwd, c10::optional<at::Tensor> g_rgba, c10::optional<at::Tensor> g_fn,
@@ -170,6 +173,16 @@ std::vector<at::Tensor> render_backward(int64_t f_bwd, const std::string& proto,
     g.grad_lights = mptr(gl); g.grad_bg = mptr(gbg); g.grad_azimuths = mptr(ga); g.grad_elevations = mptr(ge); g.grad_distances = mptr(gd);
     g.grad_biases = mptr(gb);
     check(((render_bwd_t)f_bwd)(&d, &g, (void*)stream), "mm_render_backward");
+    if (f_status) {
+        std::vector<int32_t> dropped((size_t)B);
+        const int st = ((render_status_t)f_status)(&d, (void*)stream, dropped.data());
+        std::string list;
+        bool any = false;
+        for (int32_t n : dropped) { list += (list.empty() ? "" : ", ") + std::to_string(n); any = any || n != 0; }
+        TORCH_CHECK(!(st == MM_ERR_WORKSPACE && any), "mm_render_backward: the texture-record pool overflowed (records dropped per image: [", list,
+                    "]); the texture gradients of those images are NaN. Raise DiffRender.extra_texture_records_per_pixel.");
+        check(st, "mm_render_status");
+    }
     return {gv, gt_, gl, gbg, ga, ge, gd, gb};
 }
 
@@ -210,26 +223,24 @@ at::Tensor recon_backward(int64_t f_bwd, at::Tensor pred, at::Tensor gt, at::Ten
 }
 
 // ---- the autograd nodes themselves, in C++: no Python (and no GIL hand-over to the autograd thread) in the backward -----------------------
-// The stream is captured at forward time: the autograd engine runs a node's backward under the stream its forward ran on.
 using torch::autograd::AutogradContext;
 using torch::autograd::tensor_list;
 
 class RenderNode : public torch::autograd::Function<RenderNode> {
  public:
-    static tensor_list forward(AutogradContext* ctx, int64_t f_fwd, int64_t f_loss, int64_t f_bwd, std::string proto, int64_t ws_bytes,
+    static tensor_list forward(AutogradContext* ctx, int64_t f_fwd, int64_t f_loss, int64_t f_bwd, int64_t f_status, std::string proto, int64_t ws_bytes,
                                at::Tensor vertices, at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths,
                                at::Tensor elevations, at::Tensor distances, at::Tensor biases, c10::optional<at::Tensor> gt, bool want_imnormal,
-                               double image_weight, int64_t stream, bool defer) {
+                               double image_weight, bool defer) {
         TORCH_CHECK(azimuths.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
         const DeviceGuard guard(azimuths.device());
-        stream = current_stream(azimuths.device());              // (the argument is kept for the binding's signature only)
         // the camera scalars may arrive as (B), (B,1), ...: the kernels see (B), the gradients go back in the caller's shapes (advisor r05)
         ctx->saved_data["shape_a"] = azimuths.sizes().vec(); ctx->saved_data["shape_e"] = elevations.sizes().vec(); ctx->saved_data["shape_d"] = distances.sizes().vec();
         at::Tensor ws = at::empty({ws_bytes}, azimuths.options().dtype(at::kByte));   // (the caching allocator is the workspace pool)
         auto out = render_forward(f_fwd, f_loss, proto, vertices, textures, lights, bg, azimuths, elevations, distances, biases, gt, want_imnormal,
-                                  image_weight, ws, stream);
+                                  image_weight, ws, current_stream(azimuths.device()));
         const bool fused = out[13].defined();
-        ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["proto"] = proto;
+        ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto;
         ctx->saved_data["image_weight"] = image_weight; ctx->saved_data["fused"] = fused;
         // dense inputs, forward products the backward re-reads, and the workspace (alive until this node dies)
         ctx->save_for_backward({out[5], out[6], out[7], out[8], out[9], out[10], out[11], out[12], out[3], out[1], out[13],
@@ -265,19 +276,20 @@ class RenderNode : public torch::autograd::Function<RenderNode> {
         if (!fused && g.size() > 4 && g[4].defined() && ctx->saved_data.count("mb")) mb = mailbox_of(ctx->saved_data["mb"].toTensor());
         const bool deferred = mb && mb->gt.defined() && mb->totals != nullptr;
         TORCH_CHECK(deferred || fused || g.size() <= 4 || !g[4].defined(), "a recon_data token carries a gradient but its render has no recon_data on record");
+        const int64_t f_bwd = ctx->saved_data["f_bwd"].toInt(), f_status = ctx->saved_data["f_status"].toInt();
         auto gr = deferred
-            ? render_backward(ctx->saved_data["f_bwd"].toInt(), ctx->saved_data["proto"].toStringRef(), sv[0], sv[1], sv[2], opt(sv[3]), sv[4], sv[5],
+            ? render_backward(f_bwd, f_status, ctx->saved_data["proto"].toStringRef(), sv[0], sv[1], sv[2], opt(sv[3]), sv[4], sv[5],
                               sv[6], sv[7], sv[8], sv[9], opt(mb->gt), c10::nullopt, opt(g[0]), opt(g[1]), opt(g[4]), mb->image_weight, sv[12],
                               current_stream(sv[4].device()), reinterpret_cast<int64_t>(mb->totals))
-            : render_backward(ctx->saved_data["f_bwd"].toInt(), ctx->saved_data["proto"].toStringRef(), sv[0], sv[1], sv[2], opt(sv[3]), sv[4], sv[5],
+            : render_backward(f_bwd, f_status, ctx->saved_data["proto"].toStringRef(), sv[0], sv[1], sv[2], opt(sv[3]), sv[4], sv[5],
                               sv[6], sv[7], sv[8], sv[9], opt(sv[10]), opt(sv[11]), opt(g[0]), opt(g[1]),
                               (fused && g.size() > 4) ? opt(g[4]) : c10::nullopt, ctx->saved_data["image_weight"].toDouble(), sv[12],
                               current_stream(sv[4].device()), 0);
-        // one entry per forward argument: five non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, ...
-        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr[0], gr[1], gr[2], gr[3],
+        // one entry per forward argument: six non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, then four more
+        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr[0], gr[1], gr[2], gr[3],
                 gr[4].reshape(ctx->saved_data["shape_a"].toIntVector()), gr[5].reshape(ctx->saved_data["shape_e"].toIntVector()),
                 gr[6].reshape(ctx->saved_data["shape_d"].toIntVector()), gr[7],
-                at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+                at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
 
@@ -314,11 +326,10 @@ class ReconDeferredNode : public torch::autograd::Function<ReconDeferredNode> {
 class ReconNode : public torch::autograd::Function<ReconNode> {
  public:
     static at::Tensor forward(AutogradContext* ctx, int64_t f_ws, int64_t f_fwd, int64_t f_bwd, at::Tensor pred, at::Tensor gt, double image_weight,
-                              double contour, int64_t stream) {
+                              double contour) {
         TORCH_CHECK(pred.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
         const DeviceGuard guard(pred.device());
         auto out = recon_forward(f_ws, f_fwd, pred, gt, image_weight, contour, current_stream(pred.device()));
-        (void)stream;
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["image_weight"] = image_weight; ctx->saved_data["contour"] = contour;
         ctx->save_for_backward({out[1], out[2], out[3]});
         return out[0];
@@ -328,7 +339,7 @@ class ReconNode : public torch::autograd::Function<ReconNode> {
         const DeviceGuard guard(sv[0].device());
         at::Tensor grad = recon_backward(ctx->saved_data["f_bwd"].toInt(), sv[0], sv[1], sv[2], g[0], ctx->saved_data["image_weight"].toDouble(),
                                          ctx->saved_data["contour"].toDouble(), current_stream(sv[0].device()));
-        return {at::Tensor(), at::Tensor(), at::Tensor(), grad, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        return {at::Tensor(), at::Tensor(), at::Tensor(), grad, at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
 
@@ -392,13 +403,13 @@ at::Tensor geometry_node(int64_t f_fwd, int64_t f_bwd, std::string proto, int64_
 
 // defer: hand out the token a later recon_data(image, gt) can route its backward through (deferred fusion; the returned list is still
 // {rgba, face_normals, imnormal, face_idx}: the token lives in the mailbox)
-tensor_list render_node(int64_t f_fwd, int64_t f_loss, int64_t f_bwd, std::string proto, int64_t ws_bytes, at::Tensor vertices, at::Tensor textures,
-                        at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations, at::Tensor distances, at::Tensor biases,
-                        c10::optional<at::Tensor> gt, bool want_imnormal, double image_weight, int64_t stream, bool defer) {
+tensor_list render_node(int64_t f_fwd, int64_t f_loss, int64_t f_bwd, int64_t f_status, std::string proto, int64_t ws_bytes, at::Tensor vertices,
+                        at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations,
+                        at::Tensor distances, at::Tensor biases, c10::optional<at::Tensor> gt, bool want_imnormal, double image_weight, bool defer) {
     const bool fused = gt.has_value() && gt->defined();
     defer = defer && !fused && at::GradMode::is_enabled();
-    tensor_list out = RenderNode::apply(f_fwd, f_loss, f_bwd, proto, ws_bytes, vertices, textures, lights, bg, azimuths, elevations, distances, biases, gt,
-                                        want_imnormal, image_weight, stream, defer);
+    tensor_list out = RenderNode::apply(f_fwd, f_loss, f_bwd, f_status, proto, ws_bytes, vertices, textures, lights, bg, azimuths, elevations, distances,
+                                        biases, gt, want_imnormal, image_weight, defer);
     if (defer && out.size() > 4) {
         std::shared_ptr<Mailbox> mb;
         { std::lock_guard<std::mutex> lock(g_mail_mutex);
@@ -441,8 +452,8 @@ at::Tensor deferred_token(const at::Tensor& pred) {
     return tok;
 }
 
-at::Tensor recon_node(int64_t f_ws, int64_t f_fwd, int64_t f_bwd, at::Tensor pred, at::Tensor gt, double image_weight, double contour, int64_t stream,
-                      int64_t f_tot, bool allow_defer) {
+at::Tensor recon_node(int64_t f_ws, int64_t f_fwd, int64_t f_bwd, at::Tensor pred, at::Tensor gt, double image_weight, double contour, int64_t f_tot,
+                      bool allow_defer) {
     if (allow_defer && f_tot != 0 && !(contour > 0.0)) {
         if (auto mb = deferrable_render(pred)) {
             mb->claimed = true;
@@ -450,16 +461,12 @@ at::Tensor recon_node(int64_t f_ws, int64_t f_fwd, int64_t f_bwd, at::Tensor pre
             return ReconDeferredNode::apply(deferred_token(pred), mailbox_holder(mb), f_ws, f_fwd, f_tot, pred.detach(), gt, image_weight);
         }
     }
-    return ReconNode::apply(f_ws, f_fwd, f_bwd, pred, gt, image_weight, contour, stream);
+    return ReconNode::apply(f_ws, f_fwd, f_bwd, pred, gt, image_weight, contour);
 }
 
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("render_forward", &render_forward);
-    m.def("render_backward", &render_backward);
-    m.def("recon_forward", &recon_forward);
-    m.def("recon_backward", &recon_backward);
     m.def("render", &render_node);
     m.def("recon_data", &recon_node);
     m.def("render_geometry", &geometry_node);

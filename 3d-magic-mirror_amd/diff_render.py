@@ -1,226 +1,19 @@
 """Host-side mirror of the reference's ``DiffRender`` (/root/reference/networks.py:164-491) over the gfx950 C ABI.
 
 Same constructor, attributes, method names, argument meaning and return values as the reference class, so a
-``trainer.py``-style loop can switch with ``from mm_amd import DiffRender``.  ``render`` and ``recon_data`` run the
-hand-written HIP kernels of ``lib/libmm_render.so`` through ``torch.autograd.Function`` wrappers; there is no CPU or
-eager-torch fallback for them.  The mesh regularisers (``recon_flip``, ``calc_reg_*``) run as one HIP
-launch per direction (``mesh_reg.py``), and so do the attribute losses of ``recon_att`` (``att_loss.py``); its chamfer term is
-a HIP nearest-neighbour kernel.
+``trainer.py``-style loop can switch with ``from mm_amd import DiffRender``.  ``render``, ``render_geometry``, ``render_recon``
+and ``recon_data`` run the hand-written HIP kernels of ``lib/libmm_render.so`` through the C++ autograd nodes of
+``lib/mm_torch_ext.so`` (csrc/mm_torch_ext.cpp); there is no CPU, eager-torch or Python-node fallback for them.  The mesh
+regularisers (``recon_flip``, ``calc_reg_*``) run as one HIP launch per direction (``mesh_reg.py``), and so
+do the attribute losses of ``recon_att`` (``att_loss.py``); its chamfer term is a HIP nearest-neighbour kernel.
 """
 import ctypes
-import math
 
 import numpy as np
 import torch
 
 from . import _native as N
 from . import att_loss, mesh_reg, obj_io, template
-
-
-class _PooledWorkspace(object):
-    """A render workspace borrowed from its DiffRender's pool for as long as the autograd node that owns it lives (forward ->
-    last backward, retain_graph included); it goes back when the node is freed.  Five or six renders of a trainer iteration thus
-    cycle through a handful of buffers instead of allocating ~200 MB each (the library never allocates; the host side owns scratch)."""
-
-    def __init__(self, pool, key, nbytes, device):
-        # The pool is keyed by the stream the work is enqueued on as well: a buffer released by a node whose kernels are still queued
-        # on stream A is only ever handed to another render on stream A, i.e. behind them in stream order (the torch caching allocator
-        # the C++ nodes use gives the same guarantee).
-        self.pool, self.key = pool, key + (torch.cuda.current_stream(device).cuda_stream,)
-        free = pool.setdefault(self.key, [])
-        self.buf = free.pop() if free else torch.empty(nbytes, device=device, dtype=torch.uint8)
-
-    def __del__(self):
-        try:
-            free = self.pool.setdefault(self.key, [])
-            if len(free) < 8:
-                free.append(self.buf)
-        except Exception:                                        # interpreter shutdown
-            pass
-
-
-def _render_inputs(dr, no_mask, vertices, textures, lights, bg, azimuths, elevations, distances, biases):
-    """fp32 dense device tensors + the shape checks of the render boundary (shared by render and render_recon)."""
-    N.require_device(vertices, textures, lights, bg, azimuths, elevations, distances, biases)
-    dev = azimuths.device
-    f32 = lambda t: N.as_f32(t, dev)
-    vertices, textures, lights, bg = f32(vertices), f32(textures), f32(lights), f32(bg)
-    azimuths, elevations, distances, biases = f32(azimuths).reshape(-1), f32(elevations).reshape(-1), f32(distances).reshape(-1), f32(biases)
-    B = azimuths.shape[0]
-    H, W = dr.render_height, dr.image_size
-    if vertices.shape != (B, dr.num_vertices, 3):
-        raise RuntimeError("vertices must be (B,%d,3), got %s" % (dr.num_vertices, tuple(vertices.shape)))
-    if textures.dim() != 4 or textures.shape[0] != B or textures.shape[1] != 3:
-        raise RuntimeError("textures must be (B,3,Ht,Wt), got %s" % (tuple(textures.shape),))
-    if lights.shape != (B, 9) or biases.shape != (B, 2) or elevations.shape[0] != B or distances.shape[0] != B:
-        raise RuntimeError("lights (B,9), biases (B,2), elevations/distances (B) expected")
-    if no_mask:
-        if bg is None:
-            raise TypeError("render(no_mask=True) needs attributes['bg'] (B,3,H,W)")   # reference: None.permute fails
-        if bg.shape != (B, 3, H, W):
-            raise RuntimeError("bg must be (B,3,%d,%d), got %s" % (H, W, tuple(bg.shape)))
-    return dev, B, H, W, vertices, textures, lights, bg, azimuths, elevations, distances, biases
-
-
-class _RenderFn(torch.autograd.Function):
-    """rgba (B,H,W,4), face_normals (B,F,3), imnormal (B,H,W,3), face_idx (B,H,W) = render(attributes).
-    With ``gt`` (B,4,H,W): the recon_data loss of the batch is folded into the same kernels (MMRenderDesc.fused_*) and returned as a
-    fifth output; the image is then an output without gradient (its only consumer, the loss, is already inside)."""
-
-    @staticmethod
-    def forward(ctx, dr, no_mask, want_imnormal, gt, vertices, textures, lights, bg, azimuths, elevations, distances, biases, contour):
-        ctx.cam_shapes = (tuple(azimuths.shape), tuple(elevations.shape), tuple(distances.shape))   # (B), (B,1), ...: the gradients go back in these
-        dev, B, H, W, vertices, textures, lights, bg, azimuths, elevations, distances, biases = _render_inputs(
-            dr, no_mask, vertices, textures, lights, bg, azimuths, elevations, distances, biases)
-        st = dr._static(dev)
-        if want_imnormal == "geometry":                          # render_geometry: the vertex stage alone (MMRenderDesc.geometry_only)
-            fn = torch.empty((B, dr.num_faces, 3), device=dev, dtype=torch.float32)
-            d = dr._desc(st, B, False, vertices, textures, lights, None, azimuths, elevations, distances, biases, None, None, fn, None)
-            d.geometry_only = 1
-            nbytes = dr.workspace_bytes(d)
-            holder = _PooledWorkspace(dr._ws_pool, (str(dev), nbytes), nbytes, dev)
-            d.workspace, d.workspace_bytes = N.ptr(holder.buf), holder.buf.numel()
-            with torch.cuda.device(dev):
-                N.check(N.lib().mm_render_forward(ctypes.byref(d), N.current_stream(dev)), "mm_render_forward")
-            ctx.dr, ctx.geometry, ctx.ws_holder = dr, True, holder
-            ctx.save_for_backward(vertices, textures, azimuths, elevations, distances, biases)
-            ctx.set_materialize_grads(False)
-            return fn
-        ctx.geometry = False
-        rgba = torch.empty((B, H, W, 4), device=dev, dtype=torch.float32)
-        face_idx = torch.empty((B, H, W), device=dev, dtype=torch.int32)
-        fn = torch.empty((B, dr.num_faces, 3), device=dev, dtype=torch.float32)
-        imn = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32) if want_imnormal else None
-        d = dr._desc(st, B, no_mask, vertices, textures, lights, bg, azimuths, elevations, distances, biases, rgba, face_idx, fn, imn)
-        loss = None
-        if gt is not None:
-            N.require_device(gt)
-            gt = N.as_f32(gt, dev)
-            if gt.shape != (B, 4, H, W):
-                raise RuntimeError("gt_data must be (B,4,%d,%d), got %s" % (H, W, tuple(gt.shape)))
-            loss = torch.empty((), device=dev, dtype=torch.float32)
-            d.fused_gt, d.fused_image_weight, d.fused_loss = N.ptr(gt), float(dr.image_weight), N.ptr(loss)
-            d.fused_contour = float(contour)
-        nbytes = dr.workspace_bytes(d)
-        holder = _PooledWorkspace(dr._ws_pool, (str(dev), nbytes), nbytes, dev)
-        ws = holder.buf
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        with torch.cuda.device(dev):                              # launches go to the tensors' device whatever the caller's current one is
-            N.check(N.lib().mm_render_forward(ctypes.byref(d), N.current_stream(dev)), "mm_render_forward")
-            if gt is not None:
-                N.check(N.lib().mm_render_fused_loss(ctypes.byref(d), N.current_stream(dev)), "mm_render_fused_loss")
-        ctx.dr, ctx.no_mask, ctx.fused, ctx.contour = dr, bool(no_mask), gt is not None, float(contour)
-        ctx.options = int(d.options)                              # the backward uses the FORWARD's option bits (which walk form set the face flags), whatever dr.options says by then
-        ctx.ws_holder = holder                                   # returned to the pool when this node dies
-        ctx.save_for_backward(vertices, textures, lights, bg, azimuths, elevations, distances, biases, face_idx, fn, gt)
-        # (the image is not saved: the backward re-forms the prediction per pixel, bit for bit, and the caller may overwrite rgba)
-        ctx.mark_non_differentiable(face_idx)
-        ctx.set_materialize_grads(False)                          # unused outputs arrive as None in backward, not as zero-filled tensors
-        if imn is None:
-            imn = torch.empty(0, device=dev)
-        ctx.mark_non_differentiable(imn)
-        if gt is None:
-            return rgba, fn, imn, face_idx
-        ctx.mark_non_differentiable(rgba)
-        return rgba, fn, imn, face_idx, loss
-
-    @staticmethod
-    def backward(ctx, g_rgba, g_fn=None, _g_imn=None, _g_idx=None, g_loss=None):
-        if ctx.geometry:                                         # (g_rgba is dL/dface_normals here: the node's only output)
-            vertices, textures, azimuths, elevations, distances, biases = ctx.saved_tensors
-            if g_rgba is None:
-                return (None,) * 13
-            dr, dev, B = ctx.dr, azimuths.device, azimuths.shape[0]
-            g_fn = g_rgba.to(torch.float32).contiguous()
-            d = dr._desc(dr._static(dev), B, False, vertices, textures, None, None, azimuths, elevations, distances, biases, None, None, None, None)
-            d.geometry_only = 1
-            d.face_normals = g_fn.data_ptr()                     # (a valid pointer for the argument check; the backward does not read the normals)
-            ws = ctx.ws_holder.buf
-            d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-            gv = torch.empty_like(vertices)
-            ga, ge, gd, gb = torch.empty_like(azimuths), torch.empty_like(elevations), torch.empty_like(distances), torch.empty_like(biases)
-            g = N.MMRenderGrads(None, N.ptr(g_fn), N.ptr(gv), None, None, None, N.ptr(ga), N.ptr(ge), N.ptr(gd), N.ptr(gb))
-            with torch.cuda.device(dev):
-                N.check(N.lib().mm_render_backward(ctypes.byref(d), ctypes.byref(g), N.current_stream(dev)), "mm_render_backward")
-            sa, se, sd = ctx.cam_shapes
-            return None, None, None, None, gv, None, None, None, ga.reshape(sa), ge.reshape(se), gd.reshape(sd), gb, None
-        vertices, textures, lights, bg, azimuths, elevations, distances, biases, face_idx, fn, gt = ctx.saved_tensors
-        ws = ctx.ws_holder.buf
-        dr, dev = ctx.dr, azimuths.device
-        B = azimuths.shape[0]
-        H, W = dr.render_height, dr.image_size
-        st = dr._static(dev)
-        g_fn = None if g_fn is None else g_fn.to(torch.float32).contiguous()
-        d = dr._desc(st, B, ctx.no_mask, vertices, textures, lights, bg, azimuths, elevations, distances, biases, None, face_idx, fn, None)   # (rgba: not read by the backward)
-        d.options = ctx.options
-        if ctx.fused:
-            # None = the loss output took no part in what is being differentiated (materialize_grads is off): its gradient is ZERO,
-            # never one -- e.g. reg.backward() through attributes['face_normals'] after loss.backward(retain_graph=True)
-            g_loss = (torch.zeros((), device=dev, dtype=torch.float32) if g_loss is None
-                      else g_loss.to(device=dev, dtype=torch.float32).reshape(()).contiguous())
-            d.fused_gt, d.fused_image_weight, d.fused_grad_loss = N.ptr(gt), float(dr.image_weight), N.ptr(g_loss)
-            d.fused_contour = ctx.contour
-        else:
-            if g_rgba is None:
-                g_rgba = torch.zeros((B, H, W, 4), device=dev, dtype=torch.float32)
-            g_rgba = g_rgba.to(torch.float32).contiguous()
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        gv, gt_, gl = torch.empty_like(vertices), torch.empty_like(textures), torch.empty_like(lights)
-        gbg = torch.empty_like(bg) if ctx.no_mask else None
-        ga, ge, gd, gb = torch.empty_like(azimuths), torch.empty_like(elevations), torch.empty_like(distances), torch.empty_like(biases)
-        g = N.MMRenderGrads(None if ctx.fused else N.ptr(g_rgba), N.ptr(g_fn), N.ptr(gv), N.ptr(gt_), N.ptr(gl), N.ptr(gbg), N.ptr(ga), N.ptr(ge), N.ptr(gd), N.ptr(gb))
-        with torch.cuda.device(dev):
-            N.check(N.lib().mm_render_backward(ctypes.byref(d), ctypes.byref(g), N.current_stream(dev)), "mm_render_backward")
-            if ctx.dr.check_texture_records:                     # (synchronises: a diagnostic switch)
-                ctx.dr.check_records(d, N.current_stream(dev))
-        sa, se, sd = ctx.cam_shapes
-        return None, None, None, None, gv, gt_, gl, gbg, ga.reshape(sa), ge.reshape(se), gd.reshape(sd), gb, None
-
-
-class _ReconFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, gt, image_weight, contour):
-        N.require_device(pred, gt)
-        dev = pred.device
-        pred = pred.detach().to(torch.float32)
-        if not _dense_non_overlapping(pred):
-            pred = pred.contiguous()
-        gt = gt.detach().to(device=dev, dtype=torch.float32).contiguous()
-        B, C, H, W = pred.shape
-        if C != 4 or gt.shape != pred.shape:
-            raise RuntimeError("recon_data expects (B,4,H,W) prediction and target, got %s / %s" % (tuple(pred.shape), tuple(gt.shape)))
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        d = N.MMReconDesc()
-        d.B, d.H, d.W = B, H, W
-        d.pred, d.gt = N.ptr(pred), N.ptr(gt)
-        for i, s in enumerate(pred.stride()):
-            d.pred_strides[i] = s
-        d.image_weight, d.contour = float(image_weight), float(contour)
-        d.loss = N.ptr(loss)
-        ws = torch.empty(N.lib().mm_recon_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        N.check(N.lib().mm_recon_data_forward(ctypes.byref(d), N.current_stream(dev)), "mm_recon_data_forward")
-        ctx.save_for_backward(pred, gt, ws)
-        ctx.cfg = (float(image_weight), float(contour))
-        return loss
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        pred, gt, ws = ctx.saved_tensors
-        dev = pred.device
-        B, _, H, W = pred.shape
-        g_loss = g_loss.to(device=dev, dtype=torch.float32).contiguous()
-        grad = torch.empty_strided(pred.shape, pred.stride(), device=dev, dtype=torch.float32)
-        d = N.MMReconDesc()
-        d.B, d.H, d.W = B, H, W
-        d.pred, d.gt = N.ptr(pred), N.ptr(gt)
-        for i, s in enumerate(pred.stride()):
-            d.pred_strides[i] = s
-        d.image_weight, d.contour = ctx.cfg
-        d.grad_loss, d.grad_pred = N.ptr(g_loss), N.ptr(grad)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        N.check(N.lib().mm_recon_data_backward(ctypes.byref(d), N.current_stream(dev)), "mm_recon_data_backward")
-        return grad, None, None, None
 
 
 class _SplitBatchFn(torch.autograd.Function):
@@ -254,17 +47,6 @@ class _SplitBatchFn(torch.autograd.Function):
         return (full,) + (None,) * len(ctx.sizes)
 
 
-def _dense_non_overlapping(t):
-    expect = 1
-    for size, stride in sorted(zip(t.shape, t.stride()), key=lambda p: p[1]):
-        if size == 1:
-            continue
-        if stride != expect:
-            return False
-        expect *= size
-    return True
-
-
 class DiffRender(object):
     """Drop-in for ``networks.DiffRender`` (networks.py:164)."""
 
@@ -279,10 +61,11 @@ class DiffRender(object):
         self.options = 0                                # MMRenderDesc.options: MM_OPT_* bits (SURVEY Appendix C switches); 0 = defaults
         # The render workspace is the library's minimum (mm_query_workspace) plus room for this many MORE texture-gradient records per pixel
         # than the 9/8 the minimum holds (include/mm_render.h); an image that runs out gets NaN texture gradients, and with
-        # check_texture_records every backward of the class API asks the library (a stream synchronisation) and raises instead.
+        # check_texture_records every render backward of the class API (RenderNode, deferred or not) asks the library (a stream synchronisation)
+        # and raises instead.
         self.extra_texture_records_per_pixel = 0.0
         self.check_texture_records = False
-        # DEFERRED FUSION (C++ nodes only; csrc/mm_torch_ext.cpp, MMRenderDesc.fused_totals): `recon_data(pred, gt)` on the untouched image of an earlier
+        # DEFERRED FUSION (csrc/mm_torch_ext.cpp, MMRenderDesc.fused_totals): `recon_data(pred, gt)` on the untouched image of an earlier
         # `render` of this process -- the un-modified trainer's order of calls (trainer.py:276,441) -- forms its value as always and routes its BACKWARD
         # through the render node: no dL/d image tensor, no loss-backward launch; every gradient of the render's inputs has the bits of the two separate
         # backward passes.  The one observable difference: recon_data's contribution to the gradient OF THE IMAGE ITSELF (torch.autograd.grad(loss, rgbs),
@@ -307,7 +90,6 @@ class DiffRender(object):
         self._vc_table = template.vertex_corner_table(self.num_vertices, self.faces)     # (V, stride, 4): the backward's vertex -> corner gather
         self._static_cache = {}
         self._desc_cache = {}
-        self._ws_pool = {}                                       # (device, bytes) -> free render workspaces (see _PooledWorkspace)
         self._status = None                                      # one pinned int32 the backward kernels add dropped-record counts to (MMRenderDesc.status_flag)
         # dibr_rasterization defaults (kaolin v0.12.0): sigmainv=7000, boxlen=0.02, knum=30, multiplier=1000, eps=1e-8
         self.sigmainv, self.boxlen, self.knum, self.multiplier, self.eps = 7000.0, 0.02, 30, 1000.0, 1e-8
@@ -328,13 +110,9 @@ class DiffRender(object):
         return st
 
     def _render_node(self, no_mask, gt, vertices, textures, lights, bg, azimuths, elevations, distances, biases, contour=0.0):
-        """One autograd node for the render (+ the fused loss if gt is given).  With lib/mm_torch_ext.so built, the node is C++
-        (csrc/mm_torch_ext.cpp: no Python in the backward); otherwise the torch.autograd.Function above issues the same ABI calls."""
+        """One C++ autograd node for the render, + the fused loss if gt is given (csrc/mm_torch_ext.cpp: RenderNode; no Python in the backward).
+        With check_texture_records, its backward also asks mm_render_status and raises if texture-gradient records were dropped."""
         self._raise_if_records_were_dropped()                    # (an overflow of an EARLIER step's backward: a host read of pinned memory, no sync)
-        ext = None if self.check_texture_records else N.torch_ext()   # (the diagnostic switch lives in the Python nodes)
-        if ext is None:
-            return _RenderFn.apply(self, no_mask, self.emit_imnormal, gt, vertices, textures, lights, bg, azimuths, elevations, distances, biases,
-                                   float(contour))
         N.require_device(azimuths)
         if no_mask and bg is None:
             raise TypeError("render(no_mask=True) needs attributes['bg'] (B,3,H,W)")   # reference: None.permute fails
@@ -342,9 +120,10 @@ class DiffRender(object):
             raise RuntimeError("textures must be (B,3,Ht,Wt), got %s" % (tuple(textures.shape),))
         dev = azimuths.device
         proto, nbytes = self._proto(self._static(dev), azimuths.numel(), no_mask, textures.shape[2], textures.shape[3], float(contour) if gt is not None else 0.0)
-        return ext.render(N.fn_addr("mm_render_forward"), N.fn_addr("mm_render_fused_loss"), N.fn_addr("mm_render_backward"), proto, nbytes,
-                          vertices, textures, lights, bg, azimuths, elevations, distances, biases, gt, bool(self.emit_imnormal),
-                          float(self.image_weight), torch._C._cuda_getCurrentRawStream(dev.index), bool(self.defer_recon_fusion))
+        return N.torch_ext().render(N.fn_addr("mm_render_forward"), N.fn_addr("mm_render_fused_loss"), N.fn_addr("mm_render_backward"),
+                                    N.fn_addr("mm_render_status") if self.check_texture_records else 0, proto, nbytes,
+                                    vertices, textures, lights, bg, azimuths, elevations, distances, biases, gt, bool(self.emit_imnormal),
+                                    float(self.image_weight), bool(self.defer_recon_fusion))
 
     def _status_ptr(self):
         """Address of this object's pinned status word (device-writable host memory): every descriptor built here carries it, so that a
@@ -374,21 +153,10 @@ class DiffRender(object):
         extra = int(np.ceil(max(0.0, float(self.extra_texture_records_per_pixel)) * d.H * d.W)) * 24 * d.B
         return int(N.lib().mm_query_workspace(ctypes.byref(d))) + extra
 
-    @staticmethod
-    def check_records(d, stream):
-        """Raise if the last mm_render_backward on MMRenderDesc `d` dropped texture-gradient records (synchronises `stream`)."""
-        dropped = (ctypes.c_int32 * d.B)()
-        st = N.lib().mm_render_status(ctypes.byref(d), stream, dropped)
-        if st != 0 and not any(dropped):
-            N.check(st, "mm_render_status")
-        if st != 0:
-            raise RuntimeError("mm_render_backward: the texture-record pool overflowed (records dropped per image: %s); the texture gradients of those "
-                               "images are NaN. Raise DiffRender.extra_texture_records_per_pixel." % (list(dropped),))
-
-    def _proto(self, st, B, no_mask, Ht, Wt, contour=0.0, geometry_only=False):
-        """(bytes of the MMRenderDesc prototype of this shape, its workspace size) for the C++ host path; cached like _desc's prototypes.
-        contour: MMRenderDesc.fused_contour -- the C++ node copies the prototype for its forward AND its backward, so the weight travels in it."""
-        key = ("bytes", id(st), B, int(bool(no_mask)), Ht, Wt, self.knum, self.sigmainv, self.boxlen, self.multiplier, self.eps, self.options,
+    def _prototype(self, st, B, no_mask, Ht, Wt, contour=0.0, geometry_only=False):
+        """(MMRenderDesc prototype of this shape, its bytes, its workspace size), filled once per shape and cached: sizes, dibr constants,
+        template pointers, options and the status word -- everything of a descriptor but the per-call tensor pointers."""
+        key = (id(st), B, int(bool(no_mask)), Ht, Wt, self.knum, self.sigmainv, self.boxlen, self.multiplier, self.eps, self.options,
                float(self.extra_texture_records_per_pixel), float(contour), bool(geometry_only))
         hit = self._desc_cache.get(key)
         if hit is None:
@@ -405,34 +173,20 @@ class DiffRender(object):
             d.options = self.options
             d.status_flag = self._status_ptr()
             d.fused_contour = float(contour)
-            hit = (bytes(d), self.workspace_bytes(d))
+            hit = (d, bytes(d), self.workspace_bytes(d))
             if len(self._desc_cache) > 32:
                 self._desc_cache.clear()
             self._desc_cache[key] = hit
         return hit
 
+    def _proto(self, st, B, no_mask, Ht, Wt, contour=0.0, geometry_only=False):
+        """(bytes of the MMRenderDesc prototype of this shape, its workspace size) for the C++ nodes, which copy the prototype for their
+        forward AND their backward -- so contour (MMRenderDesc.fused_contour) travels in it."""
+        return self._prototype(st, B, no_mask, Ht, Wt, contour, geometry_only)[1:]
+
     def _desc(self, st, B, no_mask, vertices, textures, lights, bg, azimuths, elevations, distances, biases, rgba, face_idx, fn, imn):
-        """MMRenderDesc for one call.  The constant part (sizes, dibr constants, template pointers) is filled once per shape and
-        copied; only the per-call pointers are set here (host time matters: this path is enqueue-bound)."""
-        key = (id(st), B, int(bool(no_mask)), textures.shape[2], textures.shape[3], self.knum, self.sigmainv, self.boxlen, self.multiplier,
-               self.eps, self.options)
-        proto = self._desc_cache.get(key)
-        if proto is None:
-            proto = N.MMRenderDesc()
-            proto.B, proto.H, proto.W, proto.V, proto.F = B, self.render_height, self.image_size, self.num_vertices, self.num_faces
-            proto.Ht, proto.Wt = textures.shape[2], textures.shape[3]
-            proto.no_mask, proto.knum = int(bool(no_mask)), self.knum
-            for i in range(3):
-                proto.proj[i] = float(self.cam_proj[i, 0])
-            proto.sigmainv, proto.boxlen, proto.multiplier, proto.eps = self.sigmainv, self.boxlen, self.multiplier, self.eps
-            proto.faces, proto.face_uvs = N.ptr(st["faces"]), N.ptr(st["face_uvs"])
-            proto.vc_table, proto.vc_stride = N.ptr(st["vc_table"]), int(st["vc_table"].shape[1])
-            proto.options = self.options
-            proto.status_flag = self._status_ptr()
-            if len(self._desc_cache) > 32:
-                self._desc_cache.clear()
-            self._desc_cache[key] = proto
-        d = N.MMRenderDesc.from_buffer_copy(proto)
+        """MMRenderDesc for one call (step.RenderLossStep): a copy of the shape's prototype with the per-call pointers set."""
+        d = N.MMRenderDesc.from_buffer_copy(self._prototype(st, B, no_mask, textures.shape[2], textures.shape[3])[0])
         dp = lambda t: None if t is None else t.data_ptr()
         d.vertices, d.textures, d.lights, d.bg = dp(vertices), dp(textures), dp(lights), dp(bg)
         d.azimuths, d.elevations, d.distances, d.biases = dp(azimuths), dp(elevations), dp(distances), dp(biases)
@@ -491,16 +245,12 @@ class DiffRender(object):
         a = attributes
         self._raise_if_records_were_dropped()
         N.require_device(a['azimuths'])
-        ext = None if self.check_texture_records else N.torch_ext()
-        if ext is not None and hasattr(ext, "render_geometry"):   # the C++ node (csrc/mm_torch_ext.cpp: GeometryNode): no Python in forward or backward
-            dev = a['azimuths'].device
-            tex = a['textures']
-            proto, nbytes = self._proto(self._static(dev), a['azimuths'].numel(), False, tex.shape[2], tex.shape[3], 0.0, geometry_only=True)
-            attributes['face_normals'] = ext.render_geometry(N.fn_addr("mm_render_forward"), N.fn_addr("mm_render_backward"), proto, nbytes,
-                                                             a['vertices'], a['azimuths'], a['elevations'], a['distances'], a['biases'])
-        else:
-            attributes['face_normals'] = _RenderFn.apply(self, False, "geometry", None, a['vertices'], a['textures'], a['lights'], None,
-                                                         a['azimuths'], a['elevations'], a['distances'], a['biases'], 0.0)
+        dev = a['azimuths'].device
+        tex = a['textures']
+        proto, nbytes = self._proto(self._static(dev), a['azimuths'].numel(), False, tex.shape[2], tex.shape[3], 0.0, geometry_only=True)
+        # (the C++ node, csrc/mm_torch_ext.cpp: GeometryNode; it writes no texture records, so check_texture_records has nothing to ask)
+        attributes['face_normals'] = N.torch_ext().render_geometry(N.fn_addr("mm_render_forward"), N.fn_addr("mm_render_backward"), proto, nbytes,
+                                                                   a['vertices'], a['azimuths'], a['elevations'], a['distances'], a['biases'])
         attributes['imnormal'] = None
         return attributes
 
@@ -529,14 +279,11 @@ class DiffRender(object):
 
     # ---- networks.py:364-390 -------------------------------------------------------------------------------------
     def recon_data(self, pred_data, gt_data, no_mask=False, contour=0):
-        ext = N.torch_ext()
-        if ext is None:
-            return _ReconFn.apply(pred_data, gt_data, self.image_weight, contour)
         N.require_device(pred_data, gt_data)
         # (pred_data the untouched image of one of this process's renders: its backward is routed through that render's node -- defer_recon_fusion)
-        return ext.recon_data(N.fn_addr("mm_recon_query_workspace"), N.fn_addr("mm_recon_data_forward"), N.fn_addr("mm_recon_data_backward"),
-                              pred_data, gt_data, float(self.image_weight), float(contour), torch._C._cuda_getCurrentRawStream(pred_data.device.index),
-                              N.fn_addr("mm_recon_data_totals"), bool(self.defer_recon_fusion))
+        return N.torch_ext().recon_data(N.fn_addr("mm_recon_query_workspace"), N.fn_addr("mm_recon_data_forward"), N.fn_addr("mm_recon_data_backward"),
+                                        pred_data, gt_data, float(self.image_weight), float(contour), N.fn_addr("mm_recon_data_totals"),
+                                        bool(self.defer_recon_fusion))
 
     # ---- networks.py:326-362: seven means in one HIP launch per direction (att_loss.py / csrc/mm_attloss.hip); the chamfer
     # variant of the shape term is a HIP nearest-neighbour search + a differentiable gather ----------

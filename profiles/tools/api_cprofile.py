@@ -1,5 +1,5 @@
-"""Where the HOST time of the autograd-API step goes: cProfile over N steps of render -> recon_data -> backward (C++ host path unless
-MM_NO_TORCH_EXT=1), top functions by own time.   python profiles/tools/api_cprofile.py [steps] [fused]"""
+"""Where the HOST time of the autograd-API step goes: cProfile over N steps of render -> recon_data -> backward (the C++ autograd nodes),
+top functions by own time.   python profiles/tools/api_cprofile.py [steps] [fused]"""
 import sys, importlib, os, time, cProfile, pstats, io, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

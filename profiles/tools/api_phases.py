@@ -1,4 +1,4 @@
-"""Host time of the autograd-API step by phase (render / recon_data / backward), C++ host path vs Python path (MM_NO_TORCH_EXT=1)."""
+"""Host time of the autograd-API step by phase (render / recon_data / backward) through the C++ autograd nodes."""
 import sys, importlib, os, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -33,5 +33,5 @@ for imn in (True, False):
     for i in range(n):
         one(i, True)
         if i % 10 == 9: torch.cuda.synchronize()          # keep the queue short: pure enqueue cost, never a full launch queue
-    print("emit_imnormal=%s ext=%s: prep %.1f  render %.1f  recon_data %.1f  backward %.1f us per step" % (
-        imn, pkg._native.torch_ext() is not None, *[1e6 * x / n for x in acc]))
+    print("emit_imnormal=%s: prep %.1f  render %.1f  recon_data %.1f  backward %.1f us per step" % (
+        imn, *[1e6 * x / n for x in acc]))

@@ -105,6 +105,15 @@ def test_host_csr_builders(pkg):
         assert lib.mm_build_vertex_corner_table(V2, F2, f2.ctypes.data_as(ctypes.c_void_p), stride - 1, tab.ctypes.data_as(ctypes.c_void_p)) == -2
 
 
+def test_the_autograd_nodes_extension_loads_and_mirrors_the_descriptor(pkg):
+    """lib/mm_torch_ext.so, the class API's only host path, loads without a GPU and was built against this binding's MMRenderDesc."""
+    N = pkg._native
+    ext = N.torch_ext()
+    assert ext is not None and ext.desc_bytes() == ctypes.sizeof(N.MMRenderDesc)
+    for name in ("render", "recon_data", "render_geometry", "deferrable"):
+        assert callable(getattr(ext, name)), name
+
+
 def test_render_without_gpu_fails_loudly(pkg):
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -24,13 +24,6 @@ def _setup(pkg, name, B, S, ratio=1, seed=0, defer=True, imn=True):
     return dr, datt, gt.to(dev), dev
 
 
-def _ext(pkg):
-    ext = pkg._native.torch_ext()
-    if ext is None or not hasattr(ext, "deferrable"):
-        pytest.skip("mm_torch_ext is not built: the Python nodes never defer")
-    return ext
-
-
 def _grads(datt, no_mask=True):
     return {k: (None if datt[k].grad is None else datt[k].grad.clone()) for k in LEAVES if no_mask or k != "bg"}
 
@@ -47,7 +40,7 @@ def _same(a, b):
 @pytest.mark.parametrize("name,B,S,ratio,no_mask,seed", [("smpl_uv_642", 6, 96, 1, True, 31), ("sphere", 3, 50, 1.4, False, 32),
                                                          ("smpl_uv_642", 48, 128, 1, True, 0)])
 def test_recon_data_on_a_renders_image_is_deferred_and_has_the_separate_passes_bits(pkg, name, B, S, ratio, no_mask, seed):
-    ext = _ext(pkg)
+    ext = pkg._native.torch_ext()
     got = []
     for defer in (False, True):
         dr, datt, gt, dev = _setup(pkg, name, B, S, ratio=ratio, seed=seed, defer=defer)
@@ -64,7 +57,6 @@ def test_recon_data_on_a_renders_image_is_deferred_and_has_the_separate_passes_b
 def test_deferred_recon_data_with_other_consumers_of_the_image_and_of_the_normals(pkg):
     """The image also feeds something else (a discriminator in the trainer), and a regulariser hangs on attributes['face_normals']: the image's
     other gradient arrives as grad_rgba and is ADDED inside the pixel pass -- autograd's own sum, bit for bit."""
-    _ext(pkg)
     got = []
     for defer in (False, True):
         dr, datt, gt, dev = _setup(pkg, "smpl_uv_642", 5, 80, seed=7, defer=defer)
@@ -79,7 +71,7 @@ def test_deferred_recon_data_with_other_consumers_of_the_image_and_of_the_normal
 
 
 def test_only_the_untouched_image_of_a_render_defers_and_everything_else_gives_the_same_numbers(pkg):
-    ext = _ext(pkg)
+    ext = pkg._native.torch_ext()
     ref = None
     cases = ("plain", "off", "clone", "inplace", "contour", "second", "scaled")
     for case in cases:
@@ -115,7 +107,6 @@ def test_only_the_untouched_image_of_a_render_defers_and_everything_else_gives_t
 
 
 def test_a_deferred_loss_that_is_not_differentiated_contributes_nothing_and_backward_twice_works(pkg):
-    _ext(pkg)
     dr, datt, gt, dev = _setup(pkg, "smpl_uv_642", 4, 64, seed=5)
     rgbs, out = dr.render(no_mask=True, **datt)
     loss = dr.recon_data(rgbs, gt, no_mask=True)
@@ -141,22 +132,23 @@ def test_a_deferred_loss_that_is_not_differentiated_contributes_nothing_and_back
     assert float(g1["textures"].abs().max()) > 0
 
 
-def test_the_python_nodes_and_the_deferring_cpp_nodes_agree_bit_for_bit(pkg):
-    N = pkg._native
-    ext = _ext(pkg)
-    got = []
-    try:
-        for use_ext in (True, False):
-            N._EXT = ext if use_ext else None
-            dr, datt, gt, dev = _setup(pkg, "smpl_uv_642", 5, 80, seed=41)
-            rgbs, out = dr.render(no_mask=True, **datt)
-            loss = dr.recon_data(rgbs, gt, no_mask=True) + 1e-3 * out["face_normals"].sum()
-            loss.backward()
-            got.append((loss.detach().clone(), rgbs.detach().clone(), _grads(datt)))
-    finally:
-        N._EXT = ext
-    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
-    _same(got[0][2], got[1][2])
+def test_the_deferring_class_api_and_the_c_abi_step_agree_bit_for_bit(pkg):
+    """The deferred class-API step (render -> recon_data -> backward, one render backward call) against step.RenderLossStep's un-fused step
+    (mm_recon_data_backward writing dL/d image, mm_render_backward reading it), issued from preallocated buffers: same bits."""
+    import importlib
+    stepmod = importlib.import_module("3d-magic-mirror_amd.step")
+    ext = pkg._native.torch_ext()
+    dr, datt, gt, dev = _setup(pkg, "smpl_uv_642", 5, 80, seed=41)
+    ref = stepmod.RenderLossStep(dr, {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in datt.items()}, gt, no_mask=True,
+                                 emit_imnormal=dr.emit_imnormal, fused=False)
+    ref.run()
+    rgbs, out = dr.render(no_mask=True, **datt)
+    assert ext.deferrable(rgbs)
+    loss = dr.recon_data(rgbs, gt, no_mask=True)
+    loss.backward()
+    torch.cuda.synchronize()
+    assert torch.equal(loss.detach(), ref.loss) and torch.equal(rgbs.detach(), ref.rgba.permute(0, 3, 1, 2))
+    _same(_grads(datt), {k: ref.grads[k] for k in LEAVES})
 
 
 def test_deferred_totals_at_the_c_abi(pkg):
@@ -190,7 +182,6 @@ def test_deferred_steps_free_everything_they_held(pkg):
     """The render node keeps the recon_data's target and workspace alive for its backward (the mailbox) -- and lets go of them with the graph: no
     reference cycle through the token (the token tensor is made at recon_data time, not kept by the node).  Device memory in use is flat over steps
     that bring a fresh target each."""
-    _ext(pkg)
     dr, datt, gt, dev = _setup(pkg, "smpl_uv_642", 8, 64, seed=3)
     used = []
     for step in range(24):

@@ -642,32 +642,32 @@ def test_lane_exchange_primitives_on_this_gpu():
     assert out.returncode == 0 and "bad 0" in out.stdout, out.stdout + out.stderr
 
 
-def test_cpp_and_python_host_paths_agree(pkg):
-    """The optional C++ autograd nodes (lib/mm_torch_ext.so) and the Python torch.autograd.Functions issue the same ABI calls: same bits,
-    for render + recon_data and for render_recon."""
-    N = pkg._native
-    if N.torch_ext() is None:
-        pytest.skip("mm_torch_ext is not built")
-    ext, got = N._EXT, []
-    try:
-        for use_ext in (True, False):
-            N._EXT = ext if use_ext else None
-            for fused in (False, True):
-                dr, att, datt, gt, inp, proj, H, W, dev = _setup(pkg, "smpl_uv_642", 5, 80, seed=41)
-                if fused:
-                    loss, rgbs, out = dr.render_recon(gt.to(dev), no_mask=True, **datt)
-                else:
-                    rgbs, out = dr.render(no_mask=True, **datt)
-                    loss = dr.recon_data(rgbs, gt.to(dev), no_mask=True) + 1e-3 * out["face_normals"].sum()
-                loss.backward()
-                got.append((loss.detach().clone(), rgbs.detach().clone(), out["imnormal"].clone(), dr.last_face_idx.clone(),
-                            {k: datt[k].grad.clone() for k in LEAVES}))
-    finally:
-        N._EXT = ext
-    for a, b in ((got[0], got[2]), (got[1], got[3])):
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]) and torch.equal(a[3], b[3])
+def test_class_api_and_c_abi_step_agree(pkg):
+    """The class API's C++ autograd nodes (lib/mm_torch_ext.so) and step.RenderLossStep -- an independent issuer of the same ABI calls against
+    preallocated buffers -- give the same bits: render + recon_data (recon_data's backward deferred into the render node or not) against the
+    un-fused step, render_recon against the fused step; loss, image, imnormal, face_idx and all eight input gradients."""
+    import importlib
+    stepmod = importlib.import_module("3d-magic-mirror_amd.step")
+    for fused, defer in ((False, True), (False, False), (True, True)):
+        dr, att, datt, gt, inp, proj, H, W, dev = _setup(pkg, "smpl_uv_642", 5, 80, seed=41)
+        dr.defer_recon_fusion = defer
+        plain = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in datt.items()}
+        step = stepmod.RenderLossStep(dr, plain, gt.to(dev), no_mask=True, emit_imnormal=dr.emit_imnormal, fused=fused)
+        step.run()
+        if fused:
+            loss, rgbs, out = dr.render_recon(gt.to(dev), no_mask=True, **datt)
+        else:
+            rgbs, out = dr.render(no_mask=True, **datt)
+            assert pkg._native.torch_ext().deferrable(rgbs) == defer
+            loss = dr.recon_data(rgbs, gt.to(dev), no_mask=True)
+        loss.backward()
+        torch.cuda.synchronize()
+        what = (fused, defer)
+        assert torch.equal(loss.detach(), step.loss) and torch.equal(rgbs.detach(), step.rgba.permute(0, 3, 1, 2)), what
+        assert torch.equal(out["imnormal"], step.imnormal) and torch.equal(dr.last_face_idx, step.face_idx), what
         for k in LEAVES:
-            assert torch.equal(a[4][k], b[4][k]), k
+            assert torch.equal(datt[k].grad, step.grads[k]), what + (k,)
+            assert float(datt[k].grad.abs().max()) > 0, what + (k,)
 
 
 def test_recon_data_matches_reference_golden(pkg):
@@ -811,18 +811,13 @@ def test_stress_size_batch_independence_and_four_images_against_oracle(pkg, orac
             _gclose(one[kk].grad.cpu().numpy(), g_o[kk], what=kk)
 
 
-@pytest.mark.parametrize("use_ext", [True, False])
-def test_unused_fused_loss_contributes_no_gradient(pkg, use_ext):
+def test_unused_fused_loss_contributes_no_gradient(pkg):
     """render_recon's loss output is ONE of the node's differentiable outputs.  Differentiating something that does not involve it --
     a regulariser through attributes['face_normals'] alone -- must give exactly what the un-fused render gives: the missing gradient
-    of the loss is zero, not one (both host paths; also under a float64 default dtype, which must not leak into the 4-byte scalar)."""
-    N = pkg._native
-    if use_ext and N.torch_ext() is None:
-        pytest.skip("mm_torch_ext is not built")
-    ext, got = N.torch_ext(), []
+    of the loss is zero, not one (also under a float64 default dtype, which must not leak into the 4-byte scalar)."""
+    got = []
     old = torch.get_default_dtype()
     try:
-        N._EXT = ext if use_ext else None
         torch.set_default_dtype(torch.float64)
         for fused in (False, True):
             dr, att, datt, gt, inp, proj, H, W, dev = _setup(pkg, "smpl_uv_642", 4, 64, seed=5)
@@ -838,7 +833,6 @@ def test_unused_fused_loss_contributes_no_gradient(pkg, use_ext):
                 g_both = {k: datt[k].grad.clone() for k in LEAVES}
             got.append((g_reg, g_both if fused else None))
     finally:
-        N._EXT = ext
         torch.set_default_dtype(old)
     for k in LEAVES:
         a, b = got[0][0][k], got[1][0][k]
@@ -1031,32 +1025,23 @@ def test_unfused_contour_backward_matches_the_oracle_and_is_bitwise_reproducible
     np.testing.assert_allclose(grads[0].cpu().numpy(), dpo, rtol=1e-4, atol=1e-9)
 
 
-@pytest.mark.parametrize("use_ext", [True, False])
-def test_camera_scalars_of_shape_B_by_1_get_gradients_of_their_own_shape(pkg, use_ext):
+def test_camera_scalars_of_shape_B_by_1_get_gradients_of_their_own_shape(pkg):
     """azimuths / elevations / distances arrive as (B,1) from some callers (a Linear head's output): the kernels see (B), the gradients must come
     back as (B,1) -- autograd rejects a (B) gradient for a (B,1) input (advisor r05) -- with the bits of the (B) call; render and render_geometry."""
-    N = pkg._native
-    if use_ext and N.torch_ext() is None:
-        pytest.skip("mm_torch_ext is not built")
-    ext = N.torch_ext()
-    try:
-        N._EXT = ext if use_ext else None
-        got = []
-        for col in (False, True):
-            dr, att, datt, gt, inp, proj, H, W, dev = _setup(pkg, "smpl_uv_642", 3, 64, seed=9)
-            if col:
-                for k in ("azimuths", "elevations", "distances"):
-                    datt[k] = datt[k].detach().reshape(-1, 1).requires_grad_(True)
-            rgbs, out = dr.render(no_mask=True, **datt)
-            geo = dr.render_geometry(**{k: v for k, v in datt.items()})
-            (dr.recon_data(rgbs, gt.to(dev), no_mask=True) + 1e-3 * geo["face_normals"].sum()).backward()
+    got = []
+    for col in (False, True):
+        dr, att, datt, gt, inp, proj, H, W, dev = _setup(pkg, "smpl_uv_642", 3, 64, seed=9)
+        if col:
             for k in ("azimuths", "elevations", "distances"):
-                assert datt[k].grad.shape == datt[k].shape, (k, datt[k].grad.shape)
-            got.append({k: datt[k].grad.reshape(-1).clone() for k in ("azimuths", "elevations", "distances", "vertices")})
-        for k in got[0]:
-            assert torch.equal(got[0][k], got[1][k]), k
-    finally:
-        N._EXT = ext
+                datt[k] = datt[k].detach().reshape(-1, 1).requires_grad_(True)
+        rgbs, out = dr.render(no_mask=True, **datt)
+        geo = dr.render_geometry(**{k: v for k, v in datt.items()})
+        (dr.recon_data(rgbs, gt.to(dev), no_mask=True) + 1e-3 * geo["face_normals"].sum()).backward()
+        for k in ("azimuths", "elevations", "distances"):
+            assert datt[k].grad.shape == datt[k].shape, (k, datt[k].grad.shape)
+        got.append({k: datt[k].grad.reshape(-1).clone() for k in ("azimuths", "elevations", "distances", "vertices")})
+    for k in got[0]:
+        assert torch.equal(got[0][k], got[1][k]), k
 
 
 def test_a_geometry_only_render_asks_for_the_vertex_stages_workspace_alone(pkg):

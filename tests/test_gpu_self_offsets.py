@@ -23,8 +23,8 @@ import numpy as np, torch
 sys.path.insert(0, sys.argv[1])
 pkg = importlib.import_module("3d-magic-mirror_amd")
 if sys.argv[3] != "-":
-    pkg._native.LIB_PATH = sys.argv[3]
-    os.environ["MM_NO_TORCH_EXT"] = "1"            # (the extension links the product library; the Python nodes issue the same ABI calls)
+    pkg._native.LIB_PATH = sys.argv[3]                # (the C++ nodes resolve every library function through _native.lib(): this build)
+    assert pkg._native.lib()._name == sys.argv[3]
 dev = torch.device("cuda:0")
 out = {}
 for name, B, S in (("sphere", 3, 64), ("smpl_uv_642", 4, 128)):
