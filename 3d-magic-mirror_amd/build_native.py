@@ -59,7 +59,7 @@ def build(force=False, verbose=False, out=None, extra_flags=None):
     import fcntl
     import shutil
     import tempfile
-    target = out or LIB                                          # out: a variant build (profiles/tools), e.g. lib/libmm_timeline.so
+    target = out or LIB                                          # out: a variant build, e.g. TEST_LIB_SELF_OFFSETS or one of profiles/tools
     if out is None and not force and not needs_build():
         return LIB
     os.makedirs(os.path.dirname(LIB), exist_ok=True)

@@ -18,12 +18,7 @@
 //         knum silhouette faces give K4; hits are ballot-compacted over the wave and finished by all 64 lanes into INT64 fixed-point per-item
 //         LDS sums; one plain store per item, added up per face in index order by the vertex backward.
 //   Integer adds commute exactly: the whole backward is bitwise reproducible.
-#include <cstdlib>
 #include "mm_backward.h"
-
-MM_TIMELINE_STORAGE(gather_bwd)
-MM_PP_STORAGE(gather_face)      // 0 setup, 1 sweep (face_idx loads), 2 compaction, 3 item loads, 4 item arithmetic + LDS adds, 5 stores; counts: trips, items
-MM_PP_STORAGE(gather_tex)       // 0 count + first record, 1 clear, 2 records, 3 tile store; counts: records
 
 #ifndef MM_ITEM_UNROLL
 #define MM_ITEM_UNROLL 1        // hit items per lane whose loads are in flight together.  2 (as up to r02i) hides a trip per 128 hits but costs ten VGPRs: at 64
@@ -190,12 +185,10 @@ __device__ inline void texture_gather_block(const BwdArgs& a, int block, int (*s
     map_block(block, a.B, ntiles, b, T);
     const int tid = threadIdx.x;
     const int tx0 = (T % a.ntx) * MM_TS, ty0 = (T / a.ntx) * MM_TS;
-    MM_PP_BEGIN();
     const int nall = a.tcur[(size_t)b * ntiles + T], off = a.toff[(size_t)b * ntiles + T] - 1;
     const int dropped = a.tdrop[b];                            // records of the image its array had no room for (pixel_bwd)
     const int nrec = max(0, min(nall, a.trcap - off));           // (the list is cut where the array ends)
     const TexRecord* recs = a.trec + (size_t)b * a.trcap + off;
-    MM_PP_MARK(0);
     // largest contribution of the tile's records (first pass; the second one below re-reads them from L2)
     float mx = 0.f;
     for (int r = tid; r < nrec; r += 256) mx = fmaxf(mx, tex_record_max(recs[r]));
@@ -204,7 +197,6 @@ __device__ inline void texture_gather_block(const BwdArgs& a, int block, int (*s
     for (int i = tid; i < 3 * MM_TS * MM_TS / 4; i += 256) ((int4*)&s_acc[0][0])[i] = make_int4(0, 0, 0, 0);   // (16-byte LDS stores)
     __syncthreads();
     mx = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    MM_PP_MARK(1);
     float inv = 0.f;
     if (mx > 0.f && mx < INFINITY) {                             // workgroup-uniform; nothing to add up otherwise (about half of all tiles)
         int e;
@@ -222,8 +214,6 @@ __device__ inline void texture_gather_block(const BwdArgs& a, int block, int (*s
             if (a.status_flag) __hip_atomic_fetch_add(a.status_flag, dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (the host may be polling it)
         }
     }
-    MM_PP_MARK(2);
-    MM_PP_COUNT(nrec, 0);
     // write the tile once (also where nothing landed: no separate zero-fill of grad_textures): four texels of a row per thread and store
     if ((a.Wt & 3) == 0 && (((size_t)a.grad_textures) & 15) == 0) {
         for (int i = tid; i < 3 * MM_TS * MM_TS / 4; i += 256) {
@@ -244,8 +234,6 @@ __device__ inline void texture_gather_block(const BwdArgs& a, int block, int (*s
             if (x < a.Wt && y < a.Ht) a.grad_textures[(((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x] = (float)s_acc[c][r] * inv;
         }
     }
-    MM_PP_MARK(3);
-    MM_PP_FLUSH(gather_tex, (long long)block * 4 + (threadIdx.x >> 6));
 }
 
 struct ItemLoad { float4 q0, q1; float q2, sq; int lf, px, py, g; bool owned, live; };
@@ -264,7 +252,7 @@ __device__ inline void item_finish(const BwdArgs& a, FaceSlot& fs, const ItemLoa
     const int bm = box_mode(a.options);
     const bool inbox = bm ? !(box_reject(x0, fs.box[0] - a.infl, fs.box[2] + a.infl, bm) || box_reject(y0, fs.box[1] - a.infl, fs.box[3] + a.infl, bm))
                           : !(x0 < fs.box[0] - a.infl || x0 > fs.box[2] + a.infl || y0 < fs.box[1] - a.infl || y0 > fs.box[3] + a.infl);
-    if (sq != 0.f && (MM_K4_KEEP_ONES || sq != 1.f) && ga != 0.f && fs.f <= ld.lf && inbox) {
+    if (sq != 0.f && ga != 0.f && fs.f <= ld.lf && inbox) {
         const float4 p0 = fs.p0, p1 = fs.p1;
         const f2 pp = {x0, y0}, ca = {p0.x, p0.y}, cb = {p0.z, p0.w}, cc = {p1.x, p1.y};
         SegHit h = seg_nearest(pp, ca, cb);               // edge 0: corner a -> b
@@ -297,7 +285,7 @@ __device__ inline void item_finish(const BwdArgs& a, FaceSlot& fs, const ItemLoa
 //     ballot-compacted over the whole wave and finished by all 64 lanes (one round of loads per trip) into the per-face
 //     fixed-point LDS sums.  This lane's face is `f` of image `b`, and its group sweeps box pixels [lo, hi) of it.
 template <int FL>
-__device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, int f, int lane, const FaceBox& fb, int lo, int hi, float scale MM_PP_ARG) {
+__device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, int f, int lane, const FaceBox& fb, int lo, int hi, float scale) {
     const int grp = lane / FL, sl = lane % FL;
     const size_t hw = (size_t)a.H * a.W;
     const float s2 = a.mult * a.mult;
@@ -313,7 +301,6 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
     nmax = max(nmax, (int)lane_xchg<16>((unsigned)nmax, lane)); nmax = max(nmax, (int)lane_xchg<32>((unsigned)nmax, lane));
     static_assert(FL == 16 || FL == 8 || FL == 4, "the exchange strides above start at the lanes-per-item count");
     wave_sync_lds();
-    MM_PP_MARK(0);
 
     // A lane's pixels of a trip are MM_FL apart in the row-major box: the first one by division, the others by stepping (column += MM_FL mod
     // width, row += MM_FL div width, one wrap at most) -- five instructions instead of the twelve of a division, sixteen times per trip.
@@ -334,13 +321,10 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
             col += step_c; off += step_off;
             if (col >= fb.bw) { col -= fb.bw; off += wrap_off; }
         }
-        MM_PP_MARK(1);
         // one compacted item list for both kinds of hit: pixels these faces own (K2: add the pixel pass's contributions)
         // and uncovered pixels that may hold one of these faces among their first knum soft-mask faces (K4, Appendix A.2)
         const int n = compact_hits(own, opn, lane, st->items);
         wave_sync_lds();
-        MM_PP_MARK(2);
-        MM_PP_COUNT(1, n);
         // MM_ITEM_UNROLL items per lane and trip (each round is a dependent trip to memory; see the macro for why it is 1)
         for (int j0 = 0; j0 < n; j0 += 64 * MM_ITEM_UNROLL) {
             ItemLoad ld[MM_ITEM_UNROLL];
@@ -364,7 +348,6 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
                     else { const float2 sl2 = a.soft[pix]; ld[u].sq = sl2.x; ld[u].lf = __float_as_int(sl2.y); }
                 }
             }
-            MM_PP_MARK(3);
 #pragma unroll
             for (int u = 0; u < MM_ITEM_UNROLL; ++u) {
                 if (u >= 1 && j0 + 64 * u >= n) break;
@@ -372,7 +355,6 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
             }
         }
         wave_sync_lds();
-        MM_PP_MARK(4);
     }
 }
 
@@ -404,13 +386,10 @@ __device__ inline void face_gather_block(const BwdArgs& a, int block, SweepStage
     // MM_OPT_SOFT_SKIP_CULLED: a culled face owns no pixel and took no part in the soft mask -> nothing to sweep
     const bool front = (a.options & MM_OPT_CULL_STRICT) ? fb.nz > 0.f : fb.nz >= 0.f;
     const int hi = live && (front || !(a.options & MM_OPT_SOFT_SKIP_CULLED)) ? min(fb.npx, lo + ni.y) : lo;
-    MM_PP_BEGIN();
     float inv;
     const float scale = face_sum_scale(a, b, ni.y, inv);
-    face_sweep(a, st, b, e.x, lane, fb, lo, hi, scale MM_PP_PASS);
+    face_sweep(a, st, b, e.x, lane, fb, lo, hi, scale);
     if (live) for (int k = sl; k < 9; k += FL) a.part[((size_t)b * a.item_cap + item) * 12 + k] = (float)st->slot[grp].acc[k] * inv;
-    MM_PP_MARK(5);
-    MM_PP_FLUSH(gather_face, wid);
 }
 
 // (this wave's part of the value; networks.py:376-389: image_weight * loss_image + 1 * (loss_mask + contour * loss_contour))
@@ -434,12 +413,7 @@ __device__ inline float fused_loss_value(const long long* ltot, int B, int H, in
 #define MM_GATHER_LB 8            // waves per SIMD the register allocation is held to (64 VGPRs, no spills)
 #endif
 template <int FL>
-__global__ __launch_bounds__(256, MM_GATHER_LB) void gather_bwd_kernel(BwdArgs a, int ntex, int dbg_skip) {
-    MM_TIMELINE_BEGIN();
-#ifdef MM_PHASE_PROF                                            // timing experiments only (results are wrong): leave one kind of workgroup out
-    if ((dbg_skip & 1) && (int)blockIdx.x < ntex) return;
-    if ((dbg_skip & 2) && (int)blockIdx.x >= ntex) return;
-#endif
+__global__ __launch_bounds__(256, MM_GATHER_LB) void gather_bwd_kernel(BwdArgs a, int ntex) {
     // the two kinds of workgroup never coexist in one workgroup: their LDS is overlaid (more workgroups per CU)
     constexpr size_t kLds = sizeof(float) * 3 * MM_TS * MM_TS > sizeof(SweepStageT<FL>) * 4 ? sizeof(float) * 3 * MM_TS * MM_TS : sizeof(SweepStageT<FL>) * 4;
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kLds];
@@ -455,7 +429,6 @@ __global__ __launch_bounds__(256, MM_GATHER_LB) void gather_bwd_kernel(BwdArgs a
     // the earlier start of the slowest workgroups gains.
     if ((int)blockIdx.x < ntex) texture_gather_block(a, blockIdx.x, s_acc);
     else face_gather_block(a, blockIdx.x - ntex, s_stage);
-    MM_TIMELINE_END(gather_bwd);
 }
 
 // the fused recon_data value on its own (mm_render_fused_loss): the same fixed-order sum over images the gather kernel's last
@@ -506,12 +479,8 @@ int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Works
         const int fpw = fl4 ? 16 : MM_FPW;
         const long long nwaves = (long long)d->B * ((w.item_cap + fpw - 1) / fpw);          // (item group, image), sized for the cap: waves
         const unsigned nface = (unsigned)((nwaves + 3) / 4);                                // beyond an image's item count exit at once
-        int dbg_skip = 0;
-#ifdef MM_PHASE_PROF
-        if (const char* e = getenv("MM_DBG_GATHER")) dbg_skip = atoi(e);
-#endif
-        if (fl4) hipLaunchKernelGGL(gather_bwd_kernel<4>, dim3(ntex + nface), dim3(256), 0, s, a, ntex, dbg_skip);
-        else hipLaunchKernelGGL(gather_bwd_kernel<MM_FL>, dim3(ntex + nface), dim3(256), 0, s, a, ntex, dbg_skip);
+        if (fl4) hipLaunchKernelGGL(gather_bwd_kernel<4>, dim3(ntex + nface), dim3(256), 0, s, a, ntex);
+        else hipLaunchKernelGGL(gather_bwd_kernel<MM_FL>, dim3(ntex + nface), dim3(256), 0, s, a, ntex);
     }
     return launch_ok("raster_bwd");
 }

@@ -13,19 +13,11 @@
 
 #define MM_WAVE 64
 // MM_FP_EXACT at the head of a block: every fp32 expression inside rounds as written, whatever the translation unit's flags (the relaxed backward
-// includes these functions too).  -DMM_ALLOW_CONTRACT (bound experiments only, wrong bits): the block follows the translation unit's flags.
-#ifdef MM_ALLOW_CONTRACT
-#define MM_FP_EXACT
-#else
+// includes these functions too).
 #define MM_FP_EXACT _Pragma("clang fp contract(off)")
-#endif
 // a value that is the same in all lanes of the wave BY CONSTRUCTION (derived from threadIdx.x >> 6 and the like), said so: the compiler then
-// keeps it in a scalar register, and what is addressed by it becomes scalar arithmetic and scalar-cache loads.  -DMM_NO_SCALAR_WAVE: A/B switch.
-#ifdef MM_NO_SCALAR_WAVE
-#define MM_WAVE_UNIFORM(x) (x)
-#else
+// keeps it in a scalar register, and what is addressed by it becomes scalar arithmetic and scalar-cache loads.
 #define MM_WAVE_UNIFORM(x) __builtin_amdgcn_readfirstlane((int)(x))
-#endif
 #define MM_TILE 8             // a wave owns an 8x8 pixel tile, one lane per pixel
 #define MM_BLOCK_PX 16        // a 256-thread workgroup renders a 16x16 pixel block: 2x2 wave tiles
 #define MM_BLOCK_WAVES 4
@@ -71,17 +63,14 @@ struct TexRecord { unsigned xy; float tx, ty, d0, d1, d2; };       // xy = x0 | 
 // surface lands in a few tiles of the texture (a close-up puts four fifths of an image's records into one of 128).
 // which form of the forward walk a shape gets (mm_raster_walk.h): the compacting queue (+ the face flags the backward's sweep plan reads) for
 // screen bins larger than a tile, the per-batch walk for 8-pixel bins; MM_OPT_WALK_QUEUE / MM_OPT_WALK_BATCH force one (identical results)
-#ifndef MM_BATCH_FLAGS
-#define MM_BATCH_FLAGS 0     // 1: the per-batch walk (8-pixel bins) flags the faces that receive gradient, like the compacting walk -- built and measured in r06: raster_fwd +2.5-3 us, gather_bwd -1.4 us at 128x128 (profiles/r06_batch_walk_flags_ab.md): off
-#endif
-inline bool walk_flags_mode(int options, int bin_shift);
 inline bool walk_queue_mode(int options, int bin_shift) {
     if (options & MM_OPT_WALK_QUEUE) return true;
     if (options & MM_OPT_WALK_BATCH) return false;
     return bin_shift != 3;
 }
-// does the forward walk of this shape leave face flags (Workspace::fflag) for the backward's sweep plan?
-inline bool walk_flags_mode(int options, int bin_shift) { return MM_BATCH_FLAGS ? true : walk_queue_mode(options, bin_shift); }
+// does the forward walk of this shape leave face flags (Workspace::fflag) for the backward's sweep plan?  Only the compacting walk: flags from
+// the per-batch walk cost raster_fwd 2.5-3 us to save gather_bwd 1.4 us at 128x128 (r06, profiles/r06_batch_walk_flags_ab.md)
+inline bool walk_flags_mode(int options, int bin_shift) { return walk_queue_mode(options, bin_shift); }
 
 // ---- workspace carving (all offsets multiples of 256 bytes) ---------------------------------------------------------
 struct Workspace {
@@ -135,19 +124,17 @@ struct Workspace {
 
 __host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// K4 (silhouette backward: mm_backward.hip, mm_dibr.hip): a pixel whose stored product is EXACTLY 1 took only faces whose factor 1 - exp(-sigma d^2) rounds to 1 in fp32 (exp below 2^-24:
+// the forward's alpha is 0 to the last bit).  Their derivative terms are not zero, only < 6e-8 of a term at exp ~ 0.5.  Rounds 1-4 skipped such pixels;
+// since round 5 they are evaluated like any other: in an image that shows NOTHING ELSE -- a far-away mesh on an 8x8 screen -- they are the
+// whole geometry gradient, which the scale-aware parity bar sees (fuzz case 82 of seed 6106), and the skip bought no time (profiles/r05_k4_ones_ab.md).
+
 // Small templates in LARGE batches: the vertex backward as one workgroup per image, face-major then vertex-major through LDS
 // (vertex_image_bwd_kernel: no ticket, no partial-row round trip).  One workgroup = one CU's load / store pipeline per image: with
 // fewer images than a fraction of the chip's 256 CUs the 8-lanes-per-vertex grid of vertex_bwd_kernel (21 workgroups per image) is as
 // fast or faster (B=48: 16.2 vs 16.1 us at 128x128, 28.5 vs 18.0 at 256x256 where faces have several sweep items); at B=384 it is 29.6
 // against 52.5 us (profiles/r04_per_image_stages_ab.md).
 #define MM_VIMG_BWD_MAX_FACES 1700
-// K4 (silhouette backward): a pixel whose stored product is EXACTLY 1 took only faces whose factor 1 - exp(-sigma d^2) rounds to 1 in fp32 (exp below 2^-24:
-// the forward's alpha is 0 to the last bit).  Their derivative terms are not zero, only < 6e-8 of a term at exp ~ 0.5.  Rounds 1-4 skipped such pixels
-// (MM_K4_KEEP_ONES 0); since round 5 they are evaluated like any other: in an image that shows NOTHING ELSE -- a far-away mesh on an 8x8 screen -- they are the
-// whole geometry gradient, which the scale-aware parity bar sees (fuzz case 82 of seed 6106), and the skip bought no time (profiles/r05_k4_ones_ab.md).
-#ifndef MM_K4_KEEP_ONES
-#define MM_K4_KEEP_ONES 1
-#endif
 #ifndef MM_VIMG_BWD_MIN_B
 #define MM_VIMG_BWD_MIN_B 128
 #endif
@@ -307,12 +294,8 @@ MM_FP_EXACT
 }
 __device__ inline float soft_factor(float x0, float y0, const float4& p0, const float4& p1, float sig2) {
 MM_FP_EXACT
-#ifdef MM_BOUND_SOFT1                                           // (bound experiment, WRONG results: one edge instead of three)
-    const float d = seg_dist2_fast(x0, y0, p0.x, p0.y, p0.z, p0.w);
-#else
     const float d = fminf(fminf(seg_dist2_fast(x0, y0, p0.x, p0.y, p0.z, p0.w), seg_dist2_fast(x0, y0, p0.z, p0.w, p1.x, p1.y)),
                           seg_dist2_fast(x0, y0, p1.x, p1.y, p0.x, p0.y));
-#endif
     return 1.f - __builtin_amdgcn_exp2f(-(d * sig2) * 1.4426950408889634f);
 }
 // pixel centre from the host-formed factor k = multiplier / W (or / H): the same float as pixel_x / pixel_y in a translation unit with
@@ -367,12 +350,7 @@ __device__ inline void bary_weights(float ax, float ay, float bx, float by, floa
                                     float& w0, float& w1, float& w2, float& nrm) {
     if (!one_minus) {
         edge_weights(ax, ay, bx, by, cx, cy, x0, y0, eps, w0, w1, w2, nrm);
-#ifdef MM_BOUND_FASTDIV                                         // (bound experiment, WRONG bits: one hardware reciprocal instead of three IEEE divisions)
-        const float r = __builtin_amdgcn_rcpf(nrm);
-        w0 *= r; w1 *= r; w2 *= r;
-#else
         w0 /= nrm; w1 /= nrm; w2 /= nrm;
-#endif
         return;
     }
     float aex = ax - x0, aey = ay - y0, bex = bx - x0, bey = by - y0, cex = cx - x0, cey = cy - y0;
@@ -458,69 +436,6 @@ struct ProfScope {
     ProfScope(void** e, int sl, hipStream_t st) : ev(e), slot(sl), s(st) { if (ev) (void)hipEventRecord((hipEvent_t)ev[2 * slot], s); }
     ~ProfScope() { if (ev) (void)hipEventRecord((hipEvent_t)ev[2 * slot + 1], s); }
 };
-
-// -DMM_TIMELINE (debug builds, profiles/tools/timeline.py): wall-clock begin / end of every workgroup of a kernel, 100 MHz ticks
-// comparable across CUs.  MM_TIMELINE_STORAGE(name) in the kernel's translation unit defines the buffer and its C getter
-// mm_debug_timeline_<name>(out[MM_TIMELINE_MAX][2]).  Everything compiles to nothing otherwise.
-#ifdef MM_TIMELINE
-#define MM_TIMELINE_MAX 81920
-// third word: where the workgroup's first wave ran -- HW_REG_HW_ID (gfx9 layout: wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]) in the
-// low half, HW_REG_XCC_ID [3:0] (the XCD) in the high half: profiles/tools/timeline.py turns it into the per-CU placement of the launch
-#define MM_TIMELINE_STORAGE(name)                                                                                         \
-    namespace mm { __device__ unsigned long long g_tl_##name[MM_TIMELINE_MAX][3]; }                                          \
-    extern "C" int mm_debug_timeline_##name(unsigned long long* out) {                                                       \
-        return hipMemcpyFromSymbol(out, HIP_SYMBOL(mm::g_tl_##name), sizeof(unsigned long long) * MM_TIMELINE_MAX * 3) == hipSuccess ? 0 : -1; \
-    }
-#define MM_TIMELINE_BEGIN() const unsigned long long tl_begin_ = wall_clock64()
-#define MM_TIMELINE_END(name) do { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x < MM_TIMELINE_MAX) {                 \
-    mm::g_tl_##name[blockIdx.x][0] = tl_begin_; mm::g_tl_##name[blockIdx.x][1] = wall_clock64();                             \
-    mm::g_tl_##name[blockIdx.x][2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |                         \
-                                     ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (3 << 11)) << 32); } } while (0)
-#else
-#define MM_TIMELINE_STORAGE(name)
-#define MM_TIMELINE_BEGIN() do { } while (0)
-#define MM_TIMELINE_END(name) do { } while (0)
-#endif
-
-// -DMM_PHASE_PROF (debug builds, profiles/tools/phase_prof.py): per-wave wall-clock totals of a kernel's phases.  A PhaseProf object
-// accumulates the time between successive mark(i) calls into slot i (every mark first waits for everything the wave has issued,
-// so a phase is charged with the latency of its own loads; that serialisation is why this is a debug build only) and flush()
-// stores the slots + the wave's total + two free counters.  MM_PP_STORAGE(name) in the kernel's translation unit defines the
-// buffer and its C getter mm_debug_pp_<name>(out[MM_PP_MAX][MM_PP_SLOTS + 3]).  Compiles to nothing otherwise.
-#ifdef MM_PHASE_PROF
-#define MM_PP_MAX 16384
-#define MM_PP_SLOTS 10
-#define MM_PP_STORAGE(name)                                                                                               \
-    namespace mm { __device__ unsigned long long g_pp_##name[MM_PP_MAX][MM_PP_SLOTS + 3]; }                                  \
-    extern "C" int mm_debug_pp_##name(unsigned long long* out) {                                                             \
-        return hipMemcpyFromSymbol(out, HIP_SYMBOL(mm::g_pp_##name), sizeof(unsigned long long) * MM_PP_MAX * (MM_PP_SLOTS + 3)) == hipSuccess ? 0 : -1; \
-    }
-struct PhaseProf {
-    unsigned long long t0, t, acc[MM_PP_SLOTS], c0, c1;
-    __device__ PhaseProf() : c0(0), c1(0) {
-        for (int i = 0; i < MM_PP_SLOTS; ++i) acc[i] = 0;
-        t0 = t = wall_clock64();
-    }
-    __device__ void mark(int i) { __builtin_amdgcn_s_waitcnt(0); const unsigned long long n = wall_clock64(); acc[i] += n - t; t = n; }
-    __device__ void count(unsigned long long a, unsigned long long b) { c0 += a; c1 += b; }
-};
-#define MM_PP_BEGIN() mm::PhaseProf pp_
-#define MM_PP_MARK(i) pp_.mark(i)
-#define MM_PP_COUNT(a, b) pp_.count(a, b)
-#define MM_PP_ARG , mm::PhaseProf& pp_
-#define MM_PP_PASS , pp_
-#define MM_PP_FLUSH(name, wave_index) do { const long long wi_ = (wave_index); if ((threadIdx.x & 63) == 0 && wi_ < MM_PP_MAX) {     \
-    for (int i_ = 0; i_ < MM_PP_SLOTS; ++i_) mm::g_pp_##name[wi_][i_] = pp_.acc[i_];                                          \
-    mm::g_pp_##name[wi_][MM_PP_SLOTS] = wall_clock64() - pp_.t0; mm::g_pp_##name[wi_][MM_PP_SLOTS + 1] = pp_.c0; mm::g_pp_##name[wi_][MM_PP_SLOTS + 2] = pp_.c1; } } while (0)
-#else
-#define MM_PP_STORAGE(name)
-#define MM_PP_BEGIN() do { } while (0)
-#define MM_PP_MARK(i) do { } while (0)
-#define MM_PP_COUNT(a, b) do { } while (0)
-#define MM_PP_ARG
-#define MM_PP_PASS
-#define MM_PP_FLUSH(name, wave_index) do { } while (0)
-#endif
 
 // launch check shared by every launcher: the HIP error (if any) is kept per host thread for mm_last_error_detail()
 struct LaunchError { hipError_t code; const char* what; };
@@ -653,9 +568,6 @@ __device__ inline void face_pixel_box(float ax, float ay, float bx, float by, fl
 __host__ __device__ inline int sweep_shrink(float boxlen, int n) { const int s = (int)(boxlen * (float)n * 0.5f) - 1; return s > 0 ? s : 0; }
 __host__ __device__ inline void sweep_box(unsigned org, unsigned ext, bool taken, int sx, int sy, int W, int H, int& px0, int& py0, int& bw, int& bh) {
     px0 = (int)(org & 0xFFFFu); py0 = (int)(org >> 16); bw = (int)(ext & 0xFFFFu); bh = (int)(ext >> 16);
-#ifdef MM_DBG_NO_INFLATE                                        // (timing experiment only, results WRONG: every face swept over its own box -- what the K4 sweeps of the
-    taken = false;                                               //  inflated boxes cost, profiles/r05_gather_k4_bound.md)
-#endif
     if (taken || bw <= 0 || bh <= 0) return;
     const int l = px0 > 0 ? sx : 0, r = px0 + bw < W ? sx : 0, t = py0 > 0 ? sy : 0, b = py0 + bh < H ? sy : 0;
     if (bw - l - r <= 0 || bh - t - b <= 0) return;               // (cannot happen for a face that owns a pixel; never sweep nothing on a rounding doubt)

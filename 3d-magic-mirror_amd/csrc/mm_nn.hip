@@ -42,8 +42,9 @@ __device__ inline nn_f2 nn_dist2(nn_f2 px, nn_f2 py, nn_f2 pz, float qx, float q
 typedef float nn_f16 __attribute__((ext_vector_type(16)));
 typedef float nn_f8 __attribute__((ext_vector_type(8)));
 // eight points = 24 dwords into scalar registers, WITHOUT waiting for them (the compiler's own scalar loads are followed by their wait at
-// once; here the next group's points travel while this group's are measured).  nn_swait is the wait, and because it names the registers
-// as in/out operands no use of them can be scheduled above it.
+// once, even from a hand-pipelined loop; here the next group's points travel while this group's are measured: B=48 642x642, one direction,
+// 6.6 us against 8.1 for plain C++ loads).  nn_swait is the wait, and because it names the registers as in/out operands no use of them can
+// be scheduled above it.
 __device__ inline void nn_sload(nn_f16& a, nn_f8& b, const float* p) {
     asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %2, 0x40" : "=&s"(a), "=&s"(b) : "s"(p));
     __builtin_amdgcn_sched_barrier(0);                            // (the arithmetic of the group in hand stays BEHIND the request)
@@ -93,7 +94,6 @@ __global__ __launch_bounds__(64 * MM_NN_WAVES) void nn_pair_kernel(int N, int M,
     };
     static_assert(MM_NN_GROUP == 8, "nn_min8");
     const int gend = min(g1, nfull);
-#if !defined(MM_NN_NO_PREFETCH)
     if (g0 < gend) {
         nn_f16 a16, b16; nn_f8 a8, b8;
         auto take_v = [&](const nn_f16& v16, const nn_f8& v8, int g) {
@@ -115,15 +115,6 @@ __global__ __launch_bounds__(64 * MM_NN_WAVES) void nn_pair_kernel(int N, int M,
         }
         nn_swait(a16, a8);                                        // (the last request lands before its registers are anything else's)
     }
-#else                                                            // plain C++ (the compiler's scalar loads, each followed by its wait): B=48 642x642 one direction
-    for (int g = g0; g < gend; ++g) {                            // 8.1 us against 6.6 (a hand-pipelined plain-C++ loop compiles to the same waits)
-        float q[3 * MM_NN_GROUP];
-        const float* __restrict__ p = os + (size_t)g * (3 * MM_NN_GROUP);
-#pragma unroll
-        for (int k = 0; k < 3 * MM_NN_GROUP; ++k) q[k] = p[k];     // wave-uniform address, read-only memory: scalar loads
-        take(q, g);
-    }
-#endif
     if (g1 == ng && nfull < ng && g0 < g1) {                      // (wave-uniform) the partial group: points beyond the cloud are infinitely far
         float q[3 * MM_NN_GROUP];
 #pragma unroll

@@ -2,9 +2,6 @@
 // this half is compiled with the forward's floating-point flags).
 #include "mm_backward.h"
 
-MM_TIMELINE_STORAGE(pixel_bwd)
-MM_PP_STORAGE(pixel_bwd)        // 0 loss totals + g4, 1 shading recompute + stores, 2 record append, 3 dlights reduction
-
 namespace mm {
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -133,7 +130,6 @@ __device__ inline void plan_sweep_items(const BwdArgs& a, int b, int q) {
 // that kernel would have written -- plus the caller's grad_rgba if there is one.  Never together with kContour.
 template <bool kNoMask, bool kContour, bool kDeferred>
 __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) {
-    MM_TIMELINE_BEGIN();
     __shared__ float s_dl[MM_BLOCK_WAVES][9];
     __shared__ float s_gm[MM_BLOCK_WAVES][2];
     if ((int)blockIdx.x < a.plan_wgs * a.B) { plan_sweep_items(a, blockIdx.x / a.plan_wgs, blockIdx.x % a.plan_wgs); return; }   // (workgroup-uniform)
@@ -471,7 +467,6 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     if (threadIdx.x < 9)
         a.dl_part[((size_t)b * a.blocks_per_image + blk) * 12 + threadIdx.x] =
             ((s_dl[0][threadIdx.x] + s_dl[1][threadIdx.x]) + s_dl[2][threadIdx.x]) + s_dl[3][threadIdx.x];
-    MM_TIMELINE_END(pixel_bwd);
 }
 
 int launch_pixel_bwd(const BwdArgs& a, const MMRenderDesc* d, hipStream_t s) {

@@ -25,9 +25,6 @@
 #include "mm_raster_walk.h"
 #include "mm_order.h"
 
-MM_TIMELINE_STORAGE(raster_fwd)
-MM_PP_STORAGE(raster_fwd)       // 0 tile setup, 1 mask -> id list, 2 fetch + stage + box tests + transposes, 3 colour pairs, 4 silhouette pairs, 5 shade + store, 6 / 7 coop barriers, 8 first mask load (latency alone), 9 first record fetch of a window (latency alone)
-
 namespace mm {
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -43,7 +40,7 @@ namespace mm {
 // kContour: the fused loss carries recon_data's contour term (host: fused_gt && fused_contour > 0)
 template <bool kNoMask, bool kBlock, bool kQueue, bool kContour>
 __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_eu(MM_RASTER_WPE, MM_RASTER_WPE))) void raster_fwd_kernel(RasterArgs a_) {   // kBlock: 5 waves per SIMD = 96 VGPRs, 5 x 32 KiB LDS per CU
-#if defined(MM_ARGS_BY_VALUE) || !defined(__HIP_DEVICE_COMPILE__)
+#ifndef __HIP_DEVICE_COMPILE__
     const RasterArgs& a = a_;
 #else
     // The arguments are READ FROM THE KERNARG SEGMENT WHERE THEY ARE USED (scalar loads from constant memory, through the scalar cache) instead of
@@ -52,9 +49,7 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
     (void)a_;
     const RasterArgs& a = *(const RasterArgs*)__builtin_amdgcn_kernarg_segment_ptr();   // (the kernel's only parameter: the segment starts with it)
 #endif
-    MM_TIMELINE_BEGIN();
     __shared__ WaveStage s_stage[kBlock ? 4 : 1];
-    MM_PP_BEGIN();
     const int wv = kBlock ? threadIdx.x >> 6 : 0;               // (MM_WAVE_UNIFORM here and on the order entry: 83 instead of 96 VGPRs, but 1-3 % SLOWER at every size)
     int limit = 4 * a.blocks_per_image, rank = -1;               // rank: this workgroup's index among its image's walking workgroups (-1: from blockIdx)
     if (a.order) {
@@ -78,20 +73,16 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
     const TileCtx t = make_tile<kBlock>(a, wv, rank, valid, coop, limit);    // coop is workgroup-uniform; !valid only in the last workgroup of the non-empty tiles
     unsigned long long key;
     SoftState ss;
-    MM_PP_MARK(0);
     if (kBlock && coop) {
-        tile_walk_coop(a, t, s_stage, wv, key, ss MM_PP_PASS);
+        tile_walk_coop(a, t, s_stage, wv, key, ss);
         if (wv != 0) return;                                     // the tile's pixels are shaded once
     } else {
         if (!valid) return;
-        if (kQueue) tile_walk(a, t, &s_stage[wv], key, ss MM_PP_PASS);
-        else tile_walk_batch(a, t, &s_stage[wv], key, ss MM_PP_PASS);
+        if (kQueue) tile_walk(a, t, &s_stage[wv], key, ss);
+        else tile_walk_batch(a, t, &s_stage[wv], key, ss);
     }
     shade_store<kNoMask, kContour>(a, t, key, ss);
     flush_taken_last(a, t, &s_stage[(kBlock && coop) ? 0 : wv]);
-    MM_PP_MARK(5);
-    MM_PP_FLUSH(raster_fwd, (long long)blockIdx.x * (kBlock ? 4 : 1) + wv);
-    MM_TIMELINE_END(raster_fwd);
 }
 
 // Candidates per screen bin for big screens / meshes (the order kernel below counts the mask bits itself where a tile's mask row is a few
@@ -207,10 +198,9 @@ int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s) 
     const bool block = walk_block_mode(a);
     const dim3 grid(walk_grid(a, block));
     ProfScope ps(d->prof_events, MM_PROF_RASTER_FWD, s);
-    // 8-pixel bins: the bin is the tile, nothing to compact -> the per-batch walk, no face flags (every face gets its sweep items;
-    // -DMM_BATCH_FLAGS=1: the r06 A/B in which this walk sets them too)
+    // 8-pixel bins: the bin is the tile, nothing to compact -> the per-batch walk, no face flags (every face gets its sweep items)
     const bool queue = walk_queue_mode(a);
-    if (!queue && !MM_BATCH_FLAGS) a.fflag = nullptr;
+    if (!queue) a.fflag = nullptr;
 #define MM_LAUNCH_RASTER2(NM, BL, QU, CO) hipLaunchKernelGGL((raster_fwd_kernel<NM, BL, QU, CO>), grid, dim3(BL ? 256 : 64), 0, s, a)
 #define MM_LAUNCH_RASTER(NM, BL, QU) do { if (a.contour > 0.f) MM_LAUNCH_RASTER2(NM, BL, QU, true); else MM_LAUNCH_RASTER2(NM, BL, QU, false); } while (0)
     if (block) {

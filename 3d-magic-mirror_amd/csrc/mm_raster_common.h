@@ -44,12 +44,6 @@ struct RasterArgs {
 #ifndef MM_PAIR_ROUND
 #define MM_PAIR_ROUND 512
 #endif
-#ifndef MM_HEAVY_CAND
-#define MM_HEAVY_CAND 192     // a tile with at least this many candidates (three batches) is walked by four waves together ...
-#endif
-#ifndef MM_HEAVY_MAX
-#define MM_HEAVY_MAX 32       // ... if it is among the image's MM_HEAVY_MAX heaviest
-#endif
 
 struct TileCtx {
     int b, blk, px, py, tx0, ty0, lane, wave;   // wave = quadrant of the 16x16 block `blk`
@@ -215,9 +209,6 @@ __device__ inline void hard_pair(const RasterArgs& a, const TileCtx& t, Stage* s
 #ifndef MM_HARD_DIRECT
 #define MM_HARD_DIRECT 192
 #endif
-#ifndef MM_PAIR_Z
-#define MM_PAIR_Z 0            // 1: early-z per PAIR (interpolated depth with a hardware reciprocal) instead of per face (its largest corner depth): fewer
-#endif                         // survivors, six more registers -- and this kernel lives on its occupancy
 typedef float mm_f2 __attribute__((ext_vector_type(2)));
 template <class Stage>
 __device__ inline void hard_pairs(const RasterArgs& a, const TileCtx& t, Stage* st, uint64_t m, bool by_cand) {
@@ -242,13 +233,9 @@ __device__ inline void hard_pairs(const RasterArgs& a, const TileCtx& t, Stage* 
             const unsigned e0 = st->pairs[v0 ? q0 + t.lane : 0], e1 = st->pairs[v1 ? q0 + 64 + t.lane : 0];
             const int j0 = (int)(e0 >> 8), j1 = (int)(e1 >> 8), l0 = (int)(e0 & 63u), l1 = (int)(e1 & 63u);
             const float4 A0 = st->p0[j0], B0 = st->p1[j0], A1 = st->p0[j1], B1 = st->p1[j1];
-            // early-z: what the pixel holds by now (the high word of its key; 0 = nothing yet) against an upper bound of the depth this pair
-            // would give it -- the interpolation with a hardware reciprocal (1 ulp) plus 2e-5 of the corner depths' magnitudes
-#if MM_PAIR_Z
-            const float cz0 = st->p2[j0].x, cz1 = st->p2[j1].x;
-#else
-            const unsigned zb0 = __float_as_uint(st->p2[j0].w), zb1 = __float_as_uint(st->p2[j1].w);   // the face's depth bound
-#endif
+            // early-z: what the pixel holds by now (the high word of its key; 0 = nothing yet) against the face's depth bound (its largest corner
+            // depth).  A bound per PAIR (the interpolated depth) leaves fewer survivors but costs six more registers, and this kernel lives on its occupancy
+            const unsigned zb0 = __float_as_uint(st->p2[j0].w), zb1 = __float_as_uint(st->p2[j1].w);
             const unsigned kh0 = (unsigned)(st->key[l0] >> 32), kh1 = (unsigned)(st->key[l1] >> 32);
             bool pass0, pass1;
             {
@@ -265,15 +252,7 @@ MM_FP_EXACT
                 const bool sane0 = fabsf(nrm.x) <= 1e12f, sane1 = fabsf(nrm.y) <= 1e12f;
                 const bool rej0 = sane0 && ((!one_minus && neg(k0.x, nrm.x)) || neg(k1.x, nrm.x) || neg(k2.x, nrm.x));
                 const bool rej1 = sane1 && ((!one_minus && neg(k0.y, nrm.y)) || neg(k1.y, nrm.y) || neg(k2.y, nrm.y));
-#if MM_PAIR_Z
-                const mm_f2 az = {B0.z, B1.z}, bz = {B0.w, B1.w}, cz = {cz0, cz1};
-                const mm_f2 zn = (k0 * az + k1 * bz) + k2 * cz;
-                const float zu0 = zn.x * __builtin_amdgcn_rcpf(nrm.x) + 2e-5f * ((fabsf(az.x) + fabsf(bz.x)) + fabsf(cz.x));
-                const float zu1 = zn.y * __builtin_amdgcn_rcpf(nrm.y) + 2e-5f * ((fabsf(az.y) + fabsf(bz.y)) + fabsf(cz.y));
-                const bool near0 = !(zu0 == zu0) || depth_ord(zu0) >= kh0, near1 = !(zu1 == zu1) || depth_ord(zu1) >= kh1;   // (NaN: stays in)
-#else
                 const bool near0 = zb0 >= kh0, near1 = zb1 >= kh1;
-#endif
                 pass0 = v0 && !rej0 && near0; pass1 = v1 && !rej1 && near1;
             }
             const uint64_t b0 = __ballot(pass0), b1 = __ballot(pass1);
@@ -295,9 +274,6 @@ MM_FP_EXACT
 // sig2 = sigmainv / multiplier^2 (d is in multiplier units).
 template <class Stage>
 __device__ inline void soft_pair(const RasterArgs& a, const TileCtx& t, Stage* st, Stage* acc, float sig2, int l, int j, bool live) {
-#ifdef MM_BOUND_NOSOFT                                          // (bound experiment, WRONG results: the silhouette pairs cost nothing)
-    return;
-#endif
     const float x0 = pixel_x_k(t.tx0 + (l & 7), a.W, a.kx), y0 = pixel_y_k(t.ty0 + (l >> 3), a.H, a.ky);
     const float4 p0 = st->p0[j], p1 = st->p1[j];
     const float q = soft_factor(x0, y0, p0, p1, sig2);
@@ -330,9 +306,6 @@ MM_FP_EXACT
 }
 template <class Stage>
 __device__ inline void soft_pairs(const RasterArgs& a, const TileCtx& t, Stage* st, uint64_t sm, float sig2) {
-#ifdef MM_BOUND_NOSOFT
-    return;
-#endif
     int total;
     int k = wave_prefix_excl(__popcll(sm), t.lane, total);      // index of this lane's next unwritten pair
     uint64_t rem = sm;
@@ -357,11 +330,7 @@ MM_FP_EXACT
                 const mm_f2 y0 = {a.ky * (t.yf0 - (float)(2 * (l0 >> 3))), a.ky * (t.yf0 - (float)(2 * (l1 >> 3)))};
                 const mm_f2 ax = {A0.x, A1.x}, ay = {A0.y, A1.y}, bx = {A0.z, A1.z}, by = {A0.w, A1.w}, cx = {B0.x, B1.x}, cy = {B0.y, B1.y};
                 const mm_f2 d0 = seg_dist2_pk(x0, y0, ax, ay, bx, by), d1 = seg_dist2_pk(x0, y0, bx, by, cx, cy), d2 = seg_dist2_pk(x0, y0, cx, cy, ax, ay);
-#ifdef MM_BOUND_SOFT1                                           // (bound experiment, WRONG results: one edge instead of three)
-                const float dx = d0.x, dy = d0.y;
-#else
                 const float dx = fminf(fminf(d0.x, d1.x), d2.x), dy = fminf(fminf(d0.y, d1.y), d2.y);
-#endif
                 q[0] = 1.f - __builtin_amdgcn_exp2f(-(dx * sig2) * 1.4426950408889634f);
                 q[1] = 1.f - __builtin_amdgcn_exp2f(-(dy * sig2) * 1.4426950408889634f);
             }
@@ -532,9 +501,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     if (t.in_img) {
         *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], out[3]);
         a.face_idx[pix] = h.f;
-#ifndef MM_NO_OWN_FLAG
         if (h.f >= 0 && a.fflag) a.fflag[((size_t)t.b * a.F + h.f) * 2] = 1;     // "owns a pixel" (idempotent plain store: the backward sweeps this face)
-#endif
         a.soft[pix] = make_float2((h.f >= 0 || ss.zeros >= 2) ? 0.f : (ss.zeros == 1 ? -ss.qnz : ss.qnz), __int_as_float(ss.lastf));
         if (a.imnormal) { a.imnormal[pix * 3] = nx; a.imnormal[pix * 3 + 1] = ny; a.imnormal[pix * 3 + 2] = nz; }
     }
@@ -596,19 +563,6 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
     unsigned sl[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) sl[q] = a.order[(size_t)b * nslot + min(e0 + q, nslot - 1)] & 0x7FFFu;
-#ifdef MM_BOUND_NO_EMPTY                                        // BOUND EXPERIMENT (WRONG results, never in the product; profiles/r06_empty_shading_bound.md): of an empty tile's
-    for (int q = 0; q < 4; ++q) {                                // 60 bytes per pixel only the 12 the backward cannot do without (face_idx = -1, soft-mask state) are written
-        const int blk = (int)sl[q] >> 2, quad = (int)sl[q] & 3;
-        const int px = (blk % a.blocks_x) * MM_BLOCK_PX + (quad & 1) * MM_TILE + (lane & 7);
-        const int py = (blk / a.blocks_x) * MM_BLOCK_PX + (quad >> 1) * MM_TILE + (lane >> 3);
-        if (q < ne && px < a.W && py < a.H) {
-            const size_t pix = (size_t)b * hw + (size_t)py * a.W + px;
-            a.face_idx[pix] = -1;
-            a.soft[pix] = make_float2(1.f, __int_as_float(0x7FFFFFFF));
-        }
-    }
-    return;
-#endif
     const float coef = MM_SH_C0 * a.lights[b * 9] + (0.f - MM_SH_C6B) * a.lights[b * 9 + 6];   // (bands 0 and 6: the same lights whatever the band order)
     bool in[4];
     size_t pin[4];
@@ -707,17 +661,7 @@ __device__ inline void walk_image_rank(int i, int B, int spread, int& b, int& j)
 }
 inline bool walk_queue_mode(const RasterArgs& a) { return walk_queue_mode(a.options, a.bin_shift); }
 // blocks instead of tiles are sorted where a block's four tiles share a bin (bins of 16 pixels or more) and tiles are walked one per workgroup
-inline bool walk_block_sort(const RasterArgs& a) {
-#ifdef MM_NO_BLOCK_SORT
-    return false;
-#else
-#ifdef MM_BLOCK_SORT_IN_BLOCK_SHAPE                             // (A/B: the bin's four tiles as the four waves of ONE workgroup -- one CU, one L1)
-    return a.bin_shift >= 4;
-#else
-    return a.bin_shift >= 4 && !(a.options & MM_OPT_WALK_BLOCK);
-#endif
-#endif
-}
+inline bool walk_block_sort(const RasterArgs& a) { return a.bin_shift >= 4 && !(a.options & MM_OPT_WALK_BLOCK); }
 inline int walk_spread(const RasterArgs& a) {
     if (a.order == nullptr || 4 * a.blocks_per_image < 1024) return 0;
     return a.block_sort && !walk_block_mode(a) ? 2 : 1;

@@ -21,18 +21,12 @@ struct __attribute__((aligned(16))) WaveStage {
     unsigned short pairs[MM_PAIR_ROUND];    // (row << 8) | column of the bit matrix being evaluated (candidate, pixel) or (pixel, candidate)
     unsigned long long key[64];             // per pixel: best (orderable z << 32 | ~face) so far; 0 = none
     long long logsum[64];                   // per pixel: sum of log2(1-p) in 2^-32 fixed point (integer adds commute)
-#ifdef MM_LDS_DIET
-    int zeros[16];
-#else
     int zeros[64];                          // per pixel: number of factors (1-p) that are exactly 0
-#endif
     unsigned long long takenw[64];          // faces of the current chunk of 4096 that some pixel took into its silhouette product: bit b of word w = face
                                             // chunk * 4096 + w * 64 + b (LDS ors; written to RasterArgs::fflag when the chunk has been walked)
     int npair[4];                           // cooperative walk: this wave's colour / silhouette pair counts of the round
 };
-#ifndef MM_NO_STAGE_ASSERT
 static_assert(sizeof(WaveStage) <= 8192, "four of them must fit 32 KiB: five workgroups per CU");
-#endif
 // cooperative walk: per pixel, inflated-box hits of this wave's batch of the current round / id of the knum-th silhouette face taken
 __device__ inline int* coop_cnt(WaveStage* st) { return reinterpret_cast<int*>(&st->qm[0][0]); }
 __device__ inline int* coop_lastf(WaveStage* st) { return reinterpret_cast<int*>(&st->qm[1][0]); }
@@ -71,12 +65,6 @@ __device__ inline void flush_taken_last(const RasterArgs& a, const TileCtx& t, W
     flush_taken(a, t, acc, ((a.words - 1) / 64) * 64);
 }
 
-#ifndef MM_TAKEN_EXACT
-#define MM_TAKEN_EXACT 1
-#endif
-#ifndef MM_WALK_TWICE
-#define MM_WALK_TWICE 0
-#endif
 // Work of a 256-thread workgroup: FOUR tiles, one per wave (nothing shared), or ONE heavy tile walked by its four waves together
 // (tile_walk_coop).  With the plan kernel's order (tiles of an image by decreasing candidate count, the first nheavy of them heavy):
 // workgroup j of image b takes heavy tile j, or -- behind the heavy ones -- the four tiles nheavy + 4 (j - nheavy) + wave.  Launch
@@ -162,9 +150,7 @@ __device__ inline int idw_next(IdWindows& iw, const TileCtx& t, WaveStage* st) {
 #ifndef MM_HARD_ROW_MAX
 #define MM_HARD_ROW_MAX 6
 #endif
-#ifndef MM_NEAR_PASSES
-#define MM_NEAR_PASSES 2          // depth bands a flush's colour candidates are evaluated in, nearest first (1: one pass in index order)
-#endif
+#define MM_NEAR_PASSES 2          // depth bands a flush's colour candidates are evaluated in, nearest first
 #ifndef MM_NEAR_MIN_PAIRS
 #define MM_NEAR_MIN_PAIRS 256     // ... if the flush has more (pixel, candidate) box pairs than this
 #endif
@@ -196,12 +182,11 @@ __device__ inline void stage_slot(WaveStage* st, int slot, int f, const float4& 
 // hits per batch) costs a tenth of what it did when every batch was staged, transposed and paired.
 //   want_soft(): wave-uniform, asked once per raw batch: can any pixel still take a silhouette face?  (Monotone: once false, always false.)
 template <class WantSoft, class Flush>
-__device__ inline void scan_candidates(const RasterArgs& a, const TileCtx& t, WaveStage* st, const unsigned& zfloor, int& cur_cbase, WantSoft&& want_soft, Flush&& flush MM_PP_ARG) {
+__device__ inline void scan_candidates(const RasterArgs& a, const TileCtx& t, WaveStage* st, const unsigned& zfloor, int& cur_cbase, WantSoft&& want_soft, Flush&& flush) {
     const float4* geo = a.geo + (size_t)t.b * a.F * 3;
     const int bmode = box_mode(a.options);
     int qn = 0;                                                  // candidates waiting in the queue (wave-uniform)
     uint64_t next_word = idw_load(a, t, 0);
-    MM_PP_MARK(8);                                               // (phase build: the first mask load's latency alone)
     for (int cbase = 0; cbase < a.words; cbase += 64) {
       IdWindows iw;
       cur_cbase = cbase;
@@ -217,8 +202,6 @@ __device__ inline void scan_candidates(const RasterArgs& a, const TileCtx& t, Wa
         if (total == 0 && !final) break;
         const int wbase = cbase;
         wave_lds_sync();
-        MM_PP_MARK(1);
-        MM_PP_COUNT(total, 0);
         // the face records of batch k+1 are requested before batch k is tested (a tile with hundreds of candidates would otherwise pay a
         // dependent trip to memory per batch)
         float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, n2 = n0;
@@ -228,7 +211,6 @@ __device__ inline void scan_candidates(const RasterArgs& a, const TileCtx& t, Wa
             n0 = geo[(size_t)nf * 3 + 0]; n1 = geo[(size_t)nf * 3 + 1]; n2 = geo[(size_t)nf * 3 + 2];
         };
         if (total) fetch(0);
-        MM_PP_MARK(9);                                           // (phase build: a window's first record fetch, its latency alone)
         const int nbatch = (total + 63) / 64 + (final ? 1 : 0);
         for (int i = 0; i < nbatch; ++i) {
             const int k0 = i * 64, n = max(0, min(64, total - k0));
@@ -250,7 +232,6 @@ __device__ inline void scan_candidates(const RasterArgs& a, const TileCtx& t, Wa
                 const uint64_t surv = __ballot(keep);
                 ns = __popcll(surv);
                 slot = ballot_rank(surv);
-                MM_PP_MARK(2);
                 if (!(n == 0 ? qn > 0 : qn + ns > 64)) break;    // (wave-uniform) not the end of the walk, and the survivors fit
                 flush(qn); qn = 0;
                 if (n == 0) break;
@@ -290,42 +271,19 @@ __device__ inline void winner(const RasterArgs& a, const TileCtx& t, unsigned lo
 // some pixel can still take a face.  A pixel takes silhouette faces while no face flushed SO FAR covers it: for a pixel
 // that stays uncovered that is every candidate, in order -- exactly the two-pass result; whatever a pixel gathered
 // before a later flush covered it is never looked at.
-__device__ inline void tile_walk(const RasterArgs& a, const TileCtx& t, WaveStage* st, unsigned long long& key, SoftState& ss MM_PP_ARG) {
+__device__ inline void tile_walk(const RasterArgs& a, const TileCtx& t, WaveStage* st, unsigned long long& key, SoftState& ss) {
     key = 0ull;
     ss.qnz = 1.f; ss.zeros = 0; ss.lastf = 0x7FFFFFFF;
     if (t.empty) return;                                         // wave-uniform: more than half of all tiles are empty
     const float s2 = a.sigmainv / (a.mult * a.mult);
-#if MM_WALK_TWICE
-    // BOUND EXPERIMENT (profiles/r05_depth_order_bound.md; never in the product): the tile is walked twice by the same code (a loop, not a second
-    // call site).  1: the second walk starts from the FIRST walk's winners -- every pixel already holds its final depth, the tile's depth floor is
-    // final, only truly uncovered pixels take silhouette faces: what a perfect nearest-first order of the candidates could at best leave of the
-    // colour pairs.  2: the second walk starts from nothing (calibration: the cost of one whole walk).  Results are those of the second walk,
-    // which are the first's (the winner is an idempotent maximum; the silhouette state is reset).
-    unsigned long long seed = 0ull;
-    int lastf = 0x7FFFFFFF;
-    for (int rep = 0; rep < 2; ++rep) {
-    st->key[t.lane] = MM_WALK_TWICE == 1 ? seed : 0ull; st->logsum[t.lane] = 0ll; st->zeros[t.lane] = 0; st->takenw[t.lane] = 0ull;
-    wave_lds_sync();
-    int cnt = 0, cbase = 0;
-    lastf = 0x7FFFFFFF;
-    bool open = t.in_img && (MM_WALK_TWICE == 1 ? seed == 0ull : true);
-    unsigned zfloor = MM_WALK_TWICE == 1 ? wave_min_u32(t.in_img ? (unsigned)(seed >> 32) : 0xFFFFFFFFu) : 0u;
-#ifdef MM_PHASE_PROF
-    if (rep == 1) { pp_.c0 = 0; pp_.c1 = 0; for (int i = 1; i <= 4; ++i) pp_.acc[i] = 0; }   // the counters and walk phases of the second walk alone
-#endif
-#else
     st->key[t.lane] = 0ull; st->logsum[t.lane] = 0ll; st->zeros[t.lane] = 0; st->takenw[t.lane] = 0ull;
     wave_lds_sync();
     int cnt = 0, lastf = 0x7FFFFFFF, cbase = 0;
     bool open = t.in_img;
     unsigned zfloor = 0;                                         // smallest depth_ord held by an in-image pixel of the tile (wave-uniform; 0: some pixel holds nothing)
-#endif
     scan_candidates(a, t, st, zfloor, cbase, [&]() { return __ballot(open && cnt < a.knum) != 0; }, [&](int n) {
         wave_lds_sync();                                         // the queue's stores
         const uint64_t mh = t.lane < n ? st->qm[0][t.lane] : 0ull, ms = t.lane < n ? st->qm[1][t.lane] : 0ull;
-#ifdef MM_PHASE_PROF
-        { int th; (void)wave_prefix_excl(__popcll(mh), t.lane, th); MM_PP_COUNT(1ull << 32, (unsigned long long)th); }   // flushes | colour pairs
-#endif
         if (__ballot(mh != 0)) {
             // NEAREST FIRST.  The winner is an order-free maximum, so the flush's candidates may be evaluated in any order -- and the order decides
             // how much early-z saves: in index order a pixel under forty overlapping boxes meets its nearest face at a random place of the list.
@@ -337,17 +295,13 @@ __device__ inline void tile_walk(const RasterArgs& a, const TileCtx& t, WaveStag
             const unsigned zbd = t.lane < n ? __float_as_uint(st->p2[t.lane].w) : 0u;
             int npass = 1;
             unsigned zlo = 0u, zhi = 0u;
-#if MM_NEAR_PASSES > 1
-            {
-                int pairs_total;
-                (void)wave_prefix_excl(__popcll(mh), t.lane, pairs_total);
-                if (pairs_total > MM_NEAR_MIN_PAIRS) {            // (wave-uniform) a short list: one pass, as before
-                    zhi = (unsigned)wave_max_i32((int)(zbd >> 1)) << 1;                         // (31-bit reductions: the bands need no last bit)
-                    zlo = wave_min_u32(mh != 0 ? zbd : 0xFFFFFFFFu);
-                    npass = zhi > zlo ? MM_NEAR_PASSES : 1;
-                }
+            int pairs_total;
+            (void)wave_prefix_excl(__popcll(mh), t.lane, pairs_total);
+            if (pairs_total > MM_NEAR_MIN_PAIRS) {                // (wave-uniform) a short list: one pass, as before
+                zhi = (unsigned)wave_max_i32((int)(zbd >> 1)) << 1;                             // (31-bit reductions: the bands need no last bit)
+                zlo = wave_min_u32(mh != 0 ? zbd : 0xFFFFFFFFu);
+                npass = zhi > zlo ? MM_NEAR_PASSES : 1;
             }
-#endif
             uint64_t left = mh;
             for (int pass = 0; pass < npass; ++pass) {
                 // band `pass` holds the bounds in (edge[pass + 1], edge[pass]]: edge[0] = +inf, edge[npass] = -inf
@@ -366,33 +320,19 @@ __device__ inline void tile_walk(const RasterArgs& a, const TileCtx& t, WaveStag
                     zfloor = wave_min_u32(t.in_img ? (unsigned)(kk >> 32) : 0xFFFFFFFFu);
                 }
             }
-            MM_PP_MARK(3);
         }
         const uint64_t openm = __ballot(open && cnt < a.knum);
         if (__ballot(ms != 0) && openm) {
             const uint64_t ps = wave_transpose64(ms, t.lane);    // pixel-major: this lane's pixel, bit j = queued candidate j
             const uint64_t sm = soft_take(ps, open, a.knum - cnt);   // the first knum hits of this pixel, in order
-#if MM_TAKEN_EXACT
             mark_taken(a, t, st, st, (wave_or_u64(sm) >> t.lane) & 1ull, 1ull, cbase);   // exactly the candidates some pixel took (bit 0 = this lane's)
-#else
-            mark_taken(a, t, st, st, ms, openm, cbase);          // a superset: every candidate whose inflated box holds a pixel that is still taking
-#endif
             cnt += __popcll(sm);
             if (sm != 0 && cnt >= a.knum) lastf = __float_as_int(st->p2[63 - __clzll((unsigned long long)sm)].z);   // knum-th face taken
             if (__ballot(sm != 0)) soft_pairs(a, t, st, sm, s2);
-#ifdef MM_PHASE_PROF
-            { int ts; (void)wave_prefix_excl(__popcll(sm), t.lane, ts); MM_PP_COUNT(0, (unsigned long long)ts << 32); }   // silhouette pairs
-#endif
-            MM_PP_MARK(4);
         }
         wave_lds_sync();                                         // the queue is free again
-    } MM_PP_PASS);
+    });
     wave_lds_sync();
-#if MM_WALK_TWICE
-    seed = st->key[t.lane];
-    wave_lds_sync();
-    }
-#endif
     key = st->key[t.lane];
     ss.zeros = st->zeros[t.lane];
     ss.qnz = exp2f((float)((double)st->logsum[t.lane] * (1.0 / 4294967296.0)));
@@ -403,7 +343,7 @@ __device__ inline void tile_walk(const RasterArgs& a, const TileCtx& t, WaveStag
 // to compact, and with a few dozen candidates per tile the launch lasts as long as one tile's chain of dependent steps -- the queue, the
 // filter pass and the face flags of tile_walk only lengthen it: 128x128 with 1 280 faces, raster_fwd 32.5 us against 40).  Every batch of 64
 // candidates is staged, box-tested, transposed to the per-pixel view and its pairs evaluated at once; same results bit for bit.
-__device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, WaveStage* st, unsigned long long& key, SoftState& ss MM_PP_ARG) {
+__device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, WaveStage* st, unsigned long long& key, SoftState& ss) {
     key = 0ull;
     ss.qnz = 1.f; ss.zeros = 0; ss.lastf = 0x7FFFFFFF;
     if (t.empty) return;                                         // wave-uniform: more than half of all tiles are empty
@@ -416,7 +356,6 @@ __device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, Wa
     bool open = t.in_img;
     unsigned zfloor = 0;
     uint64_t next_word = idw_load(a, t, 0);
-    MM_PP_MARK(8);
     for (int cbase = 0; cbase < a.words; cbase += 64) {
       IdWindows iw;
       idw_begin(iw, a, t, next_word);
@@ -424,8 +363,6 @@ __device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, Wa
       for (int total = idw_next(iw, t, st); total != 0; total = idw_next(iw, t, st)) {
         const int wbase = cbase;
         wave_lds_sync();
-        MM_PP_MARK(1);
-        MM_PP_COUNT(total, 0);
         // the face records of batch k+1 are requested before batch k is evaluated
         float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, n2 = n0;
         int nf = 0;
@@ -436,11 +373,7 @@ __device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, Wa
             }
         };
         fetch(0);
-        MM_PP_MARK(9);
         for (int k0 = 0; k0 < total; k0 += 64) {
-#ifdef MM_BOUND_CAP                                             // BOUND EXPERIMENT (WRONG results, never in the product; profiles/r06_semi_heavy_bound.md): a single-wave tile stops after
-            if (k0 >= MM_BOUND_CAP) break;                       // this many candidates -- what the launch would last if no single-wave tile were heavier than that
-#endif
             const int n = min(64, total - k0);
             const float4 g0 = n0, g1 = n1, g2 = n2;
             const int f = nf;
@@ -455,38 +388,19 @@ __device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, Wa
             const uint64_t ph = __ballot(mh != 0) ? wave_transpose64(mh, t.lane) : 0ull;
             const uint64_t ps = __ballot(ms != 0) ? wave_transpose64(ms, t.lane) : 0ull;
             wave_lds_sync();
-            MM_PP_MARK(2);
             if (__ballot(ph != 0)) {
-#ifdef MM_BATCH_FILTER                                          // (A/B, profiles/r05_batch_walk_ab.md: the compacting walk's two-phase pair evaluation -- packed sign filter +
-                hard_pairs(a, t, st, ph, false);                 //  early-z, then the divisions for the survivors -- in the per-batch walk; lists of <= MM_HARD_DIRECT pairs go direct)
-#else
                 pair_parallel(t, st, ph, [&](int l, int j, bool live) { hard_pair(a, t, st, st, j, l, live); });   // pixel l, candidate j
-#endif
                 const unsigned long long kk = st->key[t.lane];
                 open = t.in_img && kk == 0ull;
                 zfloor = wave_min_u32(t.in_img ? (unsigned)(kk >> 32) : 0xFFFFFFFFu);
-                MM_PP_MARK(3);
             }
             const uint64_t sm = soft_take(ps, open, a.knum - cnt);   // the first knum hits of this pixel, in order
             cnt += __popcll(sm);
             if (sm != 0 && cnt >= a.knum) lastf = __float_as_int(st->p2[63 - __clzll((unsigned long long)sm)].z);   // knum-th face taken
-            // r06 A/B (-DMM_BATCH_FLAGS=1; a.fflag is null otherwise): the face flags for the backward here too, as the compacting walk sets them.
-            // Costs this kernel more than it saves the gather at 128x128 (profiles/r06_batch_walk_flags_ab.md): off by default.
-#if MM_BATCH_FLAGS
-            if (a.fflag && __ballot(sm != 0)) mark_taken(a, t, st, st, (wave_or_u64(sm) >> t.lane) & 1ull, 1ull, cbase);
-#endif
-#ifdef MM_BATCH_SOFT_PACKED                                             // (two pairs per lane in packed fp32, as the compacting walk does: measured SLOWER
-            if (__ballot(sm != 0)) soft_pairs(a, t, st, sm, s2);         //  here, raster_fwd 34.4 / 92.8 / 191.7 us against 33.8 / 88.4 / 184.7 at 128x128 / 256x256 / B=384)
-#else
             if (__ballot(sm != 0)) pair_parallel(t, st, sm, [&](int l, int j, bool live) { soft_pair(a, t, st, st, s2, l, j, live); });
-#endif
-            MM_PP_MARK(4);
             wave_lds_sync();
         }
       }
-#if MM_BATCH_FLAGS
-      if (cbase + 64 < a.words) { wave_lds_sync(); flush_taken(a, t, st, cbase); }   // (meshes beyond 4096 faces; the LAST chunk's faces: flush_taken_last)
-#endif
     }
     wave_lds_sync();
     key = st->key[t.lane];
@@ -505,7 +419,7 @@ __device__ inline void tile_walk_batch(const RasterArgs& a, const TileCtx& t, Wa
 // hit counts, and a batch takes what is left of knum after the batches before it -- for a pixel that stays uncovered that is the
 // sequential result bit for bit (what a pixel gathered before it was covered is never read, as in tile_walk).
 #define MM_COOP_WINDOW (4 * MM_PAIR_ROUND)    // pairs dealt per pass: the four stages' pair buffers side by side
-__device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, WaveStage* stage, int wv, unsigned long long& key, SoftState& ss MM_PP_ARG) {
+__device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, WaveStage* stage, int wv, unsigned long long& key, SoftState& ss) {
     WaveStage* st = &stage[wv];
     WaveStage* acc = &stage[0];
     key = 0ull;
@@ -523,8 +437,6 @@ __device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, Wav
       for (int total = idw_next(iw, t, st); total != 0; total = idw_next(iw, t, st)) {   // (the same in the four waves)
         const int wbase = cbase;
         wave_lds_sync();
-        MM_PP_MARK(1);
-        MM_PP_COUNT(total, 0);
         for (int r0 = 0; r0 < total; r0 += 4 * 64) {
             const int k0 = r0 + wv * 64;
             const int n = max(0, min(64, total - k0));
@@ -541,7 +453,6 @@ __device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, Wav
             const uint64_t ps = __ballot(ms != 0) ? wave_transpose64(ms, t.lane) : 0ull;
             mark_taken(a, t, st, acc, ms, __ballot(open && base_cnt < a.knum), cbase);
             coop_cnt(st)[t.lane] = __popcll(ps);
-            MM_PP_MARK(2);
             __syncthreads();
             int before = base_cnt, round_total = 0;              // hits of the batches before this wave's, in index order
 #pragma unroll
@@ -564,8 +475,6 @@ __device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, Wav
             }
             ks += TH;                                            // silhouette pairs behind all colour pairs
             const int T = TH + TS;
-            MM_PP_MARK(6);
-            MM_PP_COUNT(0, T);
             uint64_t remh = ph, rems = sm;
             for (int base = 0; base < T; base += MM_COOP_WINDOW) {
                 const int lim = min(MM_COOP_WINDOW, T - base);
@@ -584,7 +493,6 @@ __device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, Wav
                     ++ks;
                 }
                 __syncthreads();
-                MM_PP_MARK(3);
                 for (int q = threadIdx.x; q < lim; q += 256) {
                     const unsigned pr = stage[q / MM_PAIR_ROUND].pairs[q % MM_PAIR_ROUND];
                     WaveStage* src = &stage[(pr >> 12) & 3];
@@ -592,9 +500,7 @@ __device__ inline void tile_walk_coop(const RasterArgs& a, const TileCtx& t, Wav
                     if (pr & 0x4000u) soft_pair(a, t, src, acc, s2, l, j, true);
                     else hard_pair(a, t, src, acc, j, l, true);
                 }
-                MM_PP_MARK(4);
                 __syncthreads();
-                MM_PP_MARK(7);
             }
             open = t.in_img && acc->key[t.lane] == 0ull;
         }

@@ -9,9 +9,6 @@
 //   gradients are gathered in a fixed order (no atomics), reduces dT in LDS and finishes with the camera chain.
 #include "mm_device.h"
 
-MM_PP_STORAGE(vertex_fwd)       // 0 counters cleared, 1 camera (fp64 trig + look-at), 2 face records, 3 binning
-MM_PP_STORAGE(vertex_bwd)       // 0 loads of T + vertex, 1 corner gather, 2 group / wave reductions + partial store, 3 ticket, 4 last workgroup: lights, 5 camera chain
-
 namespace mm {
 
 struct VertexFwdArgs {
@@ -38,11 +35,7 @@ __device__ inline void block_camera(const float* azim, const float* elev, const 
     if (tid < 4) {
         const float ang = MM_DEG2RAD * (tid < 2 ? elev[b] : azim[b]);
         // fp64 sin/cos rounded to fp32: the oracle does the same, so both sides see correctly rounded values
-#ifdef MM_BOUND_FAST_TRIG                                       // BOUND EXPERIMENT (wrong last bits, never in the product): what the fp64 library trig costs the forward's head
-        s_trig[tid] = (tid & 1) ? __sinf(ang) : __cosf(ang);
-#else
         s_trig[tid] = (tid & 1) ? (float)sin((double)ang) : (float)cos((double)ang);
-#endif
     }
     __syncthreads();
     if (tid == 0) camera_build(dist[b], s_trig[0], s_trig[1], s_trig[2], s_trig[3], bias[2 * b], bias[2 * b + 1], *s_cam);
@@ -84,10 +77,8 @@ __global__ __launch_bounds__(256) void vertex_fwd_kernel(VertexFwdArgs a) {
     __shared__ float s_trig[4];
     __shared__ Camera s_cam;
     const int b = blockIdx.y, tid = threadIdx.x;
-    MM_PP_BEGIN();
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < a.ntcnt; i += gridDim.x * gridDim.y * 256) a.tcnt[i] = 0;
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < a.nltot; i += gridDim.x * gridDim.y * 256) a.ltot[i] = 0;
-    MM_PP_MARK(0);
     // this lane's face: its corner ids and their raw positions depend on nothing the camera produces -- both trips to memory are in
     // flight while four lanes do the fp64 trigonometry and one builds the look-at
     const int f = blockIdx.x * 256 + tid;
@@ -99,7 +90,6 @@ __global__ __launch_bounds__(256) void vertex_fwd_kernel(VertexFwdArgs a) {
         for (int j = 0; j < 3; ++j) { pa[j] = vb[(size_t)i0 * 3 + j]; pb[j] = vb[(size_t)i1 * 3 + j]; pc[j] = vb[(size_t)i2 * 3 + j]; }
     }
     block_camera(a.azim, a.elev, a.dist, a.bias, b, s_trig, &s_cam);
-    MM_PP_MARK(1);
     if (blockIdx.x == 0 && tid < 12) a.T[b * 12 + tid] = s_cam.T[tid];
     if (blockIdx.x == 0 && tid == 12) a.ticket[b] = 0u;
     if (blockIdx.x == 0 && tid >= 64 && tid < 100) a.cam[b * 48 + tid - 64] = reinterpret_cast<const float*>(&s_cam)[tid - 64];
@@ -111,11 +101,8 @@ __global__ __launch_bounds__(256) void vertex_fwd_kernel(VertexFwdArgs a) {
     if (f < a.F) face_record(a, b, f, pa, pb, pc, T, bx0, by0, bw, bh);
 
     // ---- screen binning: this wave's 64 faces are exactly mask word c (bin_wave_faces, mm_device.h) ---------------------------
-    MM_PP_MARK(2);
     const int c = blockIdx.x * 4 + (tid >> 6);
     if (a.mask != nullptr && c < a.words) bin_wave_faces(a.mask, b, a.nbx, a.nby, a.words, a.bin_shift, c, tid & 63, bx0, by0, bw, bh);
-    MM_PP_MARK(3);
-    MM_PP_FLUSH(vertex_fwd, (long long)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (tid >> 6));
 }
 
 struct VertexBwdArgs {
@@ -156,10 +143,7 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
     __shared__ float s_part[21][12];
     __shared__ int s_last;
     const int b = blockIdx.y, tid = threadIdx.x;
-    MM_PP_BEGIN();
-#ifndef MM_DBG_KEEP_TCNT                                            // (profiles/tools/tex_records.py reads the counts of the step it ran)
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < a.ntcnt; i += gridDim.x * gridDim.y * 256) a.tcnt[i] = 0;
-#endif
     float T[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) T[i] = a.T[b * 12 + i];
@@ -178,7 +162,6 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
         const float ipz = 1.f / pz;                               // one division per vertex, not three per corner
         const float xi = (me.x * a.proj0) * ipz, yi = (me.y * a.proj1) * ipz;
         float d[3] = {0.f, 0.f, 0.f};
-        MM_PP_MARK(0);
         // The vertex's corners from the fixed-stride table: its address depends on nothing but the vertex, so it travels with T and the
         // vertex itself, and the entry carries the face's three vertex ids -- the CSR (offsets -> items -> faces) was two trips more.
         for (int sl8 = cl; sl8 < a.vc_stride; sl8 += 8) {
@@ -189,19 +172,13 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
             const size_t o = (size_t)b * a.F + f;
             // the face's gradients = its sweep items' partial sums, added in index order (one item for most faces)
             float gx = 0.f, gy = 0.f, g[3] = {0.f, 0.f, 0.f};
-#ifndef MM_DBG_VBWD_SKIP
-#define MM_DBG_VBWD_SKIP 0       // traffic break-down builds (WRONG results, profiles/r06_vertex_bwd_traffic.md): 1 no item rows, 2 no face vertices, 4 no chunk map
-#endif
-            const int2 cm = (a.geometry_only || (MM_DBG_VBWD_SKIP & 4) != 0) ? make_int2(0, (MM_DBG_VBWD_SKIP & 4) ? 1 : 0) : a.chunkmap[o];
+            const int2 cm = a.geometry_only ? make_int2(0, 0) : a.chunkmap[o];
             // the face's three vertices ride along with chunkmap: loaded whether or not the normal gradient below turns out to be zero
             // -- inside that branch they would cost a dependent trip to memory of their own
             const int i0 = ent.y, i1 = ent.z, i2 = ent.w;
             float pa[3], pb[3], pc[3];
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                if (MM_DBG_VBWD_SKIP & 2) { pa[j] = p[j]; pb[j] = p[j] + 1.f; pc[j] = p[j] - 1.f; }
-                else { pa[j] = vb[(size_t)i0 * 3 + j]; pb[j] = vb[(size_t)i1 * 3 + j]; pc[j] = vb[(size_t)i2 * 3 + j]; }
-            }
+            for (int j = 0; j < 3; ++j) { pa[j] = vb[(size_t)i0 * 3 + j]; pb[j] = vb[(size_t)i1 * 3 + j]; pc[j] = vb[(size_t)i2 * 3 + j]; }
             const float* part = a.part + ((size_t)b * a.item_cap + cm.x) * 12;
             // the first MM_VBWD_ROWS items' sums in ONE trip (clamped addresses, selected afterwards: a loop over a per-lane count costs a dependent
             // trip per item); the rest MM_VBWD_ROWS at a time.  Added in index order either way.  (A face has ONE item at 128x128 and the spare rows are
@@ -210,7 +187,6 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
 #pragma unroll
             for (int c = 0; c < MM_VBWD_ROWS; ++c) {
                 const float* pc4 = a.part + ((size_t)b * a.item_cap + min(cm.x + min(c, max(cm.y - 1, 0)), a.item_cap - 1)) * 12;   // (a face without items still addresses a valid row)
-                if (MM_DBG_VBWD_SKIP & 1) { pk[c][0] = pk[c][1] = pk[c][2] = pk[c][3] = pk[c][4] = (float)item; continue; }
                 pk[c][0] = pc4[k * 2]; pk[c][1] = pc4[k * 2 + 1]; pk[c][2] = pc4[6]; pk[c][3] = pc4[7]; pk[c][4] = pc4[8];
             }
 #pragma unroll
@@ -259,7 +235,6 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
                 }
             }
         }
-        MM_PP_MARK(1);
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             d[j] += xchg_f32<4>(d[j], tid); d[j] += xchg_f32<2>(d[j], tid); d[j] += xchg_f32<1>(d[j], tid);
@@ -318,7 +293,6 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
     // ---- publish, take a ticket; the last workgroup of this image finishes the camera chain
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the storing wave drains its stores before the ticket is drawn
     __syncthreads();
-    MM_PP_MARK(2);
     if (tid == 0) {
         // No agent-scope fences here: a release fence writes back the XCD's whole L2 and an acquire invalidates it, once per
         // workgroup (removing them took this kernel from 213 to 53 us at B=384).
@@ -326,9 +300,7 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
         s_last = (prev == gridDim.x - 1) ? 1 : 0;
     }
     __syncthreads();
-    MM_PP_MARK(3);
-    if (!s_last) { MM_PP_FLUSH(vertex_bwd, (long long)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (tid >> 6)); return; }
-    MM_PP_MARK(4);
+    if (!s_last) return;
     if (tid >= 64 && tid < 100) reinterpret_cast<float*>(&s_cam)[tid - 64] = a.cam[b * 48 + tid - 64];   // the forward's camera (no trig here)
     {   // dL/dT = sum of the workgroups' partials in a FIXED order: thread (gl, comp) adds rows gl, gl + 21, gl + 42, ... of its component --
         // all of its loads in flight together: ONE trip to memory however many workgroups the image has (6 890 vertices: 216 rows; a pass of
@@ -366,8 +338,6 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
         a.grad_bias[2 * b] = db[0]; a.grad_bias[2 * b + 1] = db[1];
         a.ticket[b] = 0u;                                        // every workgroup of the image has drawn: ready for the next backward on this workspace
     }
-    MM_PP_MARK(5);
-    MM_PP_FLUSH(vertex_bwd, (long long)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (tid >> 6));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -388,9 +358,7 @@ __global__ __launch_bounds__(1024) void vertex_image_bwd_kernel(VertexBwdArgs a)
     __shared__ Camera s_cam;
     __shared__ float s_red[16][12];
     const int b = blockIdx.x, tid = threadIdx.x;
-#ifndef MM_DBG_KEEP_TCNT
     for (int i = b * 1024 + tid; i < a.ntcnt; i += gridDim.x * 1024) a.tcnt[i] = 0;
-#endif
     const float* vb = a.vertices + (size_t)b * a.V * 3;
     // ---- trip 1: what depends on nothing (T, the camera record, this thread's faces' ids and chunk maps, its vertex and its corner list)
     float T[12];
