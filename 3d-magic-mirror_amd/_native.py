@@ -131,8 +131,33 @@ class MMSsimGrads(ctypes.Structure):
     _fields_ = [("grad_ssim", c_p), ("grad_cs", c_p), ("grad_x", c_p), ("grad_y", c_p)]
 
 
+ENCFEAT_MAX_V = 14336                 # MM_ENCFEAT_MAX_V
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+
+
+class MMShapeFeatDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("V", c_i), ("x_dtype", c_i), ("x", c_p),
+                ("x_strides", ctypes.c_int64 * 4), ("template_xyz", c_p), ("col_k", c_i), ("col_idx", c_p), ("col_val", c_p),
+                ("row_k", c_i), ("row_idx", c_p), ("row_val", c_p), ("p", c_p), ("out", c_p),
+                ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class MMShapeFeatGrads(ctypes.Structure):
+    _fields_ = [("grad_out", c_p), ("grad_x", c_p), ("grad_p", c_p)]
+
+
+class MMCameraFeatDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("V", c_i), ("x_dtype", c_i), ("x", c_p),
+                ("x_strides", ctypes.c_int64 * 4), ("template_xyz", c_p), ("p_map", c_p), ("p_local", c_p), ("out", c_p),
+                ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class MMCameraFeatGrads(ctypes.Structure):
+    _fields_ = [("grad_out", c_p), ("grad_x", c_p), ("grad_p_map", c_p), ("grad_p_local", c_p)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
-ABI_VERSION = 8
+ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
 OPT_CULL_STRICT, OPT_SOFT_SKIP_CULLED, OPT_BBOX_HALF_OPEN, OPT_BARY_ONE_MINUS, OPT_SH_ORDER_XYZ = 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8
 OPT_BBOX_MIN_CLOSED_MAX_OPEN = 1 << 9
@@ -149,7 +174,8 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_face_normals_forward", "mm_face_normals_backward", "mm_dibr_query_workspace", "mm_dibr_rasterization_forward",
            "mm_dibr_rasterization_backward", "mm_texture_mapping_forward", "mm_texture_mapping_backward", "mm_texture_mapping_backward_query_workspace", "mm_sh_lighting_forward",
            "mm_sh_lighting_backward", "mm_mask_iou_forward", "mm_mask_iou_backward", "mm_ssim_query_workspace", "mm_ssim_forward",
-           "mm_ssim_backward", "mm_struct_size",
+           "mm_ssim_backward", "mm_shape_features_query_workspace", "mm_shape_features_forward", "mm_shape_features_backward",
+           "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -226,6 +252,14 @@ def lib():
     L.mm_ssim_query_workspace.argtypes = [P(MMSsimDesc)]
     L.mm_ssim_forward.argtypes = [P(MMSsimDesc), c_p]
     L.mm_ssim_backward.argtypes = [P(MMSsimDesc), P(MMSsimGrads), c_p]
+    L.mm_shape_features_query_workspace.restype = ctypes.c_size_t
+    L.mm_shape_features_query_workspace.argtypes = [P(MMShapeFeatDesc)]
+    L.mm_shape_features_forward.argtypes = [P(MMShapeFeatDesc), c_p]
+    L.mm_shape_features_backward.argtypes = [P(MMShapeFeatDesc), P(MMShapeFeatGrads), c_p]
+    L.mm_camera_features_query_workspace.restype = ctypes.c_size_t
+    L.mm_camera_features_query_workspace.argtypes = [P(MMCameraFeatDesc)]
+    L.mm_camera_features_forward.argtypes = [P(MMCameraFeatDesc), c_p]
+    L.mm_camera_features_backward.argtypes = [P(MMCameraFeatDesc), P(MMCameraFeatGrads), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -239,7 +273,7 @@ def lib():
         raise RuntimeError("libmm_render.so has ABI version %d, this binding mirrors version %d" % (L.mm_abi_version(), ABI_VERSION))
     mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
-               MMMaskIouDesc, MMSsimDesc, MMSsimGrads)
+               MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads)
     for i, cls in enumerate(mirrors):
         if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

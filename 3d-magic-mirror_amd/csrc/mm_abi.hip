@@ -29,6 +29,11 @@ int launch_texflow_bwd(const MMTexFlowDesc*, const MMTexFlowGrads*, hipStream_t)
 size_t ssim_workspace_bytes(const MMSsimDesc*);
 int launch_ssim_fwd(const MMSsimDesc*, hipStream_t);
 int launch_ssim_bwd(const MMSsimDesc*, const MMSsimGrads*, hipStream_t);
+size_t encfeat_workspace_bytes(int B, int C, int H, int W, int V, int nparts);
+int launch_shape_feat_fwd(const MMShapeFeatDesc*, hipStream_t);
+int launch_shape_feat_bwd(const MMShapeFeatDesc*, const MMShapeFeatGrads*, hipStream_t);
+int launch_camera_feat_fwd(const MMCameraFeatDesc*, hipStream_t);
+int launch_camera_feat_bwd(const MMCameraFeatDesc*, const MMCameraFeatGrads*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -326,6 +331,64 @@ int mm_ssim_backward(const MMSsimDesc* d, const MMSsimGrads* g, mm_stream_t stre
     return mm::launch_ssim_bwd(d, g, (hipStream_t)stream);
 }
 
+// the sizes both encoder-feature ops share: one workgroup per (b, c) plane, one LDS float per vertex, int32 pixel indices
+static bool encfeat_shape_ok(int B, int C, int H, int W, int V, int dtype) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || V <= 0 || V > MM_ENCFEAT_MAX_V) return false;
+    if (dtype != MM_DTYPE_F32 && dtype != MM_DTYPE_F16 && dtype != MM_DTYPE_BF16) return false;
+    return (int64_t)B * C <= 0x7fffffff && (int64_t)H * W <= (1 << 30);
+}
+
+static bool shape_feat_ok(const MMShapeFeatDesc* d) {
+    return encfeat_shape_ok(d->B, d->C, d->H, d->W, d->V, d->x_dtype) && d->col_k >= 1 && d->col_k <= d->V && d->row_k >= 1 &&
+           d->row_k <= d->V;
+}
+
+size_t mm_shape_features_query_workspace(const MMShapeFeatDesc* d) {
+    if (!d || !shape_feat_ok(d)) return 0;
+    return mm::encfeat_workspace_bytes(d->B, d->C, d->H, d->W, d->V, 1);
+}
+
+int mm_shape_features_forward(const MMShapeFeatDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (!shape_feat_ok(d)) return MM_ERR_BAD_SHAPE;
+    if (!d->x || !d->template_xyz || !d->col_idx || !d->col_val || !d->p || !d->out) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_shape_feat_fwd(d, (hipStream_t)stream);
+}
+
+int mm_shape_features_backward(const MMShapeFeatDesc* d, const MMShapeFeatGrads* g, mm_stream_t stream) {
+    if (!d || !g) return MM_ERR_NULL_POINTER;
+    if (!shape_feat_ok(d)) return MM_ERR_BAD_SHAPE;
+    if (!d->x || !d->template_xyz || !d->row_idx || !d->row_val || !d->p || !g->grad_out || (!g->grad_x && !g->grad_p))
+        return MM_ERR_NULL_POINTER;
+    if (!d->workspace || d->workspace_bytes < mm_shape_features_query_workspace(d)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_shape_feat_bwd(d, g, (hipStream_t)stream);
+}
+
+size_t mm_camera_features_query_workspace(const MMCameraFeatDesc* d) {
+    if (!d || !encfeat_shape_ok(d->B, d->C, d->H, d->W, d->V, d->x_dtype)) return 0;
+    return mm::encfeat_workspace_bytes(d->B, d->C, d->H, d->W, d->V, 2);
+}
+
+int mm_camera_features_forward(const MMCameraFeatDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (!encfeat_shape_ok(d->B, d->C, d->H, d->W, d->V, d->x_dtype)) return MM_ERR_BAD_SHAPE;
+    if (!d->x || !d->template_xyz || !d->p_map || !d->p_local || !d->out) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_camera_feat_fwd(d, (hipStream_t)stream);
+}
+
+int mm_camera_features_backward(const MMCameraFeatDesc* d, const MMCameraFeatGrads* g, mm_stream_t stream) {
+    if (!d || !g) return MM_ERR_NULL_POINTER;
+    if (!encfeat_shape_ok(d->B, d->C, d->H, d->W, d->V, d->x_dtype)) return MM_ERR_BAD_SHAPE;
+    if (!d->x || !d->template_xyz || !d->p_map || !d->p_local || !g->grad_out || (!g->grad_x && !g->grad_p_map && !g->grad_p_local))
+        return MM_ERR_NULL_POINTER;
+    if (!d->workspace || d->workspace_bytes < mm_camera_features_query_workspace(d)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_camera_feat_bwd(d, g, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -393,7 +456,8 @@ size_t mm_struct_size(int which) {
         case 9: return sizeof(MMPrepareDesc);   case 10: return sizeof(MMPrepareGrads); case 11: return sizeof(MMDibrDesc);
         case 12: return sizeof(MMDibrGrads);    case 13: return sizeof(MMTexMapDesc);   case 14: return sizeof(MMTexMapGrads);
         case 15: return sizeof(MMShDesc);       case 16: return sizeof(MMShGrads);      case 17: return sizeof(MMMaskIouDesc);
-        case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);
+        case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);    case 20: return sizeof(MMShapeFeatDesc);
+        case 21: return sizeof(MMShapeFeatGrads); case 22: return sizeof(MMCameraFeatDesc); case 23: return sizeof(MMCameraFeatGrads);
         default: return 0;
     }
 }

@@ -513,6 +513,69 @@ int mm_ssim_forward(const MMSsimDesc* desc, mm_stream_t stream);
 int mm_ssim_backward(const MMSsimDesc* desc, const MMSsimGrads* grads, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Template-anchored encoder features: the non-convolutional block the shape and camera encoders run on their backbone's
+ * (B,C,H,W) map (reference network/model_res.py: ShapeEncoder.forward, CameraEncoder.forward).  Per (b, c) plane:
+ *   local[v] = bilinear sample at template (x, y) = columns 0, 1 in [-1, 1] (-1 = first column / row), zero padding
+ *   mmpool   = sigmoid(p) * max + (1 - sigmoid(p)) * mean, over an adaptive-pool bin [floor(i n / k), ceil((i + 1) n / k))
+ * Shape:  out (B, 3C+3, V) = cat(local, mmpool_1x1 repeated over V, neighbor, template xyz), align_corners = 1, where
+ *         neighbor[u] = sum_v local[v] lpl[v,u] over the non-zeros of the (V,V) lpl, given as two fixed-stride tables.
+ * Camera: out (B, 2C, 2, 2) = cat(mmpool_2x2(x; p_map), mmpool_2x2(local as a (V,1) map; p_local)), align_corners = 0.
+ * The max's gradient goes to the FIRST maximal element of a bin in row-major order.  No float atomics: every sum has a fixed
+ * order, so both directions are bitwise reproducible.  The forward is one launch and needs no workspace; the backward builds
+ * the per-pixel (vertex, weight) list of the bilinear taps in the workspace (three launches), applies the taps as a gather,
+ * and sums the p gradients in a fixed order (two launches).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_ENCFEAT_MAX_V 14336      /* most template vertices (one float per vertex in LDS) */
+enum { MM_DTYPE_F32 = 0, MM_DTYPE_F16 = 1, MM_DTYPE_BF16 = 2 };
+typedef struct MMShapeFeatDesc {
+    int32_t B, C, H, W, V;          /* B*C <= 2^31 - 1, H*W <= 2^30, V <= MM_ENCFEAT_MAX_V */
+    int32_t x_dtype;                /* MM_DTYPE_* */
+    const void* x;                  /* (B,C,H,W) at x + b*x_strides[0] + c*x_strides[1] + h*x_strides[2] + w*x_strides[3] (elements) */
+    int64_t x_strides[4];
+    const float* template_xyz;      /* (V,3) dense */
+    int32_t col_k;                  /* entries per column of lpl, 1..V */
+    const int32_t* col_idx;         /* (col_k, V): row v of the k-th non-zero of column u at [k*V + u], -1 = none */
+    const float* col_val;           /* (col_k, V): lpl[v,u] there (0 where none) */
+    int32_t row_k;                  /* entries per row of lpl, 1..V */
+    const int32_t* row_idx;         /* (row_k, V): column u of the k-th non-zero of row v at [k*V + v], -1 = none (backward) */
+    const float* row_val;           /* (row_k, V) */
+    const float* p;                 /* (1) MMPool.p, device memory */
+    float* out;                     /* (B, 3C+3, V) dense: written by the forward */
+    void* workspace;                /* mm_shape_features_query_workspace bytes: scratch of the backward, unused by the forward */
+    size_t workspace_bytes;
+} MMShapeFeatDesc;
+typedef struct MMShapeFeatGrads {
+    const float* grad_out;          /* (B, 3C+3, V) dense */
+    void* grad_x;                   /* (B,C,H,W) dense in x_dtype, every element overwritten, or NULL */
+    float* grad_p;                  /* (1) overwritten, or NULL; not both NULL */
+} MMShapeFeatGrads;
+typedef struct MMCameraFeatDesc {
+    int32_t B, C, H, W, V;          /* limits as MMShapeFeatDesc */
+    int32_t x_dtype;
+    const void* x;
+    int64_t x_strides[4];
+    const float* template_xyz;      /* (V,3) dense; columns 0, 1 sample */
+    const float* p_map;             /* (1) MMPool.p of the pool over x */
+    const float* p_local;           /* (1) MMPool.p of the pool over the sampled (V,1) map */
+    float* out;                     /* (B, 2C, 2, 2) dense */
+    void* workspace;                /* mm_camera_features_query_workspace bytes: scratch of the backward */
+    size_t workspace_bytes;
+} MMCameraFeatDesc;
+typedef struct MMCameraFeatGrads {
+    const float* grad_out;          /* (B, 2C, 2, 2) dense */
+    void* grad_x;                   /* (B,C,H,W) dense in x_dtype, or NULL */
+    float* grad_p_map;              /* (1), or NULL */
+    float* grad_p_local;            /* (1), or NULL; not all three NULL */
+} MMCameraFeatGrads;
+/* bytes of workspace the backward of this shape needs; 0 for a bad shape */
+size_t mm_shape_features_query_workspace(const MMShapeFeatDesc* desc);
+int mm_shape_features_forward(const MMShapeFeatDesc* desc, mm_stream_t stream);
+int mm_shape_features_backward(const MMShapeFeatDesc* desc, const MMShapeFeatGrads* grads, mm_stream_t stream);
+size_t mm_camera_features_query_workspace(const MMCameraFeatDesc* desc);
+int mm_camera_features_forward(const MMCameraFeatDesc* desc, mm_stream_t stream);
+int mm_camera_features_backward(const MMCameraFeatDesc* desc, const MMCameraFeatGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -534,14 +597,15 @@ const char* mm_last_error_detail(void);
  * compiled, 0 for an unknown id.  Ids: 0 MMRenderDesc, 1 MMRenderGrads, 2 MMReconDesc, 3 MMMeshRegDesc, 4 MMMeshRegGrads,
  * 5 MMAttLossDesc, 6 MMAttLossGrads, 7 MMTexFlowDesc, 8 MMTexFlowGrads, 9 MMPrepareDesc, 10 MMPrepareGrads, 11 MMDibrDesc,
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
- * 19 MMSsimGrads. */
+ * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
  * MM_OPT_BBOX_MIN_CLOSED_MAX_OPEN; 4: MMRenderDesc.geometry_only / status_flag, MMPrepareDesc.proj_device, MMTexMapGrads.workspace, mm_chamfer_nearest, mm_build_vertex_corner_csr_device; 5: MMRenderDesc.fused_contour; 6: MMRenderDesc.fused_totals, mm_recon_data_totals; still 6: the hint bit MM_OPT_MANY_IN_FLIGHT, which changes no result and no layout; 7: MMSsimDesc, MMSsimGrads,
  * mm_ssim_query_workspace / mm_ssim_forward / mm_ssim_backward, struct ids 18 and 19; 8: mm_chamfer_backward, and mm_nearest_neighbour
- * refuses B > 65535 as mm_chamfer_nearest does).  Bindings must refuse a library whose version differs from what they mirror. */
-#define MM_ABI_VERSION 8
+ * refuses B > 65535 as mm_chamfer_nearest does; 9: MMShapeFeatDesc / Grads, MMCameraFeatDesc / Grads, mm_shape_features_* and
+ * mm_camera_features_*, struct ids 20-23).  Bindings must refuse a library whose version differs from what they mirror. */
+#define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
 #ifdef __cplusplus
