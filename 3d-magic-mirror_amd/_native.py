@@ -156,6 +156,20 @@ class MMCameraFeatGrads(ctypes.Structure):
     _fields_ = [("grad_out", c_p), ("grad_x", c_p), ("grad_p_map", c_p), ("grad_p_local", c_p)]
 
 
+class MMInterpDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("V", c_i), ("Ht", c_i), ("Wt", c_i), ("H", c_i), ("W", c_i),
+                ("vertices", c_p), ("delta_vertices", c_p), ("textures", c_p), ("bg", c_p), ("lights", c_p),
+                ("out_vertices", c_p), ("out_delta_vertices", c_p), ("out_textures", c_p), ("out_bg", c_p), ("out_lights", c_p),
+                ("idx_a", c_p), ("idx_b", c_p), ("alpha_shape", c_p), ("alpha_texture", c_p), ("alpha_light", c_p),
+                ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class MMInterpGrads(ctypes.Structure):
+    _fields_ = [("grad_out_vertices", c_p), ("grad_out_delta_vertices", c_p), ("grad_out_textures", c_p), ("grad_out_bg", c_p),
+                ("grad_out_lights", c_p), ("grad_vertices", c_p), ("grad_delta_vertices", c_p), ("grad_textures", c_p), ("grad_bg", c_p),
+                ("grad_lights", c_p)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -175,7 +189,8 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_dibr_rasterization_backward", "mm_texture_mapping_forward", "mm_texture_mapping_backward", "mm_texture_mapping_backward_query_workspace", "mm_sh_lighting_forward",
            "mm_sh_lighting_backward", "mm_mask_iou_forward", "mm_mask_iou_backward", "mm_ssim_query_workspace", "mm_ssim_forward",
            "mm_ssim_backward", "mm_shape_features_query_workspace", "mm_shape_features_forward", "mm_shape_features_backward",
-           "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward", "mm_struct_size",
+           "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward",
+           "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -260,6 +275,11 @@ def lib():
     L.mm_camera_features_query_workspace.argtypes = [P(MMCameraFeatDesc)]
     L.mm_camera_features_forward.argtypes = [P(MMCameraFeatDesc), c_p]
     L.mm_camera_features_backward.argtypes = [P(MMCameraFeatDesc), P(MMCameraFeatGrads), c_p]
+    L.mm_interp_query_workspace.restype = ctypes.c_size_t
+    L.mm_interp_query_workspace.argtypes = [P(MMInterpDesc)]
+    L.mm_collapse_resample.argtypes = [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p]
+    L.mm_attribute_mix_forward.argtypes = [P(MMInterpDesc), c_p]
+    L.mm_attribute_mix_backward.argtypes = [P(MMInterpDesc), P(MMInterpGrads), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -273,7 +293,8 @@ def lib():
         raise RuntimeError("libmm_render.so has ABI version %d, this binding mirrors version %d" % (L.mm_abi_version(), ABI_VERSION))
     mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
-               MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads)
+               MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
+               MMInterpDesc, MMInterpGrads)
     for i, cls in enumerate(mirrors):
         if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

@@ -34,6 +34,10 @@ int launch_shape_feat_fwd(const MMShapeFeatDesc*, hipStream_t);
 int launch_shape_feat_bwd(const MMShapeFeatDesc*, const MMShapeFeatGrads*, hipStream_t);
 int launch_camera_feat_fwd(const MMCameraFeatDesc*, hipStream_t);
 int launch_camera_feat_bwd(const MMCameraFeatDesc*, const MMCameraFeatGrads*, hipStream_t);
+size_t interp_workspace_bytes(int B);
+int launch_mix_fwd(const MMInterpDesc*, hipStream_t);
+int launch_mix_bwd(const MMInterpDesc*, const MMInterpGrads*, hipStream_t);
+int launch_collapse_resample(int B, int V, const float* dv, int* idx_a, int* idx_b, const float* u, float thr, int* n_bad, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -389,6 +393,64 @@ int mm_camera_features_backward(const MMCameraFeatDesc* d, const MMCameraFeatGra
     return mm::launch_camera_feat_bwd(d, g, (hipStream_t)stream);
 }
 
+// sizes of the attribute mix: every row length and the launch's chunk count (one chunk per <= 1024 floats of a row) fit an int32
+// has_bg: the forward's bg, or the backward's bg gradient pair (the backward reads no source)
+static int interp_shape(const MMInterpDesc* d, bool has_bg) {
+    if (d->B <= 0 || d->V <= 0 || d->Ht <= 0 || d->Wt <= 0 || (has_bg && (d->H <= 0 || d->W <= 0))) return MM_ERR_BAD_SHAPE;
+    if (d->B > 65535) return MM_ERR_UNSUPPORTED;
+    const int64_t lens[3] = {3LL * d->V, 3LL * d->Ht * d->Wt, has_bg ? 3LL * d->H * d->W : 0};
+    int64_t chunks = 2 * (lens[0] / 1024 + 1) + 1;
+    for (int t = 1; t < 3; ++t) {
+        if (lens[t] > 0x7fffffff) return MM_ERR_UNSUPPORTED;
+        chunks += lens[t] / 1024 + 1;
+    }
+    return chunks * d->B > 0x7fffffff ? MM_ERR_UNSUPPORTED : MM_OK;
+}
+
+size_t mm_interp_query_workspace(const MMInterpDesc* d) {
+    if (!d || interp_shape(d, false) != MM_OK) return 0;
+    return mm::interp_workspace_bytes(d->B);
+}
+
+int mm_attribute_mix_forward(const MMInterpDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    const int st = interp_shape(d, d->bg != nullptr);
+    if (st != MM_OK) return st;
+    if (!d->vertices || !d->delta_vertices || !d->textures || !d->lights || !d->out_vertices || !d->out_delta_vertices ||
+        !d->out_textures || !d->out_lights || (d->bg && !d->out_bg) || !d->idx_a || !d->idx_b || !d->alpha_shape || !d->alpha_texture ||
+        !d->alpha_light)
+        return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_mix_fwd(d, (hipStream_t)stream);
+}
+
+int mm_attribute_mix_backward(const MMInterpDesc* d, const MMInterpGrads* g, mm_stream_t stream) {
+    if (!d || !g) return MM_ERR_NULL_POINTER;
+    const int st = interp_shape(d, g->grad_out_bg || g->grad_bg);
+    if (st != MM_OK) return st;
+    if (!d->idx_a || !d->idx_b || !d->alpha_shape || !d->alpha_texture || !d->alpha_light) return MM_ERR_NULL_POINTER;
+    const void* up[5] = {g->grad_out_vertices, g->grad_out_delta_vertices, g->grad_out_textures, g->grad_out_bg, g->grad_out_lights};
+    const void* gs[5] = {g->grad_vertices, g->grad_delta_vertices, g->grad_textures, g->grad_bg, g->grad_lights};
+    bool any = false;
+    for (int t = 0; t < 5; ++t) {
+        if (!up[t] != !gs[t]) return MM_ERR_NULL_POINTER;     // an upstream gradient without its destination, or the reverse
+        any = any || up[t];
+    }
+    if (!any) return MM_OK;                                   // nothing to differentiate: nothing is launched
+    if (!d->workspace || d->workspace_bytes < mm_interp_query_workspace(d)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_mix_bwd(d, g, (hipStream_t)stream);
+}
+
+int mm_collapse_resample(int32_t B, int32_t V, const float* delta_vertices, int32_t* idx_a, int32_t* idx_b, const float* uniforms,
+                         float threshold, int32_t* n_bad, mm_stream_t stream) {
+    if (!delta_vertices || !idx_a || !idx_b || !uniforms || !n_bad) return MM_ERR_NULL_POINTER;
+    if (B <= 0 || V <= 0) return MM_ERR_BAD_SHAPE;
+    if (B > 65535) return MM_ERR_UNSUPPORTED;                     // the good mask lives in LDS: one bit per sample
+    mm::clear_stale_error();
+    return mm::launch_collapse_resample(B, V, delta_vertices, idx_a, idx_b, uniforms, threshold, n_bad, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -458,6 +520,7 @@ size_t mm_struct_size(int which) {
         case 15: return sizeof(MMShDesc);       case 16: return sizeof(MMShGrads);      case 17: return sizeof(MMMaskIouDesc);
         case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);    case 20: return sizeof(MMShapeFeatDesc);
         case 21: return sizeof(MMShapeFeatGrads); case 22: return sizeof(MMCameraFeatDesc); case 23: return sizeof(MMCameraFeatGrads);
+        case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);
         default: return 0;
     }
 }

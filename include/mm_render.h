@@ -576,6 +576,63 @@ int mm_camera_features_forward(const MMCameraFeatDesc* desc, mm_stream_t stream)
 int mm_camera_features_backward(const MMCameraFeatDesc* desc, const MMCameraFeatGrads* grads, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Attribute interpolation: the block the reference's generator step runs between its first and second render
+ * (trainer.py:293-342).  For every output row j of each of the five attribute tensors:
+ *   out[j] = fl(fl(a[j] * src[ia[j]]) + fl(fl(1 - a[j]) * src[ib[j]]))     (every operation rounded in fp32: torch's eager result)
+ * with a = alpha_shape for vertices and delta_vertices, alpha_texture for textures and bg, alpha_light for lights.  A row whose ia
+ * or ib lies outside [0, B) is written as NaN and nothing is read for it.  The backward gives source row i
+ *   sum over j with ia[j] == i, ascending, of fl(a[j] * g[j]), then over j with ib[j] == i, ascending, of fl(fl(1 - a[j]) * g[j]),
+ * accumulated left to right from +0.0 (rows nobody selected: 0).  No float atomics; bitwise reproducible.  The forward is one
+ * launch and needs no workspace; the backward builds the inverse index lists in the workspace (one small launch) and gathers.
+ * B <= 65535 (MM_ERR_UNSUPPORTED otherwise).  All tensors fp32, dense, rows contiguous.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct MMInterpDesc {
+    int32_t B, V, Ht, Wt, H, W;     /* H, W are read only when bg (forward) or bg's gradient pair (backward) is given */
+    const float* vertices;          /* (B,V,3) */
+    const float* delta_vertices;    /* (B,V,3) */
+    const float* textures;          /* (B,3,Ht,Wt) */
+    const float* bg;                /* (B,3,H,W), or NULL */
+    const float* lights;            /* (B,9) */
+    float* out_vertices;            /* outputs of the forward, shaped like the sources */
+    float* out_delta_vertices;
+    float* out_textures;
+    float* out_bg;                  /* ignored when bg is NULL */
+    float* out_lights;
+    const int32_t* idx_a;           /* (B) device: the row each output row takes with weight a */
+    const int32_t* idx_b;           /* (B) device: ... with weight 1 - a */
+    const float* alpha_shape;       /* (B) */
+    const float* alpha_texture;     /* (B) */
+    const float* alpha_light;       /* (B) */
+    void* workspace;                /* mm_interp_query_workspace bytes: scratch of the backward, unused by the forward */
+    size_t workspace_bytes;
+} MMInterpDesc;
+typedef struct MMInterpGrads {
+    /* per tensor an upstream gradient (shaped like the output) and the source gradient it produces (overwritten), both given or both
+     * NULL; a NULL pair is skipped (no launch at all when all five are).  The backward reads none of the sources. */
+    const float* grad_out_vertices;
+    const float* grad_out_delta_vertices;
+    const float* grad_out_textures;
+    const float* grad_out_bg;
+    const float* grad_out_lights;
+    float* grad_vertices;
+    float* grad_delta_vertices;
+    float* grad_textures;
+    float* grad_bg;
+    float* grad_lights;
+} MMInterpGrads;
+/* bytes of workspace the backward needs for this B; 0 for a bad shape */
+size_t mm_interp_query_workspace(const MMInterpDesc* desc);
+/* Collapse resampling, one launch: bad[b] = ((|x| + |y|) + |z|) / 3 > threshold over the last vertex of delta_vertices (B,V,3),
+ * in fp32; a NaN mean is not bad.  good = the samples that are not bad, ascending.  Every slot s of idx_a holding a bad sample is
+ * set to good[min(floor(fl(uniforms[s] * n_good)), n_good - 1)], and every such slot of idx_b to the same with uniforms[B + s]
+ * (uniforms: (2,B) in [0, 1)).  Indices outside [0, B) are left as they are.  *n_bad (device int) = the number of bad samples; when
+ * every sample is bad the indices are left unchanged and *n_bad = B. */
+int mm_collapse_resample(int32_t B, int32_t V, const float* delta_vertices, int32_t* idx_a, int32_t* idx_b, const float* uniforms,
+                         float threshold, int32_t* n_bad, mm_stream_t stream);
+int mm_attribute_mix_forward(const MMInterpDesc* desc, mm_stream_t stream);
+int mm_attribute_mix_backward(const MMInterpDesc* desc, const MMInterpGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -597,14 +654,17 @@ const char* mm_last_error_detail(void);
  * compiled, 0 for an unknown id.  Ids: 0 MMRenderDesc, 1 MMRenderGrads, 2 MMReconDesc, 3 MMMeshRegDesc, 4 MMMeshRegGrads,
  * 5 MMAttLossDesc, 6 MMAttLossGrads, 7 MMTexFlowDesc, 8 MMTexFlowGrads, 9 MMPrepareDesc, 10 MMPrepareGrads, 11 MMDibrDesc,
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
- * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads. */
+ * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
+ * 25 MMInterpGrads. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
  * MM_OPT_BBOX_MIN_CLOSED_MAX_OPEN; 4: MMRenderDesc.geometry_only / status_flag, MMPrepareDesc.proj_device, MMTexMapGrads.workspace, mm_chamfer_nearest, mm_build_vertex_corner_csr_device; 5: MMRenderDesc.fused_contour; 6: MMRenderDesc.fused_totals, mm_recon_data_totals; still 6: the hint bit MM_OPT_MANY_IN_FLIGHT, which changes no result and no layout; 7: MMSsimDesc, MMSsimGrads,
  * mm_ssim_query_workspace / mm_ssim_forward / mm_ssim_backward, struct ids 18 and 19; 8: mm_chamfer_backward, and mm_nearest_neighbour
  * refuses B > 65535 as mm_chamfer_nearest does; 9: MMShapeFeatDesc / Grads, MMCameraFeatDesc / Grads, mm_shape_features_* and
- * mm_camera_features_*, struct ids 20-23).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_camera_features_*, struct ids 20-23; still 9: MMInterpDesc / Grads, mm_interp_query_workspace, mm_collapse_resample and
+ * mm_attribute_mix_*, struct ids 24 and 25, which only add -- no existing struct, field or meaning changes; a binding detects them by
+ * mm_struct_size(24) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
