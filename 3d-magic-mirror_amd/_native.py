@@ -35,6 +35,10 @@ class MMRenderGrads(ctypes.Structure):
                 ("grad_distances", c_p), ("grad_biases", c_p)]
 
 
+class MMRenderViewsDesc(ctypes.Structure):
+    _fields_ = [("render", MMRenderDesc), ("views", c_i)]
+
+
 class MMReconDesc(ctypes.Structure):
     _fields_ = [("B", c_i), ("H", c_i), ("W", c_i), ("pred", c_p), ("pred_strides", ctypes.c_int64 * 4), ("gt", c_p),
                 ("image_weight", c_f), ("contour", c_f), ("loss", c_p), ("grad_loss", c_p), ("grad_pred", c_p),
@@ -190,7 +194,8 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_sh_lighting_backward", "mm_mask_iou_forward", "mm_mask_iou_backward", "mm_ssim_query_workspace", "mm_ssim_forward",
            "mm_ssim_backward", "mm_shape_features_query_workspace", "mm_shape_features_forward", "mm_shape_features_backward",
            "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward",
-           "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward", "mm_struct_size",
+           "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
+           "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -280,6 +285,10 @@ def lib():
     L.mm_collapse_resample.argtypes = [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p]
     L.mm_attribute_mix_forward.argtypes = [P(MMInterpDesc), c_p]
     L.mm_attribute_mix_backward.argtypes = [P(MMInterpDesc), P(MMInterpGrads), c_p]
+    L.mm_render_views_query_workspace.restype = ctypes.c_size_t
+    L.mm_render_views_query_workspace.argtypes = [P(MMRenderViewsDesc)]
+    L.mm_render_views_forward.argtypes = [P(MMRenderViewsDesc), c_p]
+    L.mm_render_views_backward.argtypes = [P(MMRenderViewsDesc), P(MMRenderGrads), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -294,7 +303,7 @@ def lib():
     mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
                MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
-               MMInterpDesc, MMInterpGrads)
+               MMInterpDesc, MMInterpGrads, MMRenderViewsDesc)
     for i, cls in enumerate(mirrors):
         if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

@@ -6,10 +6,12 @@
 #include "mm_device.h"
 
 namespace mm {
-int launch_vertex_fwd(const MMRenderDesc*, const Workspace&, hipStream_t);
-int launch_vertex_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t);
-int launch_raster_fwd(const MMRenderDesc*, const Workspace&, hipStream_t);
-int launch_raster_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t);
+// views: images per sample of a multi-view call (the per-sample inputs then hold B / views rows); 1 = mm_render_forward / mm_render_backward
+int launch_vertex_fwd(const MMRenderDesc*, const Workspace&, hipStream_t, int views = 1);
+int launch_vertex_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t, int views = 1);
+int launch_raster_fwd(const MMRenderDesc*, const Workspace&, hipStream_t, int views = 1);
+int launch_raster_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t, int views = 1);
+int launch_view_sum(int B, int views, const float* const* staging, float* const* out, const int* len, hipStream_t);
 int launch_fused_loss(const MMRenderDesc*, const Workspace&, hipStream_t);
 size_t recon_workspace_bytes(const MMReconDesc*);
 int launch_recon_fwd(const MMReconDesc*, hipStream_t);
@@ -139,6 +141,36 @@ int mm_render_backward(const MMRenderDesc* d, const MMRenderGrads* g, mm_stream_
     return mm::launch_vertex_bwd(d, g, w, s);
 }
 
+// ---- multi-view render (include/mm_render.h: MMRenderViewsDesc) ------------------------------------------------------------------------
+// staging areas of the per-image gradients of the four per-sample inputs, (B*N, row) floats each, at the HEAD of a multi-view workspace: the
+// render workspace of the B*N images follows them with exactly the bytes that are left, as mm_render_forward would be given them
+struct ViewsStaging { size_t off[4]; int len[4]; size_t bytes; };
+static ViewsStaging views_staging(const MMRenderDesc* d) {
+    ViewsStaging st;
+    const size_t rows[4] = {(size_t)d->V * 3, (size_t)3 * d->Ht * d->Wt, 9, (size_t)3 * d->H * d->W};
+    size_t o = 0;
+    for (int t = 0; t < 4; ++t) { st.off[t] = o; st.len[t] = (int)rows[t]; o += mm::align256((size_t)d->B * rows[t] * sizeof(float)); }
+    st.bytes = o;
+    return st;
+}
+
+// everything checked before any launch; *r = the descriptor of the B*N images as the render kernels take it (the workspace without the staging)
+static int check_render_views(const MMRenderViewsDesc* v, bool backward, MMRenderDesc* r) {
+    if (!v) return MM_ERR_NULL_POINTER;
+    const MMRenderDesc* d = &v->render;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->V <= 0 || d->F <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
+    if (v->views < 1 || d->B % v->views != 0) return MM_ERR_BAD_SHAPE;
+    if (d->fused_gt || d->fused_totals || d->geometry_only) return MM_ERR_UNSUPPORTED;    // fused / deferred losses and geometry-only over views: not built
+    if ((size_t)3 * d->Ht * d->Wt > 0x7fffffff || (size_t)3 * d->H * d->W > 0x7fffffff || d->B / v->views > 65535) return MM_ERR_UNSUPPORTED;
+    *r = *d;
+    if (v->views > 1) {
+        const size_t st = views_staging(d).bytes;
+        r->workspace = d->workspace ? (char*)d->workspace + st : nullptr;      // (st is a multiple of 256: the alignment is the caller's)
+        r->workspace_bytes = d->workspace_bytes > st ? d->workspace_bytes - st : 0;
+    }
+    return check_render(r, backward);
+}
+
 static int check_recon(const MMReconDesc* d, bool backward) {
     if (!d) return MM_ERR_NULL_POINTER;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0) return MM_ERR_BAD_SHAPE;
@@ -148,6 +180,52 @@ static int check_recon(const MMReconDesc* d, bool backward) {
     if (d->contour > 0.f && (d->H < 4 || d->W < 4)) return MM_ERR_BAD_SHAPE;
     if (!d->workspace || d->workspace_bytes < mm_recon_query_workspace(d)) return MM_ERR_WORKSPACE;
     return MM_OK;
+}
+
+size_t mm_render_views_query_workspace(const MMRenderViewsDesc* v) {
+    if (!v || v->views < 1 || v->render.B <= 0 || v->render.B % v->views != 0) return 0;
+    const size_t base = mm_query_workspace(&v->render);
+    if (base == 0 || v->views == 1) return base;
+    return base + views_staging(&v->render).bytes;
+}
+
+int mm_render_views_forward(const MMRenderViewsDesc* v, mm_stream_t stream) {
+    MMRenderDesc r;
+    int st = check_render_views(v, false, &r);
+    if (st != MM_OK) return st;
+    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    hipStream_t s = (hipStream_t)stream;
+    mm::clear_stale_error();
+    st = mm::launch_vertex_fwd(&r, w, s, v->views);
+    if (st != MM_OK) return st;
+    return mm::launch_raster_fwd(&r, w, s, v->views);
+}
+
+int mm_render_views_backward(const MMRenderViewsDesc* v, const MMRenderGrads* g, mm_stream_t stream) {
+    MMRenderDesc r;
+    int st = check_render_views(v, true, &r);
+    if (st != MM_OK) return st;
+    if (!g || !g->grad_vertices || !g->grad_azimuths || !g->grad_elevations || !g->grad_distances || !g->grad_biases || !g->grad_rgba ||
+        !g->grad_textures || !g->grad_lights || (r.no_mask && !g->grad_bg))
+        return MM_ERR_NULL_POINTER;
+    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    hipStream_t s = (hipStream_t)stream;
+    MMRenderGrads gi = *g;                                        // the per-image gradients the kernels write
+    const ViewsStaging stg = views_staging(&r);
+    float* staging[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (v->views > 1) {
+        char* base = (char*)v->render.workspace;
+        for (int t = 0; t < 4; ++t) staging[t] = (float*)(base + stg.off[t]);
+        gi.grad_vertices = staging[0]; gi.grad_textures = staging[1]; gi.grad_lights = staging[2];
+        gi.grad_bg = r.no_mask ? staging[3] : nullptr;
+    }
+    mm::clear_stale_error();
+    st = mm::launch_raster_bwd(&r, &gi, w, s, v->views);
+    if (st != MM_OK) return st;
+    st = mm::launch_vertex_bwd(&r, &gi, w, s, v->views);
+    if (st != MM_OK || v->views == 1) return st;
+    float* out[4] = {g->grad_vertices, g->grad_textures, g->grad_lights, r.no_mask ? g->grad_bg : nullptr};
+    return mm::launch_view_sum(r.B / v->views, v->views, staging, out, stg.len, s);
 }
 
 size_t mm_recon_query_workspace(const MMReconDesc* d) {
@@ -520,7 +598,7 @@ size_t mm_struct_size(int which) {
         case 15: return sizeof(MMShDesc);       case 16: return sizeof(MMShGrads);      case 17: return sizeof(MMMaskIouDesc);
         case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);    case 20: return sizeof(MMShapeFeatDesc);
         case 21: return sizeof(MMShapeFeatGrads); case 22: return sizeof(MMCameraFeatDesc); case 23: return sizeof(MMCameraFeatGrads);
-        case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);
+        case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);  case 26: return sizeof(MMRenderViewsDesc);
         default: return 0;
     }
 }

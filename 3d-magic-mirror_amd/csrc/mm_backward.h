@@ -43,6 +43,9 @@ struct BwdArgs {
     const int2* items; const int2* nitems; float* part; int item_cap;   // sweep items {face, chunk} of the plan workgroups; their partial sums
     int2* plan_chunkmap; int2* plan_items; int2* plan_nitems; int plan_wgs;           // ... as the plan workgroups (first B of pixel_bwd's grid) write them
     int ntx, nty;
+    int views;                                                   // multi-view calls (mm_render_views_backward): images per sample -- textures, lights and bg hold
+                                                                 // B / views rows, image b reads row b / views (pixel_bwd's kViews instantiations only); every
+                                                                 // gradient stays per image.  (Here it fills the padding in front of the pointer: no offset moves.)
     float* grad_textures;
 };
 

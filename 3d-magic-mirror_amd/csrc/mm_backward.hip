@@ -443,8 +443,9 @@ int launch_fused_loss(const MMRenderDesc* d, const Workspace& w, hipStream_t s) 
     return launch_ok("fused_loss");
 }
 
-int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s) {
+int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views) {
     BwdArgs a;
+    a.views = views;
     a.B = d->B; a.H = d->H; a.W = d->W; a.F = d->F; a.Ht = d->Ht; a.Wt = d->Wt; a.knum = d->knum;
     a.blocks_x = (d->W + MM_BLOCK_PX - 1) / MM_BLOCK_PX;
     a.blocks_per_image = w.blocks_per_image; a.options = d->options;

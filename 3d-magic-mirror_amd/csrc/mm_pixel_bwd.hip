@@ -128,7 +128,9 @@ __device__ inline void plan_sweep_items(const BwdArgs& a, int b, int q) {
 // kDeferred: DEFERRED fusion (BwdArgs::ltot as deferred_totals, MMRenderDesc.fused_totals): recon_data ran on its own on the image this render wrote; dL/d rgba is formed
 // here with mm_recon_data_backward's expressions (csrc/mm_loss.hip: recon_bwd_kernel), in their order, from that call's per-image totals -- the bits
 // that kernel would have written -- plus the caller's grad_rgba if there is one.  Never together with kContour.
-template <bool kNoMask, bool kContour, bool kDeferred>
+// kViews: a multi-view call (BwdArgs::views > 1; never fused): bg, lights and textures are read from the image's SAMPLE (row b / views); what is
+// written -- grad_bg included -- stays per image.  mm_render_backward launches the kViews = false instantiations, which hold none of that code.
+template <bool kNoMask, bool kContour, bool kDeferred, bool kViews>
 __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) {
     __shared__ float s_dl[MM_BLOCK_WAVES][9];
     __shared__ float s_gm[MM_BLOCK_WAVES][2];
@@ -142,6 +144,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     const float x0 = pixel_x_k(px, a.W, a.kx), y0 = pixel_y_k(py, a.H, a.ky);                  // (host-formed IEEE quotients: the forward's centres)
     const size_t hw = (size_t)a.H * a.W, pin = (size_t)py * a.W + px;
     const size_t pix = (size_t)b * hw + pin;
+    const int sb = kViews ? b / a.views : b;                      // the row of the per-sample inputs
     if (blk == 0 && threadIdx.x == 0) a.ticket[b] = 0u;           // arrival counter of the vertex backward, used after this kernel
     // The pass is a chain of dependent trips to memory; it is written so that four remain: (1) everything addressed by the pixel
     // alone -- face_idx, prediction, ground truth, background; (2) what the winner's id addresses -- geometry, normal, corner uvs;
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     float bgv[3] = {0.f, 0.f, 0.f};
     if (kNoMask && in_img) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)b * 3 + c) * hw + pin];
+        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)sb * 3 + c) * hw + pin];
     }
     float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
     int hf = -1;
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     const bool any_covered = __ballot(in_img && hf >= 0) != 0;   // wave-uniform
     if (!any_covered) {
         if (kNoMask && in_img) {
-            const float* L = a.lights + b * 9;                   // (bands 0 and 6 only: the same lights whatever the band order)
+            const float* L = a.lights + sb * 9;                  // (bands 0 and 6 only: the same lights whatever the band order)
             const float coef = MM_SH_C0 * L[0] + (0.f - MM_SH_C6B) * L[6];
             float dc = 0.f;
 #pragma unroll
@@ -290,7 +293,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
             const int cy0 = min(max(s.y0, 0), a.Ht - 1), cy1 = min(max(s.y1, 0), a.Ht - 1);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* tex = a.textures + ((size_t)b * 3 + c) * a.Ht * a.Wt;
+                const float* tex = a.textures + ((size_t)sb * 3 + c) * a.Ht * a.Wt;
                 tq[c][0] = tex[(size_t)cy0 * a.Wt + cx0]; tq[c][1] = tex[(size_t)cy0 * a.Wt + cx1];
                 tq[c][2] = tex[(size_t)cy1 * a.Wt + cx0]; tq[c][3] = tex[(size_t)cy1 * a.Wt + cx1];
             }
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
         sh_bands(nx, ny, nz, bnd);
         float L[9];                                              // lights in sh_bands' order (see shade_store)
 #pragma unroll
-        for (int i = 0; i < 9; ++i) L[i] = a.lights[b * 9 + i];
+        for (int i = 0; i < 9; ++i) L[i] = a.lights[sb * 9 + i];
         if (a.options & MM_OPT_SH_ORDER_XYZ) { const float tmp = L[2]; L[2] = L[3]; L[3] = tmp; }
         float coef = 0.f;
 #pragma unroll
@@ -473,13 +476,18 @@ int launch_pixel_bwd(const BwdArgs& a, const MMRenderDesc* d, hipStream_t s) {
     ProfScope p(d->prof_events, MM_PROF_PIXEL_BWD, s);
     dim3 grid(a.blocks_per_image * d->B + a.plan_wgs * d->B);    // + the plan workgroups, in front
     const bool contour = a.gt != nullptr && a.contour > 0.f;
-    if (a.options & MM_INT_DEFERRED) {                           // deferred fusion (never with the contour term: check_render)
-        if (d->no_mask) hipLaunchKernelGGL((pixel_bwd_kernel<true, false, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, true>), grid, dim3(256), 0, s, a);
+    if (a.views > 1) {                                           // multi-view (never fused: mm_render_views_backward refuses it)
+        if (d->no_mask) hipLaunchKernelGGL((pixel_bwd_kernel<true, false, false, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, false, true>), grid, dim3(256), 0, s, a);
         return MM_OK;
     }
-    if (d->no_mask) { if (contour) hipLaunchKernelGGL((pixel_bwd_kernel<true, true, false>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((pixel_bwd_kernel<true, false, false>), grid, dim3(256), 0, s, a); }
-    else { if (contour) hipLaunchKernelGGL((pixel_bwd_kernel<false, true, false>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, false>), grid, dim3(256), 0, s, a); }
+    if (a.options & MM_INT_DEFERRED) {                           // deferred fusion (never with the contour term: check_render)
+        if (d->no_mask) hipLaunchKernelGGL((pixel_bwd_kernel<true, false, true, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, true, false>), grid, dim3(256), 0, s, a);
+        return MM_OK;
+    }
+    if (d->no_mask) { if (contour) hipLaunchKernelGGL((pixel_bwd_kernel<true, true, false, false>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((pixel_bwd_kernel<true, false, false, false>), grid, dim3(256), 0, s, a); }
+    else { if (contour) hipLaunchKernelGGL((pixel_bwd_kernel<false, true, false, false>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, false, false>), grid, dim3(256), 0, s, a); }
     return MM_OK;
 }
 

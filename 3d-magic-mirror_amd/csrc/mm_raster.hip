@@ -38,7 +38,9 @@ namespace mm {
 #endif
 // kQueue: the compacting walk (tile_walk) for screen bins larger than a tile; otherwise the per-batch walk (tile_walk_batch)
 // kContour: the fused loss carries recon_data's contour term (host: fused_gt && fused_contour > 0)
-template <bool kNoMask, bool kBlock, bool kQueue, bool kContour>
+// kViews: a multi-view call (mm_render_views_forward, RasterArgs::views > 1; never with the fused loss): the shade epilogue reads bg, lights and
+// textures from the image's sample.  The instantiations mm_render_forward launches are the kViews = false ones and hold none of that code.
+template <bool kNoMask, bool kBlock, bool kQueue, bool kContour, bool kViews>
 __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_eu(MM_RASTER_WPE, MM_RASTER_WPE))) void raster_fwd_kernel(RasterArgs a_) {   // kBlock: 5 waves per SIMD = 96 VGPRs, 5 x 32 KiB LDS per CU
 #ifndef __HIP_DEVICE_COMPILE__
     const RasterArgs& a = a_;
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
         if (j >= W1) {                                           // (interleaving the two kinds of workgroup evenly was measured: no gain at 512x512,
             if (j - W1 >= W2) return;                            //  slower at 128x128, where every walking workgroup is resident from the start)
             const int e0 = nne + (j - W1) * per + wv * 4, ne = min(4, 4 * a.blocks_per_image - e0);
-            if (ne > 0) shade_empty_tiles<kNoMask, kContour>(a, b, e0, ne, threadIdx.x & 63);
+            if (ne > 0) shade_empty_tiles<kNoMask, kContour, kViews>(a, b, e0, ne, threadIdx.x & 63);
             return;
         }
         rank = j;
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
         if (kQueue) tile_walk(a, t, &s_stage[wv], key, ss);
         else tile_walk_batch(a, t, &s_stage[wv], key, ss);
     }
-    shade_store<kNoMask, kContour>(a, t, key, ss);
+    shade_store<kNoMask, kContour, kViews>(a, t, key, ss);
     flush_taken_last(a, t, &s_stage[(kBlock && coop) ? 0 : wv]);
 }
 
@@ -172,6 +174,7 @@ RasterArgs make_raster_args(const MMRenderDesc* d, const Workspace& w) {
     a.nheavy = nullptr;
     a.block_sort = 0;
     a.feats = nullptr; a.D = 0; a.interp = nullptr; a.soft_out = nullptr; a.face_idx64 = nullptr; a.options = d->options;
+    a.views = 1;
     return a;
 }
 
@@ -190,8 +193,9 @@ const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nh
     return order;
 }
 
-int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s) {
+int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views) {
     RasterArgs a = make_raster_args(d, w);
+    a.views = views;
     a.order = launch_order(a, w.order, w.nheavy, w.bincount, d->B, d->prof_events, s);     // heavy-first launch order
     a.spread = walk_spread(a);
     a.nheavy = w.nheavy;
@@ -201,8 +205,9 @@ int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s) 
     // 8-pixel bins: the bin is the tile, nothing to compact -> the per-batch walk, no face flags (every face gets its sweep items)
     const bool queue = walk_queue_mode(a);
     if (!queue) a.fflag = nullptr;
-#define MM_LAUNCH_RASTER2(NM, BL, QU, CO) hipLaunchKernelGGL((raster_fwd_kernel<NM, BL, QU, CO>), grid, dim3(BL ? 256 : 64), 0, s, a)
-#define MM_LAUNCH_RASTER(NM, BL, QU) do { if (a.contour > 0.f) MM_LAUNCH_RASTER2(NM, BL, QU, true); else MM_LAUNCH_RASTER2(NM, BL, QU, false); } while (0)
+#define MM_LAUNCH_RASTER2(NM, BL, QU, CO, VI) hipLaunchKernelGGL((raster_fwd_kernel<NM, BL, QU, CO, VI>), grid, dim3(BL ? 256 : 64), 0, s, a)
+#define MM_LAUNCH_RASTER(NM, BL, QU) do { if (views > 1) MM_LAUNCH_RASTER2(NM, BL, QU, false, true); else if (a.contour > 0.f) MM_LAUNCH_RASTER2(NM, BL, QU, true, false); \
+                                          else MM_LAUNCH_RASTER2(NM, BL, QU, false, false); } while (0)
     if (block) {
         if (queue) { if (d->no_mask) MM_LAUNCH_RASTER(true, true, true); else MM_LAUNCH_RASTER(false, true, true); }
         else { if (d->no_mask) MM_LAUNCH_RASTER(true, true, false); else MM_LAUNCH_RASTER(false, true, false); }

@@ -39,6 +39,8 @@ struct RasterArgs {
     const float* feats; int D;              // (B,F,3,D) per-corner features
     float* interp; float* soft_out; long long* face_idx64;
     int options;                            // MM_OPT_* bits
+    int views;                              // multi-view calls (mm_render_views_*): images per sample -- textures, lights and bg hold B / views rows and image b
+                                            // reads row b / views (kViews instantiations only; 1 everywhere else)
 };
 
 #ifndef MM_PAIR_ROUND
@@ -396,9 +398,11 @@ __device__ inline float contour_term(float alpha, float gm, bool in_img, int lan
 //   trip 2  the twelve texels, from clamped (always valid) addresses, unconditionally; a corner outside contributes an exact zero
 // The arithmetic (expressions, order, roundings) is unchanged.
 // kContour: the fused loss carries recon_data's contour term (a.contour > 0; chosen by the host -- the reference's default is none, train.py:115)
-template <bool kNoMask, bool kContour>
+// kViews: a multi-view call -- the per-sample inputs (bg, lights, textures) are addressed by the image's SAMPLE, a wave-uniform division per tile
+template <bool kNoMask, bool kContour, bool kViews = false>
 __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsigned long long key, const SoftState& ss) {
     if (!t.in_img && !a.gt) return;
+    const int sb = kViews ? t.b / a.views : t.b;                 // the row of the per-sample inputs
     const int cpx = min(t.px, a.W - 1), cpy = min(t.py, a.H - 1);
     const size_t pix = ((size_t)t.b * a.H + cpy) * a.W + cpx;
     const size_t hw = (size_t)a.H * a.W, pin = (size_t)cpy * a.W + cpx;
@@ -409,7 +413,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     float bgv[3] = {0.f, 0.f, 0.f}, gtv[4] = {0.f, 0.f, 0.f, 0.f};
     if (kNoMask) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)t.b * 3 + c) * hw + pin];
+        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)sb * 3 + c) * hw + pin];
     }
     if (a.gt) {                                                  // (clamped pixel: a valid address in every lane)
 #pragma unroll
@@ -432,7 +436,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     float out[4];
     float L[9];                                                  // lights in the order of sh_bands (x, z, y): MM_OPT_SH_ORDER_XYZ pairs
 #pragma unroll                                                   // the user's lights 2 / 3 with the y / z bands instead
-    for (int i = 0; i < 9; ++i) L[i] = a.lights[t.b * 9 + i];
+    for (int i = 0; i < 9; ++i) L[i] = a.lights[sb * 9 + i];
     if (a.options & MM_OPT_SH_ORDER_XYZ) { const float tmp = L[2]; L[2] = L[3]; L[3] = tmp; }
     if (!any) {
         // No lane of the tile is covered.  The general path below then computes, per lane,
@@ -470,7 +474,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
         float tq[3][4];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float* tex = a.textures + ((size_t)t.b * 3 + c) * a.Ht * a.Wt;
+            const float* tex = a.textures + ((size_t)sb * 3 + c) * a.Ht * a.Wt;
             tq[c][0] = tex[(size_t)cy0 * a.Wt + cx0]; tq[c][1] = tex[(size_t)cy0 * a.Wt + cx1];
             tq[c][2] = tex[(size_t)cy1 * a.Wt + cx0]; tq[c][3] = tex[(size_t)cy1 * a.Wt + cx1];
         }
@@ -556,14 +560,15 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
 // tile of its own wave pays the wave's fixed costs (launch, two dependent trips to memory, the store drain) for ~40 instructions of
 // work.  Here the four tiles' loads are in flight together.  Per pixel exactly what shade_store's uncovered-tile path computes
 // (m = 0, n = 0, soft-mask state "nothing taken"); the four tiles' recon_data terms go to ltot as one exact integer add per sum.
-template <bool kNoMask, bool kContour>
+template <bool kNoMask, bool kContour, bool kViews = false>
 __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int ne, int lane) {
     const int nslot = 4 * a.blocks_per_image;
+    const int sb = kViews ? b / a.views : b;                     // the row of the per-sample inputs (lights, bg)
     const size_t hw = (size_t)a.H * a.W;
     unsigned sl[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) sl[q] = a.order[(size_t)b * nslot + min(e0 + q, nslot - 1)] & 0x7FFFu;
-    const float coef = MM_SH_C0 * a.lights[b * 9] + (0.f - MM_SH_C6B) * a.lights[b * 9 + 6];   // (bands 0 and 6: the same lights whatever the band order)
+    const float coef = MM_SH_C0 * a.lights[sb * 9] + (0.f - MM_SH_C6B) * a.lights[sb * 9 + 6];   // (bands 0 and 6: the same lights whatever the band order)
     bool in[4];
     size_t pin[4];
     float bgv[4][3], gtv[4][4];
@@ -575,7 +580,7 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
         in[q] = q < ne && px < a.W && py < a.H;
         pin[q] = (size_t)min(py, a.H - 1) * a.W + min(px, a.W - 1);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) bgv[q][c] = kNoMask ? a.bg[((size_t)b * 3 + c) * hw + pin[q]] : 0.f;
+        for (int c = 0; c < 3; ++c) bgv[q][c] = kNoMask ? a.bg[((size_t)sb * 3 + c) * hw + pin[q]] : 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) gtv[q][c] = a.gt ? a.gt[((size_t)b * 4 + c) * hw + pin[q]] : 0.f;
     }

@@ -1,4 +1,4 @@
-// mm_torch_ext.cpp -- the autograd nodes of the class API (DiffRender.render / render_geometry / recon_data / render_recon).
+// mm_torch_ext.cpp -- the autograd nodes of the class API (DiffRender.render / render_views / render_geometry / recon_data / render_recon).
 //
 // The C ABI of libmm_render.so stays the boundary; this file is PLUMBING above it, compiled with the host compiler only (no device
 // code, no HIP headers): one C++ call per autograd node allocates the outputs with ATen, fills the descriptor and enqueues the
@@ -396,6 +396,113 @@ class GeometryNode : public torch::autograd::Function<GeometryNode> {
     }
 };
 
+// DiffRender.render_views (MMRenderViewsDesc: B samples x N views in one pass over B*N images; the per-sample tensors are read from their single
+// copy, their gradients are the view-order sums).  The prototype is the MMRenderDesc of the B*N images; the cameras arrive as (B,N) / (B,N,2)
+// (an expanded (B,) input gets its gradient through autograd's own expand); outputs are (B,N,...).  No fused loss, no deferred fusion.
+typedef int (*views_fwd_t)(const MMRenderViewsDesc*, void*);
+typedef int (*views_bwd_t)(const MMRenderViewsDesc*, const MMRenderGrads*, void*);
+
+class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
+ public:
+    static tensor_list forward(AutogradContext* ctx, int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t views, int64_t ws_bytes,
+                               int64_t staging_bytes, at::Tensor vertices, at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths,
+                               at::Tensor elevations, at::Tensor distances, at::Tensor biases, bool want_imnormal) {
+        TORCH_CHECK(azimuths.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
+        const c10::Device dev = azimuths.device();
+        const DeviceGuard guard(dev);
+        MMRenderViewsDesc vd;
+        vd.render = proto_desc(proto); vd.views = (int32_t)views;
+        MMRenderDesc& d = vd.render;
+        const int64_t N = views, BN = d.B, H = d.H, W = d.W;
+        TORCH_CHECK(N >= 1 && BN % N == 0, "render_views: ", BN, " images are not a multiple of ", N, " views");
+        const int64_t B = BN / N;
+        ctx->saved_data["shape_a"] = azimuths.sizes().vec(); ctx->saved_data["shape_e"] = elevations.sizes().vec();
+        ctx->saved_data["shape_d"] = distances.sizes().vec(); ctx->saved_data["shape_b"] = biases.sizes().vec();
+        vertices = dense_f32(vertices, dev, "vertices"); textures = dense_f32(textures, dev, "textures"); lights = dense_f32(lights, dev, "lights");
+        azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
+        distances = dense_f32(distances, dev, "distances").reshape({-1}); biases = dense_f32(biases, dev, "biases").reshape({-1, 2});
+        at::Tensor bgt;
+        if (bg.has_value() && bg->defined()) bgt = dense_f32(*bg, dev, "bg");
+        TORCH_CHECK(azimuths.size(0) == BN && elevations.size(0) == BN && distances.size(0) == BN && biases.size(0) == BN,
+                    "render_views: the cameras must hold B*N = ", BN, " values each (biases B*N pairs)");
+        TORCH_CHECK(vertices.dim() == 3 && vertices.size(0) == B && vertices.size(1) == d.V && vertices.size(2) == 3, "vertices must be (", B, ",", d.V, ",3), got ", vertices.sizes());
+        TORCH_CHECK(textures.dim() == 4 && textures.size(0) == B && textures.size(1) == 3 && textures.size(2) == d.Ht && textures.size(3) == d.Wt,
+                    "textures must be (", B, ",3,", d.Ht, ",", d.Wt, "), got ", textures.sizes());
+        TORCH_CHECK(lights.dim() == 2 && lights.size(0) == B && lights.size(1) == 9, "lights must be (", B, ",9), got ", lights.sizes());
+        if (d.no_mask) TORCH_CHECK(bgt.defined() && bgt.dim() == 4 && bgt.size(0) == B && bgt.size(1) == 3 && bgt.size(2) == H && bgt.size(3) == W,
+                                   "bg must be (", B, ",3,", H, ",", W, ")");
+        auto opts = vertices.options();
+        at::Tensor rgba = at::empty({B, N, H, W, 4}, opts), fn = at::empty({B, N, (int64_t)d.F, 3}, opts);
+        at::Tensor face_idx = at::empty({B, N, H, W}, opts.dtype(at::kInt));
+        at::Tensor imn = want_imnormal ? at::empty({B, N, H, W, 3}, opts) : at::empty({0}, opts);
+        at::Tensor ws = at::empty({ws_bytes}, opts.dtype(at::kByte));
+        d.vertices = fptr(vertices); d.textures = fptr(textures); d.lights = fptr(lights); d.bg = d.no_mask ? fptr(bgt) : nullptr;
+        d.azimuths = fptr(azimuths); d.elevations = fptr(elevations); d.distances = fptr(distances); d.biases = fptr(biases);
+        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
+        d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
+        check(((views_fwd_t)f_fwd)(&vd, (void*)current_stream(dev)), "mm_render_views_forward");
+        ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto; ctx->saved_data["views"] = views;
+        ctx->saved_data["staging_bytes"] = staging_bytes;            // the head of the workspace (the per-image gradients' staging): mm_render_status skips it
+        // the UN-replicated inputs, the forward products the backward re-reads, and the workspace (alive until this node dies)
+        ctx->save_for_backward({vertices, textures, lights, bgt, azimuths, elevations, distances, biases, face_idx, fn, ws});
+        ctx->mark_non_differentiable({face_idx, imn});
+        ctx->set_materialize_grads(false);
+        return {rgba, fn, imn, face_idx};
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list g) {
+        const auto sv = ctx->get_saved_variables();
+        const c10::Device dev = sv[4].device();
+        const DeviceGuard guard(dev);
+        MMRenderViewsDesc vd;
+        vd.render = proto_desc(ctx->saved_data["proto"].toStringRef()); vd.views = (int32_t)ctx->saved_data["views"].toInt();
+        MMRenderDesc& d = vd.render;
+        const int64_t N = vd.views, BN = d.B, B = BN / N, H = d.H, W = d.W;
+        at::Tensor fn = sv[9], ws = sv[10];
+        d.vertices = fptr(sv[0]); d.textures = fptr(sv[1]); d.lights = fptr(sv[2]); d.bg = d.no_mask ? fptr(sv[3]) : nullptr;
+        d.azimuths = fptr(sv[4]); d.elevations = fptr(sv[5]); d.distances = fptr(sv[6]); d.biases = fptr(sv[7]);
+        d.face_idx = sv[8].data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = nullptr; d.rgba = nullptr;
+        d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
+        at::Tensor grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({B, N, H, W, 4}, sv[0].options());
+        at::Tensor gfn;
+        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
+        at::Tensor gv = at::empty_like(sv[0]), gt_ = at::empty_like(sv[1]), gl = at::empty_like(sv[2]), gbg;
+        if (d.no_mask) gbg = at::empty_like(sv[3]);
+        at::Tensor ga = at::empty_like(sv[4]), ge = at::empty_like(sv[5]), gd = at::empty_like(sv[6]), gb = at::empty_like(sv[7]);
+        MMRenderGrads gr;
+        gr.grad_rgba = fptr(grgba); gr.grad_face_normals = fptr(gfn); gr.grad_vertices = mptr(gv); gr.grad_textures = mptr(gt_);
+        gr.grad_lights = mptr(gl); gr.grad_bg = mptr(gbg); gr.grad_azimuths = mptr(ga); gr.grad_elevations = mptr(ge); gr.grad_distances = mptr(gd);
+        gr.grad_biases = mptr(gb);
+        const int64_t stream = current_stream(dev);
+        check(((views_bwd_t)ctx->saved_data["f_bwd"].toInt())(&vd, &gr, (void*)stream), "mm_render_views_backward");
+        if (const int64_t f_status = ctx->saved_data["f_status"].toInt()) {      // DiffRender.check_texture_records (synchronises): per IMAGE, as in render
+            std::vector<int32_t> dropped((size_t)BN);
+            const size_t head = (size_t)ctx->saved_data["staging_bytes"].toInt();
+            MMRenderDesc rd = d;                                     // the render workspace of the B*N images inside the multi-view workspace
+            rd.workspace = (char*)d.workspace + head; rd.workspace_bytes = d.workspace_bytes - head;
+            const int st = ((render_status_t)f_status)(&rd, (void*)stream, dropped.data());
+            std::string list;
+            bool any = false;
+            for (int32_t n : dropped) { list += (list.empty() ? "" : ", ") + std::to_string(n); any = any || n != 0; }
+            TORCH_CHECK(!(st == MM_ERR_WORKSPACE && any), "mm_render_views_backward: the texture-record pool overflowed (records dropped per image: [", list,
+                        "]); the texture gradients of those samples are NaN. Raise DiffRender.extra_texture_records_per_pixel.");
+            check(st, "mm_render_status");
+        }
+        // one entry per forward argument: seven non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, want_imnormal
+        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gv, gt_, gl, gbg,
+                ga.reshape(ctx->saved_data["shape_a"].toIntVector()), ge.reshape(ctx->saved_data["shape_e"].toIntVector()),
+                gd.reshape(ctx->saved_data["shape_d"].toIntVector()), gb.reshape(ctx->saved_data["shape_b"].toIntVector()), at::Tensor()};
+    }
+};
+
+tensor_list render_views_node(int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t views, int64_t ws_bytes, int64_t staging_bytes,
+                              at::Tensor vertices,
+                              at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations,
+                              at::Tensor distances, at::Tensor biases, bool want_imnormal) {
+    return RenderViewsNode::apply(f_fwd, f_bwd, f_status, proto, views, ws_bytes, staging_bytes, vertices, textures, lights, bg, azimuths, elevations, distances, biases,
+                                  want_imnormal);
+}
+
 at::Tensor geometry_node(int64_t f_fwd, int64_t f_bwd, std::string proto, int64_t ws_bytes, at::Tensor vertices, at::Tensor azimuths, at::Tensor elevations,
                          at::Tensor distances, at::Tensor biases) {
     return GeometryNode::apply(f_fwd, f_bwd, proto, ws_bytes, vertices, azimuths, elevations, distances, biases);
@@ -470,6 +577,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("render", &render_node);
     m.def("recon_data", &recon_node);
     m.def("render_geometry", &geometry_node);
+    m.def("render_views", &render_views_node);
     m.def("desc_bytes", []() { return (int64_t)sizeof(MMRenderDesc); });
     m.def("deferrable", [](at::Tensor pred) { return deferrable_render(pred) != nullptr; });   // tests / diagnostics: would recon_data(pred, .) defer?
 }

@@ -7,7 +7,21 @@
 //   that mask: per block of 8x8 bins one wave transpose of the lanes' coverage bits (no separate binning pass).
 // Backward (reverse of the above): one workgroup per image walks the static vertex->corner CSR, so per-vertex
 //   gradients are gathered in a fixed order (no atomics), reduces dT in LDS and finishes with the camera chain.
+//
+// This file is compiled TWICE: on its own (the kernels mm_render_forward / mm_render_backward launch), and once more through
+// mm_vertex_views.hip with MM_VERTEX_VIEWS defined -- the same kernels under the names *_views, in which image b reads the vertices of
+// SAMPLE b / views (multi-view calls, mm_render_views_*: `vertices` holds B / views rows).  A second compilation instead of a template
+// parameter: the first one then sees unchanged tokens, and its kernels keep their symbols and their machine code to the instruction
+// (tools/kernel_disasm_diff.py).
 #include "mm_device.h"
+
+#ifdef MM_VERTEX_VIEWS
+#define MM_VX(name) name##_views
+#define MM_VX_SAMPLE(b) ((b) / a.views)
+#else
+#define MM_VX(name) name
+#define MM_VX_SAMPLE(b) (b)
+#endif
 
 namespace mm {
 
@@ -22,6 +36,7 @@ struct VertexFwdArgs {
     float4* geo;
     float* face_normals;
     int* tcnt; int ntcnt;    // texture-record counters of the backward: cleared here for the first backward after this forward
+    int views;               // images per sample (read by the *_views kernels only; it sits in what was padding: no other member moves)
     long long* ltot; int nltot;   // fused-loss sums of the raster waves: cleared here
     int bin_shift, nbx, nby, words;
     uint64_t* mask;          // (B,nbins,words) screen-bin candidate mask, written here (nullptr: not wanted)
@@ -73,7 +88,7 @@ __device__ inline void face_record(const VertexFwdArgs& a, int b, int f, const f
     reinterpret_cast<int2*>(a.fflag)[o] = make_int2(0, 0);
 }
 
-__global__ __launch_bounds__(256) void vertex_fwd_kernel(VertexFwdArgs a) {
+__global__ __launch_bounds__(256) void MM_VX(vertex_fwd_kernel)(VertexFwdArgs a) {
     __shared__ float s_trig[4];
     __shared__ Camera s_cam;
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -85,7 +100,7 @@ __global__ __launch_bounds__(256) void vertex_fwd_kernel(VertexFwdArgs a) {
     float pa[3] = {0.f, 0.f, 0.f}, pb[3] = {0.f, 0.f, 0.f}, pc[3] = {0.f, 0.f, 0.f};
     if (f < a.F) {
         const int i0 = a.faces[f * 3 + 0], i1 = a.faces[f * 3 + 1], i2 = a.faces[f * 3 + 2];
-        const float* vb = a.vertices + (size_t)b * a.V * 3;
+        const float* vb = a.vertices + (size_t)MM_VX_SAMPLE(b) * a.V * 3;
 #pragma unroll
         for (int j = 0; j < 3; ++j) { pa[j] = vb[(size_t)i0 * 3 + j]; pb[j] = vb[(size_t)i1 * 3 + j]; pc[j] = vb[(size_t)i2 * 3 + j]; }
     }
@@ -110,6 +125,7 @@ struct VertexBwdArgs {
     float proj0, proj1, proj2;
     const int4* vc_table;   // (V,vc_stride) {face*3 + corner, the face's three vertex ids}, padded with -1
     int vc_stride;
+    int views;              // images per sample (read by the *_views kernels only; in what was padding); the gradients stay per image
     const int32_t* faces;   // (F,3) vertex ids (the per-image form walks the faces)
     const float* vertices;
     const float *azim, *elev, *dist, *bias;
@@ -137,7 +153,7 @@ struct VertexBwdArgs {
 // CSR (no atomics); dT is reduced per workgroup and added to the image's accumulator; the LAST
 // workgroup of an image to arrive (agent-scope release / ticket / acquire, cdna_hip_programming.md G16) runs the
 // camera chain.
-__global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
+__global__ __launch_bounds__(256) void MM_VX(vertex_bwd_kernel)(VertexBwdArgs a) {
     __shared__ Camera s_cam;
     __shared__ float s_red[4][12];
     __shared__ float s_part[21][12];
@@ -147,7 +163,7 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
     float T[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) T[i] = a.T[b * 12 + i];
-    const float* vb = a.vertices + (size_t)b * a.V * 3;
+    const float* vb = a.vertices + (size_t)MM_VX_SAMPLE(b) * a.V * 3;
     float acc[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) acc[i] = 0.f;
@@ -353,13 +369,13 @@ __global__ __launch_bounds__(256) void vertex_bwd_kernel(VertexBwdArgs a) {
 // {vertices, item sums} -> LDS -> outputs.  Bitwise reproducible (fixed orders throughout).
 // ---------------------------------------------------------------------------------------------------------------------
 // (MM_VIMG_BWD_MAX_FACES = 1700, mm_device.h)   36 bytes of LDS per face: 61 KB of dynamic LDS at most, below the 64 KB a launch gets without opting in
-__global__ __launch_bounds__(1024) void vertex_image_bwd_kernel(VertexBwdArgs a) {
+__global__ __launch_bounds__(1024) void MM_VX(vertex_image_bwd_kernel)(VertexBwdArgs a) {
     extern __shared__ float s_d[];                                // (F, 3 corners, 3)
     __shared__ Camera s_cam;
     __shared__ float s_red[16][12];
     const int b = blockIdx.x, tid = threadIdx.x;
     for (int i = b * 1024 + tid; i < a.ntcnt; i += gridDim.x * 1024) a.tcnt[i] = 0;
-    const float* vb = a.vertices + (size_t)b * a.V * 3;
+    const float* vb = a.vertices + (size_t)MM_VX_SAMPLE(b) * a.V * 3;
     // ---- trip 1: what depends on nothing (T, the camera record, this thread's faces' ids and chunk maps, its vertex and its corner list)
     float T[12];
 #pragma unroll
@@ -526,8 +542,16 @@ __global__ __launch_bounds__(1024) void vertex_image_bwd_kernel(VertexBwdArgs a)
     }
 }
 
-int launch_vertex_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s) {
+// views: images per sample; > 1 goes to the second compilation's launcher (and is what its kernels divide by)
+int launch_vertex_fwd_views(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views);
+int launch_vertex_bwd_views(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views);
+
+int MM_VX(launch_vertex_fwd)(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views) {
+#ifndef MM_VERTEX_VIEWS
+    if (views > 1) return launch_vertex_fwd_views(d, w, s, views);
+#endif
     VertexFwdArgs a;
+    a.views = views;
     a.B = d->B; a.V = d->V; a.F = d->F; a.H = d->H; a.W = d->W;
     a.proj0 = d->proj[0]; a.proj1 = d->proj[1]; a.proj2 = d->proj[2]; a.mult = d->multiplier; a.infl = d->boxlen * d->multiplier;
     a.faces = d->faces; a.vertices = d->vertices;
@@ -540,12 +564,16 @@ int launch_vertex_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s) 
     a.ticket = w.ticket;
     dim3 grid((d->F + 255) / 256, d->B);
     { ProfScope ps(d->prof_events, MM_PROF_VERTEX_FWD, s);
-      hipLaunchKernelGGL(vertex_fwd_kernel, grid, dim3(256), 0, s, a); }
+      hipLaunchKernelGGL(MM_VX(vertex_fwd_kernel), grid, dim3(256), 0, s, a); }
     return launch_ok("vertex_fwd");
 }
 
-int launch_vertex_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s) {
+int MM_VX(launch_vertex_bwd)(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views) {
+#ifndef MM_VERTEX_VIEWS
+    if (views > 1) return launch_vertex_bwd_views(d, g, w, s, views);
+#endif
     VertexBwdArgs a;
+    a.views = views;
     a.B = d->B; a.V = d->V; a.F = d->F;
     a.proj0 = d->proj[0]; a.proj1 = d->proj[1]; a.proj2 = d->proj[2];
     a.vc_table = (const int4*)d->vc_table; a.vc_stride = d->vc_stride; a.vertices = d->vertices;
@@ -559,11 +587,11 @@ int launch_vertex_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Works
     a.faces = d->faces; a.geometry_only = d->geometry_only;
     if (vertex_bwd_per_image(d->B, d->F, d->vc_stride)) {
         ProfScope ps(d->prof_events, MM_PROF_VERTEX_BWD, s);
-        hipLaunchKernelGGL(vertex_image_bwd_kernel, dim3(d->B), dim3(1024), (size_t)d->F * 9 * sizeof(float), s, a);
+        hipLaunchKernelGGL(MM_VX(vertex_image_bwd_kernel), dim3(d->B), dim3(1024), (size_t)d->F * 9 * sizeof(float), s, a);
         return launch_ok("vertex_image_bwd");
     }
     { ProfScope ps(d->prof_events, MM_PROF_VERTEX_BWD, s);
-      hipLaunchKernelGGL(vertex_bwd_kernel, dim3((d->V + 31) / 32, d->B), dim3(256), 0, s, a); }
+      hipLaunchKernelGGL(MM_VX(vertex_bwd_kernel), dim3((d->V + 31) / 32, d->B), dim3(256), 0, s, a); }
     return launch_ok("vertex_bwd");
 }
 

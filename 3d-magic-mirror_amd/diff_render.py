@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's ``DiffRender`` (/root/reference/networks.py:164-491) over the gfx950 C ABI.
 
 Same constructor, attributes, method names, argument meaning and return values as the reference class, so a
-``trainer.py``-style loop can switch with ``from mm_amd import DiffRender``.  ``render``, ``render_geometry``, ``render_recon``
+``trainer.py``-style loop can switch with ``from mm_amd import DiffRender``.  ``render``, ``render_views``, ``render_geometry``, ``render_recon``
 and ``recon_data`` run the hand-written HIP kernels of ``lib/libmm_render.so`` through the C++ autograd nodes of
 ``lib/mm_torch_ext.so`` (csrc/mm_torch_ext.cpp); there is no CPU, eager-torch or Python-node fallback for them.  The mesh
 regularisers (``recon_flip``, ``calc_reg_*``) run as one HIP launch per direction (``mesh_reg.py``), and so
@@ -210,6 +210,90 @@ class DiffRender(object):
         attributes['imnormal'] = imn if self.emit_imnormal else None
         self.last_face_idx = face_idx                   # kaolin returns it from dibr_rasterization; the reference drops it
         return rgbs, attributes
+
+    # ---- the same samples under several cameras (trainer.py:280-289,347 Ae / Ae90; :710-723 evaluation; :619-671 turntables) ----
+    def _view_cameras(self, attributes):
+        """(B, N, the four camera attributes as (B,N) / (B,N,2)) of a render_views call, every shape checked: B from `vertices`; a camera
+        attribute is (B,N) (biases (B,N,2)) or, broadcast over the views, (B,) (biases (B,2)); at least one carries N and all that do agree."""
+        for k in ('vertices', 'textures', 'lights', 'azimuths', 'elevations', 'distances', 'biases'):
+            if not torch.is_tensor(attributes.get(k)):
+                raise TypeError("render_views needs attributes[%r] as a tensor" % k)
+        vertices, textures, lights = attributes['vertices'], attributes['textures'], attributes['lights']
+        if vertices.dim() != 3 or tuple(vertices.shape[1:]) != (self.num_vertices, 3):
+            raise ValueError("vertices must be (B,%d,3), got %s" % (self.num_vertices, tuple(vertices.shape)))
+        B = int(vertices.shape[0])
+        if textures.dim() != 4 or textures.shape[0] != B or textures.shape[1] != 3:
+            raise ValueError("textures must be (%d,3,Ht,Wt) -- one per SAMPLE, not per view -- got %s" % (B, tuple(textures.shape)))
+        if tuple(lights.shape) != (B, 9):
+            raise ValueError("lights must be (%d,9) -- one row per SAMPLE, not per view -- got %s" % (B, tuple(lights.shape)))
+        shapes = {k: tuple(attributes[k].shape) for k in ('azimuths', 'elevations', 'distances', 'biases')}
+        views = {}
+        for k, shp in shapes.items():
+            tail = (2,) if k == 'biases' else ()
+            if shp == (B,) + tail:
+                continue                                          # broadcast over the views
+            if len(shp) == 2 + len(tail) and shp[0] == B and shp[1] >= 1 and shp[2:] == tail:
+                views[k] = shp[1]
+            else:
+                raise ValueError("%s must be (%d,N%s) or, the same for every view, (%d%s); got %s (camera shapes: %s)"
+                                 % (k, B, ",2" if tail else "", B, ",2" if tail else ",", shp, shapes))
+        if not views:
+            raise ValueError("render_views: no camera attribute carries a view axis -- give at least one of azimuths / elevations / distances as "
+                             "(%d,N) or biases as (%d,N,2) (got %s); for one view per sample call render" % (B, B, shapes))
+        if len(set(views.values())) != 1:
+            raise ValueError("render_views: the camera attributes disagree on the number of views: %s" % views)
+        n = next(iter(views.values()))
+        cams = []
+        for k in ('azimuths', 'elevations', 'distances', 'biases'):
+            t = attributes[k]
+            cams.append(t if k in views else t.unsqueeze(1).expand((B, n) + tuple(t.shape[1:])))
+        return B, n, cams
+
+    def render_views(self, no_mask=False, **attributes):
+        """``render`` of B samples under N cameras each, as ONE pass of the kernels over B*N images in which every sample's vertices, textures,
+        lights and bg are read from their single (B,...) copy -- nothing is replicated per view on the way in, at any layer (csrc/mm_torch_ext.cpp:
+        RenderViewsNode; include/mm_render.h: MMRenderViewsDesc).  Camera attributes are (B,N) (biases (B,N,2)); one given as (B,) / (B,2) holds for
+        every view (a turntable passes azimuths (B,36) and leaves the rest alone) and receives its gradient through autograd's expand.
+        Returns (rgbs (B,N,4,H,W) -- the permuted view of (B,N,H,W,4) memory, like render's --, attributes) with attributes['face_normals']
+        (B,N,F,3), attributes['imnormal'] (B,N,H,W,3) or None, and self.last_face_idx (B,N,H,W).  Image (b,n) is bit-identical to image b*N + n of
+        ``render`` on the per-sample tensors replicated with repeat_interleave(N, 0); the gradient of a per-sample tensor is the fp32 sum of its
+        views' gradients in ascending view order (plain adds: bitwise reproducible)."""
+        no_mask = bool(no_mask)
+        if no_mask and attributes.get('bg') is None:
+            raise TypeError("render_views(no_mask=True) needs attributes['bg'] (B,3,H,W)")
+        B, n, (azimuths, elevations, distances, biases) = self._view_cameras(attributes)
+        vertices, textures, lights = attributes['vertices'], attributes['textures'], attributes['lights']
+        bg = attributes['bg'] if no_mask else None
+        if bg is not None and tuple(bg.shape) != (B, 3, self.render_height, self.image_size):
+            raise ValueError("bg must be (%d,3,%d,%d) -- one per SAMPLE, not per view -- got %s" % (B, self.render_height, self.image_size, tuple(bg.shape)))
+        self._raise_if_records_were_dropped()
+        N.require_device(azimuths, elevations, distances, biases, vertices, textures, lights, bg)
+        st = self._static(azimuths.device)
+        Ht, Wt = int(textures.shape[2]), int(textures.shape[3])
+        proto, nbytes = self._proto(st, B * n, no_mask, Ht, Wt)
+        staging = self._views_staging_bytes(proto, n)            # the workspace's head; the B*N images' render workspace (render's own size) follows
+        rgba, fn, imn, face_idx = N.torch_ext().render_views(
+            N.fn_addr("mm_render_views_forward"), N.fn_addr("mm_render_views_backward"),
+            N.fn_addr("mm_render_status") if self.check_texture_records else 0, proto, n, nbytes + staging, staging,
+            vertices, textures, lights, bg, azimuths, elevations, distances, biases, bool(self.emit_imnormal))
+        attributes['face_normals'] = fn
+        attributes['imnormal'] = imn if self.emit_imnormal else None
+        self.last_face_idx = face_idx
+        return rgba.permute(0, 1, 4, 2, 3), attributes
+
+    def _views_staging_bytes(self, proto, views):
+        """What a multi-view workspace holds beyond the render workspace of its B*N images: the staging areas of the per-image gradients."""
+        key = ("views", proto, views)
+        hit = self._desc_cache.get(key)
+        if hit is None:
+            vd = N.MMRenderViewsDesc()
+            ctypes.memmove(ctypes.byref(vd), proto, len(proto))
+            vd.views = views
+            hit = int(N.lib().mm_render_views_query_workspace(ctypes.byref(vd))) - int(N.lib().mm_query_workspace(ctypes.byref(vd.render)))
+            if hit < 0:
+                raise RuntimeError("mm_render_views_query_workspace refused the shape (%d images, %d views)" % (vd.render.B, views))
+            self._desc_cache[key] = hit
+        return hit
 
     def render_many(self, attribute_sets, no_mask=False):
         """Several INDEPENDENT ``render`` calls as one: the attribute sets (same shapes) are concatenated along the batch and rendered by ONE pass

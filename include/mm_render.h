@@ -189,6 +189,37 @@ int mm_render_fused_loss(const MMRenderDesc* desc, mm_stream_t stream);
 int mm_debug_workspace_layout(const MMRenderDesc* desc, size_t* out8);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Multi-view render: B samples x N views in ONE pass of the render kernels over B*N images, every sample's mesh, texture, lights and
+ * background read from the sample's single copy.  The reference renders the same sample under several cameras wherever it deep_copies an
+ * attribute set and edits the camera (trainer.py:280-289,347 Ae / Ae90; :710-723 the five evaluation renders; :619-671 the turntables); with
+ * mm_render_forward that costs a replicated copy of every per-sample tensor per view.
+ *   render   an MMRenderDesc of the B*N IMAGES (render.B = B*N; image i = b*N + n, sample-major): the four camera inputs and every output are
+ *            per image, exactly as in mm_render_forward -- but `vertices`, `textures`, `lights` and `bg` address (B,...) tensors, one row per
+ *            SAMPLE, and image i reads row i / views.  fused_gt, fused_totals and geometry_only must be unset (MM_ERR_UNSUPPORTED).
+ *   views    N >= 1; render.B must be a multiple of it (MM_ERR_BAD_SHAPE otherwise).
+ * Forward: every image is bit-identical to image i of mm_render_forward on the (B*N,...) tensors replicated with repeat_interleave(N): the same
+ * kernels in the shapes a batch of B*N images takes, the same workspace layout, the same texture-record pool, status word and NaN rule per image.
+ * Backward: MMRenderGrads with grad_rgba, grad_face_normals and the four camera gradients per IMAGE (bit-identical to mm_render_backward's) and
+ * grad_vertices, grad_textures, grad_lights, grad_bg shaped (B,...): for each the kernels write the per-image gradients mm_render_backward would
+ * have written into a staging area of the workspace, and one more launch adds a sample's views up in ascending view order,
+ * ((g0 + g1) + g2) + ..., plain fp32 adds (no fma, no atomics): bitwise reproducible.  With views == 1 nothing is staged and nothing more is
+ * launched: the two calls are mm_render_forward / mm_render_backward.
+ * Workspace: mm_render_views_query_workspace = mm_query_workspace(&render) for views == 1, else that plus the four staging areas (each
+ * B*N rows, rounded up to 256 bytes; bg's too when no_mask is 0, so that the size depends on the shape alone).  Both calls take the SAME
+ * workspace and workspace_bytes; the staging areas come first, the render workspace of the B*N images takes all the rest (what exceeds the
+ * query enlarges the record arrays as in mm_render_forward).  mm_render_status is asked with a copy of `render` whose workspace is that
+ * rest: workspace + (query - mm_query_workspace(&render)), workspace_bytes less the same.  B <= 65535 samples.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct MMRenderViewsDesc {
+    MMRenderDesc render;
+    int32_t views;
+} MMRenderViewsDesc;
+
+size_t mm_render_views_query_workspace(const MMRenderViewsDesc* desc);
+int mm_render_views_forward(const MMRenderViewsDesc* desc, mm_stream_t stream);
+int mm_render_views_backward(const MMRenderViewsDesc* desc, const MMRenderGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Reconstruction loss: replaces DiffRender.recon_data (networks.py:364-390) incl. kaolin mask_iou (:377) and the
  * optional contour term (:379-387):  loss = image_weight * mean|pred*gm+(1-gm) - (gt*gm+(1-gm))| + (1 - mean_b IoU_b)
  *                                           [+ contour * mean((c(pred_mask) - c(gt_mask))^2)].
@@ -655,7 +686,7 @@ const char* mm_last_error_detail(void);
  * 5 MMAttLossDesc, 6 MMAttLossGrads, 7 MMTexFlowDesc, 8 MMTexFlowGrads, 9 MMPrepareDesc, 10 MMPrepareGrads, 11 MMDibrDesc,
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
- * 25 MMInterpGrads. */
+ * 25 MMInterpGrads, 26 MMRenderViewsDesc. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -664,7 +695,8 @@ size_t mm_struct_size(int which);
  * refuses B > 65535 as mm_chamfer_nearest does; 9: MMShapeFeatDesc / Grads, MMCameraFeatDesc / Grads, mm_shape_features_* and
  * mm_camera_features_*, struct ids 20-23; still 9: MMInterpDesc / Grads, mm_interp_query_workspace, mm_collapse_resample and
  * mm_attribute_mix_*, struct ids 24 and 25, which only add -- no existing struct, field or meaning changes; a binding detects them by
- * mm_struct_size(24) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_struct_size(24) != 0; still 9: MMRenderViewsDesc and mm_render_views_*, struct id 26, additions again -- MMRenderDesc and
+ * MMRenderGrads keep their layout and meaning).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
