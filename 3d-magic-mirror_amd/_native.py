@@ -174,6 +174,16 @@ class MMInterpGrads(ctypes.Structure):
                 ("grad_lights", c_p)]
 
 
+class MMCriticDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("H", c_i), ("W", c_i), ("unmask", c_i), ("Xa", c_p), ("Xer90", c_p), ("Xir", c_p),
+                ("Xa_nhwc", c_i), ("Xer90_nhwc", c_i), ("Xir_nhwc", c_i), ("alpha_er90", c_p), ("alpha_ir", c_p),
+                ("out_batch", c_p), ("out_gp_er90", c_p), ("out_gp_ir", c_p)]
+
+
+class MMCriticGrads(ctypes.Structure):
+    _fields_ = [("g_batch", c_p), ("grad_er90", c_p), ("grad_ir", c_p), ("grad_er90_nhwc", c_i), ("grad_ir_nhwc", c_i)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -195,7 +205,8 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_ssim_backward", "mm_shape_features_query_workspace", "mm_shape_features_forward", "mm_shape_features_backward",
            "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward",
            "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
-           "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward", "mm_struct_size",
+           "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward",
+           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -289,6 +300,8 @@ def lib():
     L.mm_render_views_query_workspace.argtypes = [P(MMRenderViewsDesc)]
     L.mm_render_views_forward.argtypes = [P(MMRenderViewsDesc), c_p]
     L.mm_render_views_backward.argtypes = [P(MMRenderViewsDesc), P(MMRenderGrads), c_p]
+    L.mm_critic_inputs_forward.argtypes = [P(MMCriticDesc), c_p]
+    L.mm_critic_inputs_backward.argtypes = [P(MMCriticDesc), P(MMCriticGrads), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -303,7 +316,7 @@ def lib():
     mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
                MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
-               MMInterpDesc, MMInterpGrads, MMRenderViewsDesc)
+               MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads)
     for i, cls in enumerate(mirrors):
         if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

@@ -40,6 +40,9 @@ size_t interp_workspace_bytes(int B);
 int launch_mix_fwd(const MMInterpDesc*, hipStream_t);
 int launch_mix_bwd(const MMInterpDesc*, const MMInterpGrads*, hipStream_t);
 int launch_collapse_resample(int B, int V, const float* dv, int* idx_a, int* idx_b, const float* u, float thr, int* n_bad, hipStream_t);
+int critic_chunks_per_image(const MMCriticDesc*);
+int launch_critic_fwd(const MMCriticDesc*, hipStream_t);
+int launch_critic_bwd(const MMCriticDesc*, const MMCriticGrads*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -529,6 +532,34 @@ int mm_collapse_resample(int32_t B, int32_t V, const float* delta_vertices, int3
     return mm::launch_collapse_resample(B, V, delta_vertices, idx_a, idx_b, uniforms, threshold, n_bad, (hipStream_t)stream);
 }
 
+// sizes and modes of the critic inputs; the launches count chunks of one image in an int32 (two fakes in the backward)
+static int critic_shape(const MMCriticDesc* d) {
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->unmask < 0 || d->unmask > 2) return MM_ERR_BAD_SHAPE;
+    if (!d->alpha_er90 != !d->alpha_ir) return MM_ERR_BAD_SHAPE;  // one interpolate without the other
+    if (2LL * d->B * mm::critic_chunks_per_image(d) > 0x7fffffff) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+int mm_critic_inputs_forward(const MMCriticDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    const int st = critic_shape(d);
+    if (st != MM_OK) return st;
+    if (!d->Xa || !d->Xer90 || !d->Xir || !d->out_batch || (d->alpha_er90 && (!d->out_gp_er90 || !d->out_gp_ir))) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_critic_fwd(d, (hipStream_t)stream);
+}
+
+int mm_critic_inputs_backward(const MMCriticDesc* d, const MMCriticGrads* g, mm_stream_t stream) {
+    if (!d || !g) return MM_ERR_NULL_POINTER;
+    const int st = critic_shape(d);
+    if (st != MM_OK) return st;
+    if (!g->grad_er90 && !g->grad_ir) return MM_OK;            // nothing to differentiate: nothing is launched
+    if (!g->g_batch) return MM_ERR_NULL_POINTER;
+    if (d->unmask == 0 && ((g->grad_er90 && !d->Xer90) || (g->grad_ir && !d->Xir))) return MM_ERR_NULL_POINTER;   // d m reads the fake
+    mm::clear_stale_error();
+    return mm::launch_critic_bwd(d, g, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -599,6 +630,7 @@ size_t mm_struct_size(int which) {
         case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);    case 20: return sizeof(MMShapeFeatDesc);
         case 21: return sizeof(MMShapeFeatGrads); case 22: return sizeof(MMCameraFeatDesc); case 23: return sizeof(MMCameraFeatGrads);
         case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);  case 26: return sizeof(MMRenderViewsDesc);
+        case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);
         default: return 0;
     }
 }

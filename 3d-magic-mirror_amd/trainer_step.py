@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .critic_inputs import critic_inputs
 from .diff_render import DiffRender, deep_copy
 from .texture_flow import sample_texture
 
@@ -133,15 +134,18 @@ def default_opt():
 
 
 class TrainerStep:
-    def __init__(self, template, image_size, batch, device, ratio=1, opt=None, seed=0, lean=False, many=False):
+    def __init__(self, template, image_size, batch, device, ratio=1, opt=None, seed=0, lean=False, many=False, fused_critic=False):
         """lean: the fourth render (trainer.py:367, whose image is discarded) as DiffRender.render_geometry -- same losses, same gradients.
         many (with lean): the three renders whose attributes exist up front (trainer.py:276,345,347) as ONE DiffRender.render_many call of 3B
         images.  Pays where a batch of 48 does not fill the chip (128x128); at 256x256 one pass over 144 images takes as long as three over 48
-        and the concatenations cost more than the launches saved (profiles/r04_render_path.md)."""
+        and the concatenations cost more than the launches saved (profiles/r04_render_path.md).
+        fused_critic: the stand-in critic's batch from critic_inputs (one launch each way, the renders' NHWC memory read as it is) instead of
+        torch.cat over two channel slices -- same values, same gradients."""
         self.opt = opt or default_opt()
         self.dev, self.B = device, batch
         self.lean = bool(lean)                                   # render #4 geometry-only
         self.many = bool(many) and self.lean                     # renders #1-#3 as one render_many call
+        self.fused_critic = bool(fused_critic)
         self.dr = DiffRender(template, image_size, ratio=ratio)
         torch.manual_seed(seed)
         self.netE = AttributeNet(self.dr.vertices_init, bg=self.opt.bg).to(device)
@@ -201,7 +205,10 @@ class TrainerStep:
             Aire = dr.render_geometry(**Aire)                                              # render #4: its image is discarded (trainer.py:367)
         else:
             _, Aire = self._render(3, Aire)                                                # render #4 (face_normals only)
-        outs = self.critic(torch.cat((Xer90[:, :3], Xir[:, :3]), 0))
+        if self.fused_critic:
+            outs = self.critic(critic_inputs(self.Xa, Xer90, Xir, unmask=1, gp=False).g_batch)
+        else:
+            outs = self.critic(torch.cat((Xer90[:, :3], Xir[:, :3]), 0))
         o1, o2 = torch.split(outs, Bn, 0)
         lossR_fake = o.lambda_gan * (-o1.mean() - o.ganw * o2.mean()) / (1.0 + o.ganw)
         lossR_data = o.lambda_data * dr.recon_data(Xer, self.Xa, no_mask=o.bg, contour=o.lambda_contour)

@@ -664,6 +664,46 @@ int mm_attribute_mix_forward(const MMInterpDesc* desc, mm_stream_t stream);
 int mm_attribute_mix_backward(const MMInterpDesc* desc, const MMInterpGrads* grads, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Critic inputs: the image batches the reference's GAN step assembles for its discriminator (trainer.py:370-411, 429-431).
+ * With the channel map M of the unmask mode (C output channels; m = X[:, 3]):
+ *   unmask 0 (C = 3): M(X)_c = fl(fl(X_c * m) + fl(1 - m))     the image over white with its own alpha
+ *   unmask 1 (C = 3): M(X)_c = X_c
+ *   unmask 2 (C = 4): M(X)   = X
+ * the forward writes, in one launch,
+ *   out_batch   (3B,C,H,W) = cat(M(Xa), M(Xer90), M(Xir)) -- the D step's batch; its rows [B, 3B) are the G step's batch
+ *   out_gp_er90 (B,C,H,W)  = fl(fl(a1 * M(Xa)) + fl(fl(1 - a1) * M(Xer90)))     (only when the alphas are given)
+ *   out_gp_ir   (B,C,H,W)  = fl(fl(a2 * M(Xa)) + fl(fl(1 - a2) * M(Xir)))
+ * every operation rounded in fp32: torch's eager results.  The backward takes the (2B,C,H,W) gradient of rows [B, 3B) and writes,
+ * in one launch, the gradients of Xer90 and Xir, each (B,4,H,W) in the layout its flag names:
+ *   unmask 0: d X_c = fl(g_c * m), d m = ((g_0 * (X_0 - 1)) + g_1 * (X_1 - 1)) + g_2 * (X_2 - 1)
+ *   unmask 1: d X_c = g_c, d m = 0          unmask 2: d X = g
+ * No atomics, no workspace; bitwise reproducible.  Inputs and gradients are fp32 (B,4,H,W), each either NCHW-contiguous (flag 0)
+ * or NHWC-dense, strides (4HW, 1, 4W, 4) (flag 1: what mm_render_forward writes); the outputs and g_batch are NCHW-contiguous.
+ * H * W a multiple of 4 and 16-byte aligned pointers move 16 bytes per access, anything else 4.  Xa takes no gradient.
+ * 2 * B * ceil(H * W / 256) must fit an int32 (MM_ERR_UNSUPPORTED otherwise).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct MMCriticDesc {
+    int32_t B, H, W, unmask;        /* unmask: 0, 1 or 2 (MM_ERR_BAD_SHAPE otherwise) */
+    const float* Xa;                /* (B,4,H,W) the real images; the backward does not read them (may be NULL there) */
+    const float* Xer90;             /* (B,4,H,W) the first fake; the backward reads the fakes for unmask 0 only */
+    const float* Xir;               /* (B,4,H,W) the second fake; may be the same memory as Xer90 */
+    int32_t Xa_nhwc, Xer90_nhwc, Xir_nhwc;   /* layout flag of each input */
+    const float* alpha_er90;        /* (B) a1, or NULL: then alpha_ir is NULL too and no interpolate is written */
+    const float* alpha_ir;          /* (B) a2 */
+    float* out_batch;               /* (3B,C,H,W); forward only */
+    float* out_gp_er90;             /* (B,C,H,W); forward with alphas only */
+    float* out_gp_ir;
+} MMCriticDesc;
+typedef struct MMCriticGrads {
+    const float* g_batch;           /* (2B,C,H,W) upstream gradient of out_batch's rows [B, 3B) */
+    float* grad_er90;               /* (B,4,H,W), overwritten; NULL: not wanted (both NULL: no launch) */
+    float* grad_ir;
+    int32_t grad_er90_nhwc, grad_ir_nhwc;    /* layout flag of each gradient */
+} MMCriticGrads;
+int mm_critic_inputs_forward(const MMCriticDesc* desc, mm_stream_t stream);
+int mm_critic_inputs_backward(const MMCriticDesc* desc, const MMCriticGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -686,7 +726,7 @@ const char* mm_last_error_detail(void);
  * 5 MMAttLossDesc, 6 MMAttLossGrads, 7 MMTexFlowDesc, 8 MMTexFlowGrads, 9 MMPrepareDesc, 10 MMPrepareGrads, 11 MMDibrDesc,
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
- * 25 MMInterpGrads, 26 MMRenderViewsDesc. */
+ * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -696,7 +736,8 @@ size_t mm_struct_size(int which);
  * mm_camera_features_*, struct ids 20-23; still 9: MMInterpDesc / Grads, mm_interp_query_workspace, mm_collapse_resample and
  * mm_attribute_mix_*, struct ids 24 and 25, which only add -- no existing struct, field or meaning changes; a binding detects them by
  * mm_struct_size(24) != 0; still 9: MMRenderViewsDesc and mm_render_views_*, struct id 26, additions again -- MMRenderDesc and
- * MMRenderGrads keep their layout and meaning).  Bindings must refuse a library whose version differs from what they mirror. */
+ * MMRenderGrads keep their layout and meaning; still 9: MMCriticDesc / Grads and mm_critic_inputs_forward / _backward, struct ids 27 and 28,
+ * additions once more; a binding detects them by mm_struct_size(27) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
