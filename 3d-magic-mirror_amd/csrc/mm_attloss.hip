@@ -44,7 +44,9 @@ __global__ __launch_bounds__(256) void att_fwd_kernel(AttArgs a) {
     float s = 0.f;
     {
         const size_t n = (size_t)a.B * a.T;
-        if ((n & 3) == 0 && ((((size_t)a.p_te) | ((size_t)a.t_te)) & 15) == 0) {          // 16-byte loads (torch tensors always qualify)
+        // 16-byte loads where count and both pointers allow them.  A freshly allocated torch tensor qualifies; a contiguous view at an odd
+        // element offset of a larger buffer is only 4-byte aligned and takes the scalar path below, like a count that is not a multiple of 4.
+        if ((n & 3) == 0 && ((((size_t)a.p_te) | ((size_t)a.t_te)) & 15) == 0) {
             const float4* p4 = (const float4*)a.p_te; const float4* t4 = (const float4*)a.t_te;
             const size_t n4 = n >> 2;
             size_t i = gid;
