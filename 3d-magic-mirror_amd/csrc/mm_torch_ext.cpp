@@ -65,10 +65,11 @@ typedef int (*render_bwd_t)(const MMRenderDesc*, const MMRenderGrads*, void*);
 typedef int (*recon_t)(const MMReconDesc*, void*);
 typedef size_t (*recon_ws_t)(const MMReconDesc*);
 typedef int (*render_status_t)(const MMRenderDesc*, void*, int32_t*);
+typedef int (*views_fwd_t)(const MMRenderViewsDesc*, void*);
+typedef int (*views_bwd_t)(const MMRenderViewsDesc*, const MMRenderGrads*, void*);
 
 const float* fptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
-float* mptr(at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
-const float* optp(const c10::optional<at::Tensor>& t) { return (t.has_value() && t->defined()) ? t->data_ptr<float>() : nullptr; }
+float* mptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 
 at::Tensor dense_f32(const at::Tensor& t, const c10::Device& dev, const char* what) {
     TORCH_CHECK(t.is_cuda(), "the MI355X render path needs tensors in device memory (got a ", t.device(), " tensor for ", what, "); there is no CPU fallback");
@@ -83,7 +84,7 @@ void check(int rc, const char* what) { TORCH_CHECK(rc == MM_OK, what, " failed w
 // stream context gets that one): never a raw handle remembered from the forward, which may be stale by then.  The guard makes the tensors'
 // device current for the allocations and the launches.
 typedef c10::hip::HIPGuardMasqueradingAsCUDA DeviceGuard;
-int64_t current_stream(const c10::Device& dev) { return (int64_t)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
+void* current_stream(const c10::Device& dev) { return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
 
 MMRenderDesc proto_desc(const std::string& proto) {
     TORCH_CHECK(proto.size() == sizeof(MMRenderDesc), "descriptor prototype of ", proto.size(), " bytes, expected ", sizeof(MMRenderDesc));
@@ -92,102 +93,127 @@ MMRenderDesc proto_desc(const std::string& proto) {
     return d;
 }
 
-// rgba (B,H,W,4), face_normals (B,F,3), imnormal (B,H,W,3 or empty), face_idx (B,H,W) int32, loss (scalar or undefined) + the dense inputs
-std::vector<at::Tensor> render_forward(int64_t f_fwd, int64_t f_loss, const std::string& proto, at::Tensor vertices, at::Tensor textures,
-                                       at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations,
-                                       at::Tensor distances, at::Tensor biases, c10::optional<at::Tensor> gt, bool want_imnormal, double image_weight,
-                                       at::Tensor ws, int64_t stream) {
-    MMRenderDesc d = proto_desc(proto);
-    const c10::Device dev = azimuths.device();
-    vertices = dense_f32(vertices, dev, "vertices"); textures = dense_f32(textures, dev, "textures"); lights = dense_f32(lights, dev, "lights");
-    azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
-    distances = dense_f32(distances, dev, "distances").reshape({-1}); biases = dense_f32(biases, dev, "biases");
-    at::Tensor bgt, gtt;
-    if (bg.has_value() && bg->defined()) bgt = dense_f32(*bg, dev, "bg");
-    const int64_t B = azimuths.size(0), H = d.H, W = d.W;
-    TORCH_CHECK(B == d.B, "batch size ", B, " does not match the descriptor (", d.B, ")");
-    TORCH_CHECK(vertices.dim() == 3 && vertices.size(0) == B && vertices.size(1) == d.V && vertices.size(2) == 3, "vertices must be (B,", d.V, ",3), got ", vertices.sizes());
-    TORCH_CHECK(textures.dim() == 4 && textures.size(0) == B && textures.size(1) == 3 && textures.size(2) == d.Ht && textures.size(3) == d.Wt,
-                "textures must be (B,3,Ht,Wt), got ", textures.sizes());
-    TORCH_CHECK(lights.dim() == 2 && lights.size(0) == B && lights.size(1) == 9 && biases.dim() == 2 && biases.size(0) == B && biases.size(1) == 2 &&
-                elevations.size(0) == B && distances.size(0) == B, "lights (B,9), biases (B,2), elevations/distances (B) expected");
-    if (d.no_mask) TORCH_CHECK(bgt.defined() && bgt.dim() == 4 && bgt.size(0) == B && bgt.size(1) == 3 && bgt.size(2) == H && bgt.size(3) == W,
-                               "bg must be (B,3,", H, ",", W, ")");
-    auto opts = vertices.options();
-    at::Tensor rgba = at::empty({B, H, W, 4}, opts), fn = at::empty({B, (int64_t)d.F, 3}, opts);
-    at::Tensor face_idx = at::empty({B, H, W}, opts.dtype(at::kInt));
-    at::Tensor imn = want_imnormal ? at::empty({B, H, W, 3}, opts) : at::empty({0}, opts);
-    at::Tensor loss;
-    d.vertices = fptr(vertices); d.textures = fptr(textures); d.lights = fptr(lights); d.bg = d.no_mask ? fptr(bgt) : nullptr;
-    d.azimuths = fptr(azimuths); d.elevations = fptr(elevations); d.distances = fptr(distances); d.biases = fptr(biases);
-    d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
-    d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-    if (gt.has_value() && gt->defined()) {
-        gtt = dense_f32(*gt, dev, "gt_data");
-        TORCH_CHECK(gtt.dim() == 4 && gtt.size(0) == B && gtt.size(1) == 4 && gtt.size(2) == H && gtt.size(3) == W, "gt_data must be (B,4,", H, ",", W, "), got ", gtt.sizes());
-        loss = at::empty({}, opts);
-        d.fused_gt = fptr(gtt); d.fused_image_weight = (float)image_weight; d.fused_loss = mptr(loss);
-    }
-    check(((render_fwd_t)f_fwd)(&d, (void*)stream), "mm_render_forward");
-    if (gtt.defined()) check(((render_fwd_t)f_loss)(&d, (void*)stream), "mm_render_fused_loss");
-    return {rgba, fn, imn, face_idx, loss, vertices, textures, lights, bgt, azimuths, elevations, distances, biases, gtt};
+template <class Desc> void bind_workspace(Desc& d, const at::Tensor& ws) { d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel(); }
+
+// ---- what RenderNode, GeometryNode and RenderViewsNode share: inputs, descriptor, gradients, record check, camera shapes ------------------
+using torch::autograd::AutogradContext;
+using torch::autograd::tensor_list;
+
+// The dense float32 inputs of a render on one device: vertices, textures, lights and bg per SAMPLE, the cameras per IMAGE and flat
+// ((images) / biases (images,2)).  Textures, lights and bg stay undefined where the call has none (geometry only; bg without no_mask).
+struct DenseInputs {
+    at::Tensor vertices, textures, lights, bg, azimuths, elevations, distances, biases;
+    tensor_list list() const { return {vertices, textures, lights, bg, azimuths, elevations, distances, biases}; }
+};
+
+// What a render node saves for its backward, by position: DenseInputs::list(), then the forward products the backward re-reads, the workspace
+// (alive until the node dies) and, in RenderNode alone, the fused loss's dense target.  The image is not saved: the caller may overwrite it.
+enum Saved { S_VERTICES, S_TEXTURES, S_LIGHTS, S_BG, S_AZIMUTHS, S_ELEVATIONS, S_DISTANCES, S_BIASES, S_FACE_IDX, S_FACE_NORMALS, S_WORKSPACE, S_GT };
+
+DenseInputs saved_inputs(const tensor_list& sv) {
+    return {sv[S_VERTICES], sv[S_TEXTURES], sv[S_LIGHTS], sv[S_BG], sv[S_AZIMUTHS], sv[S_ELEVATIONS], sv[S_DISTANCES], sv[S_BIASES]};
 }
 
-// gradients of vertices, textures, lights, bg (undefined unless no_mask), azimuths, elevations, distances, biases
-// f_status: mm_render_status, or 0 -- DiffRender.check_texture_records (a diagnostic: it synchronises the stream)
-std::vector<at::Tensor> render_backward(int64_t f_bwd, int64_t f_status, const std::string& proto, at::Tensor vertices, at::Tensor textures, at::Tensor lights,
-                                        c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations, at::Tensor distances,
-                                        at::Tensor biases, at::Tensor face_idx, at::Tensor fn, c10::optional<at::Tensor> gt,
-                                        c10::optional<at::Tensor> rgba_fwd, c10::optional<at::Tensor> g_rgba, c10::optional<at::Tensor> g_fn,
-                                        c10::optional<at::Tensor> g_loss, double image_weight, at::Tensor ws, int64_t stream, int64_t deferred_totals) {
-    MMRenderDesc d = proto_desc(proto);
-    const int64_t B = azimuths.size(0), H = d.H, W = d.W;
-    const bool fused = gt.has_value() && gt->defined();
-    const bool deferred = fused && deferred_totals != 0;         // deferred fusion: gt / totals come from the recon_data that consumed this render's image
-    at::Tensor grgba, gfn, gloss;
-    d.vertices = fptr(vertices); d.textures = fptr(textures); d.lights = fptr(lights); d.bg = d.no_mask ? optp(bg) : nullptr;
-    d.azimuths = fptr(azimuths); d.elevations = fptr(elevations); d.distances = fptr(distances); d.biases = fptr(biases);
-    d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = nullptr;
-    d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-    if (g_fn.has_value() && g_fn->defined()) gfn = g_fn->to(at::kFloat).contiguous();
-    if (fused) {
-        // An undefined gradient of the loss output means the loss took no part in what is being differentiated (materialize_grads is off):
-        // its gradient is ZERO, never one -- e.g. reg.backward() through attributes['face_normals'] only.
-        gloss = (g_loss.has_value() && g_loss->defined()) ? g_loss->to(at::kFloat).reshape({}).contiguous()
-                                                          : at::zeros({}, vertices.options().dtype(at::kFloat));
-        d.fused_gt = optp(gt); d.fused_image_weight = (float)image_weight; d.fused_grad_loss = fptr(gloss);
-        d.rgba = nullptr;                                    // the backward re-forms the prediction per pixel: the image is not read back (nor saved)
-        if (deferred) {
-            d.fused_totals = reinterpret_cast<const float*>(deferred_totals); d.fused_contour = 0.f;
-            if (g_rgba.has_value() && g_rgba->defined()) grgba = g_rgba->to(at::kFloat).contiguous();   // the image's other consumers: added by the kernel
-        }
+// The caller's tensors as DenseInputs, every shape checked against the prototype `d` of `images` images of `samples` samples (images = samples x
+// views; render and render_geometry have one view).  per_view: the render_views call, whose cameras arrive as (B,N) / (B,N,2) and whose
+// messages name the sample count.
+DenseInputs dense_inputs(const c10::Device& dev, const MMRenderDesc& d, int64_t samples, int64_t images, bool per_view, const at::Tensor& vertices,
+                         const at::Tensor& textures, const at::Tensor& lights, const c10::optional<at::Tensor>& bg, const at::Tensor& azimuths,
+                         const at::Tensor& elevations, const at::Tensor& distances, const at::Tensor& biases) {
+    const bool geometry = d.geometry_only == 1;                  // (no textures, lights or bg)
+    DenseInputs in;
+    in.vertices = dense_f32(vertices, dev, "vertices");
+    if (!geometry) { in.textures = dense_f32(textures, dev, "textures"); in.lights = dense_f32(lights, dev, "lights"); }
+    in.azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); in.elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
+    in.distances = dense_f32(distances, dev, "distances").reshape({-1}); in.biases = dense_f32(biases, dev, "biases");
+    if (per_view) in.biases = in.biases.reshape({-1, 2});
+    if (bg.has_value() && bg->defined()) in.bg = dense_f32(*bg, dev, "bg");
+    const at::Tensor &v = in.vertices, &t = in.textures, &l = in.lights, &b = in.biases;
+    const bool vertices_ok = v.dim() == 3 && v.size(0) == samples && v.size(1) == d.V && v.size(2) == 3;
+    const bool textures_ok = geometry || (t.dim() == 4 && t.size(0) == samples && t.size(1) == 3 && t.size(2) == d.Ht && t.size(3) == d.Wt);
+    const bool lights_ok = geometry || (l.dim() == 2 && l.size(0) == samples && l.size(1) == 9);
+    const bool bg_ok = !d.no_mask || (in.bg.defined() && in.bg.dim() == 4 && in.bg.size(0) == samples && in.bg.size(1) == 3 && in.bg.size(2) == d.H && in.bg.size(3) == d.W);
+    const bool cameras_ok = in.elevations.size(0) == images && in.distances.size(0) == images && b.dim() == 2 && b.size(0) == images && b.size(1) == 2;
+    if (per_view) {
+        TORCH_CHECK(in.azimuths.size(0) == images && cameras_ok, "render_views: the cameras must hold B*N = ", images, " values each (biases B*N pairs)");
+        TORCH_CHECK(vertices_ok, "vertices must be (", samples, ",", d.V, ",3), got ", v.sizes());
+        TORCH_CHECK(textures_ok, "textures must be (", samples, ",3,", d.Ht, ",", d.Wt, "), got ", t.sizes());
+        TORCH_CHECK(lights_ok, "lights must be (", samples, ",9), got ", l.sizes());
+        TORCH_CHECK(bg_ok, "bg must be (", samples, ",3,", d.H, ",", d.W, ")");
     } else {
-        grgba = (g_rgba.has_value() && g_rgba->defined()) ? g_rgba->to(at::kFloat).contiguous() : at::zeros({B, H, W, 4}, vertices.options());
-        d.rgba = nullptr;                                    // (not read by the backward)
+        TORCH_CHECK(in.azimuths.size(0) == images, "batch size ", in.azimuths.size(0), " does not match the descriptor (", d.B, ")");
+        TORCH_CHECK(vertices_ok, "vertices must be (B,", d.V, ",3), got ", v.sizes());
+        TORCH_CHECK(textures_ok, "textures must be (B,3,Ht,Wt), got ", t.sizes());
+        TORCH_CHECK(lights_ok && cameras_ok, geometry ? "" : "lights (B,9), ", "biases (B,2), elevations/distances (B) expected");
+        TORCH_CHECK(bg_ok, "bg must be (B,3,", d.H, ",", d.W, ")");
     }
-    at::Tensor gv = at::empty_like(vertices), gt_ = at::empty_like(textures), gl = at::empty_like(lights), gbg;
-    if (d.no_mask) gbg = at::empty_like(*bg);
-    at::Tensor ga = at::empty_like(azimuths), ge = at::empty_like(elevations), gd = at::empty_like(distances), gb = at::empty_like(biases);
-    MMRenderGrads g;
-    g.grad_rgba = (fused && !deferred) ? nullptr : fptr(grgba); g.grad_face_normals = fptr(gfn); g.grad_vertices = mptr(gv); g.grad_textures = mptr(gt_);
-    g.grad_lights = mptr(gl); g.grad_bg = mptr(gbg); g.grad_azimuths = mptr(ga); g.grad_elevations = mptr(ge); g.grad_distances = mptr(gd);
-    g.grad_biases = mptr(gb);
-    check(((render_bwd_t)f_bwd)(&d, &g, (void*)stream), "mm_render_backward");
-    if (f_status) {
-        std::vector<int32_t> dropped((size_t)B);
-        const int st = ((render_status_t)f_status)(&d, (void*)stream, dropped.data());
-        std::string list;
-        bool any = false;
-        for (int32_t n : dropped) { list += (list.empty() ? "" : ", ") + std::to_string(n); any = any || n != 0; }
-        TORCH_CHECK(!(st == MM_ERR_WORKSPACE && any), "mm_render_backward: the texture-record pool overflowed (records dropped per image: [", list,
-                    "]); the texture gradients of those images are NaN. Raise DiffRender.extra_texture_records_per_pixel.");
-        check(st, "mm_render_status");
+    return in;
+}
+
+void bind_inputs(MMRenderDesc& d, const DenseInputs& in) {
+    d.vertices = fptr(in.vertices); d.textures = fptr(in.textures); d.lights = fptr(in.lights); d.bg = d.no_mask ? fptr(in.bg) : nullptr;
+    d.azimuths = fptr(in.azimuths); d.elevations = fptr(in.elevations); d.distances = fptr(in.distances); d.biases = fptr(in.biases);
+}
+
+// The gradients of the dense inputs (textures and lights only where the call has them, bg only under no_mask) and the MMRenderGrads that points
+// at them and at the two upstream gradients (either may be undefined: NULL).
+struct RenderGrads {
+    at::Tensor vertices, textures, lights, bg, azimuths, elevations, distances, biases;
+    MMRenderGrads abi{};
+    RenderGrads(const DenseInputs& in, bool no_mask, const at::Tensor& grad_rgba, const at::Tensor& grad_face_normals) {
+        vertices = at::empty_like(in.vertices);
+        if (in.textures.defined()) { textures = at::empty_like(in.textures); lights = at::empty_like(in.lights); }
+        if (no_mask) bg = at::empty_like(in.bg);
+        azimuths = at::empty_like(in.azimuths); elevations = at::empty_like(in.elevations); distances = at::empty_like(in.distances);
+        biases = at::empty_like(in.biases);
+        abi.grad_rgba = fptr(grad_rgba); abi.grad_face_normals = fptr(grad_face_normals);
+        abi.grad_vertices = mptr(vertices); abi.grad_textures = mptr(textures); abi.grad_lights = mptr(lights); abi.grad_bg = mptr(bg);
+        abi.grad_azimuths = mptr(azimuths); abi.grad_elevations = mptr(elevations); abi.grad_distances = mptr(distances); abi.grad_biases = mptr(biases);
     }
-    return {gv, gt_, gl, gbg, ga, ge, gd, gb};
+};
+
+// DiffRender.check_texture_records (f_status: mm_render_status, or 0): a diagnostic after a backward -- it synchronises the stream.  `d` is the
+// backward's descriptor of `images` images; their render workspace starts `offset` bytes into the node's (render_views: behind the staging head).
+void check_texture_records(int64_t f_status, MMRenderDesc d, void* stream, int64_t images, size_t offset, const char* call, const char* whose) {
+    if (!f_status) return;
+    d.workspace = (char*)d.workspace + offset; d.workspace_bytes -= offset;
+    std::vector<int32_t> dropped((size_t)images);
+    const int st = ((render_status_t)f_status)(&d, stream, dropped.data());
+    std::string list;
+    bool any = false;
+    for (int32_t n : dropped) { list += (list.empty() ? "" : ", ") + std::to_string(n); any = any || n != 0; }
+    TORCH_CHECK(!(st == MM_ERR_WORKSPACE && any), call, ": the texture-record pool overflowed (records dropped per image: [", list,
+                "]); the texture gradients of those ", whose, " are NaN. Raise DiffRender.extra_texture_records_per_pixel.");
+    check(st, "mm_render_status");
+}
+
+// the cameras may arrive as (B), (B,1), (B,N), ...: the kernels see them flat, the gradients go back in the caller's shapes (advisor r05)
+void save_camera_shapes(AutogradContext* ctx, const at::Tensor& azimuths, const at::Tensor& elevations, const at::Tensor& distances, const at::Tensor& biases) {
+    ctx->saved_data["shape_a"] = azimuths.sizes().vec(); ctx->saved_data["shape_e"] = elevations.sizes().vec();
+    ctx->saved_data["shape_d"] = distances.sizes().vec(); ctx->saved_data["shape_b"] = biases.sizes().vec();
+}
+void restore_camera_shapes(AutogradContext* ctx, RenderGrads& g) {
+    auto restore = [ctx](at::Tensor& t, const char* key) {          // (a camera that arrived flat keeps its tensor: no view is made)
+        const at::DimVector shape = ctx->saved_data[key].toDimVector();
+        if (!t.sizes().equals(shape)) t = t.reshape(shape);
+    };
+    restore(g.azimuths, "shape_a"); restore(g.elevations, "shape_e"); restore(g.distances, "shape_d"); restore(g.biases, "shape_b");
+}
+
+// ---- recon_data --------------------------------------------------------------------------------------------------------------------------------
+// the descriptor of a (B,4,H,W) prediction with its own strides against a dense target; the workspace is bound if there is one yet
+MMReconDesc recon_desc(const at::Tensor& pred, const at::Tensor& gt, const at::Tensor& ws, double image_weight, double contour) {
+    MMReconDesc d{};
+    d.B = (int32_t)pred.size(0); d.H = (int32_t)pred.size(2); d.W = (int32_t)pred.size(3);
+    d.pred = fptr(pred); d.gt = fptr(gt);
+    for (int i = 0; i < 4; ++i) d.pred_strides[i] = pred.stride(i);
+    d.image_weight = (float)image_weight; d.contour = (float)contour;
+    if (ws.defined()) bind_workspace(d, ws);
+    return d;
 }
 
 // loss, dense prediction, dense target, workspace
-std::vector<at::Tensor> recon_forward(int64_t f_ws, int64_t f_fwd, at::Tensor pred, at::Tensor gt, double image_weight, double contour, int64_t stream) {
+std::vector<at::Tensor> recon_forward(int64_t f_ws, int64_t f_fwd, at::Tensor pred, at::Tensor gt, double image_weight, double contour, void* stream) {
     TORCH_CHECK(pred.is_cuda() && gt.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
     const c10::Device dev = pred.device();
     pred = pred.detach().to(at::kFloat);
@@ -195,37 +221,25 @@ std::vector<at::Tensor> recon_forward(int64_t f_ws, int64_t f_fwd, at::Tensor pr
     gt = gt.detach().to(dev, at::kFloat).contiguous();
     TORCH_CHECK(pred.dim() == 4 && pred.size(1) == 4 && gt.sizes() == pred.sizes(), "recon_data expects (B,4,H,W) prediction and target, got ", pred.sizes(), " / ", gt.sizes());
     at::Tensor loss = at::empty({}, pred.options());
-    MMReconDesc d;
-    std::memset(&d, 0, sizeof d);
-    d.B = (int32_t)pred.size(0); d.H = (int32_t)pred.size(2); d.W = (int32_t)pred.size(3);
-    d.pred = fptr(pred); d.gt = fptr(gt);
-    for (int i = 0; i < 4; ++i) d.pred_strides[i] = pred.stride(i);
-    d.image_weight = (float)image_weight; d.contour = (float)contour; d.loss = mptr(loss);
+    MMReconDesc d = recon_desc(pred, gt, at::Tensor(), image_weight, contour);
+    d.loss = mptr(loss);
     at::Tensor ws = at::empty({(int64_t)((recon_ws_t)f_ws)(&d)}, pred.options().dtype(at::kByte));
-    d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-    check(((recon_t)f_fwd)(&d, (void*)stream), "mm_recon_data_forward");
+    bind_workspace(d, ws);
+    check(((recon_t)f_fwd)(&d, stream), "mm_recon_data_forward");
     return {loss, pred, gt, ws};
 }
 
-at::Tensor recon_backward(int64_t f_bwd, at::Tensor pred, at::Tensor gt, at::Tensor ws, at::Tensor g_loss, double image_weight, double contour, int64_t stream) {
-    g_loss = g_loss.to(pred.device(), at::kFloat).contiguous();
-    at::Tensor grad = at::empty_strided(pred.sizes(), pred.strides(), pred.options());
-    MMReconDesc d;
-    std::memset(&d, 0, sizeof d);
-    d.B = (int32_t)pred.size(0); d.H = (int32_t)pred.size(2); d.W = (int32_t)pred.size(3);
-    d.pred = fptr(pred); d.gt = fptr(gt);
-    for (int i = 0; i < 4; ++i) d.pred_strides[i] = pred.stride(i);
-    d.image_weight = (float)image_weight; d.contour = (float)contour;
-    d.grad_loss = fptr(g_loss); d.grad_pred = mptr(grad);
-    d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-    check(((recon_t)f_bwd)(&d, (void*)stream), "mm_recon_data_backward");
-    return grad;
+// the live mailbox of the render whose image starts at `rgba_ptr`, if any
+std::shared_ptr<Mailbox> find_mailbox(const void* rgba_ptr) {
+    std::lock_guard<std::mutex> lock(g_mail_mutex);
+    auto it = g_mail.find(rgba_ptr);
+    return it != g_mail.end() ? it->second.lock() : nullptr;
 }
 
 // ---- the autograd nodes themselves, in C++: no Python (and no GIL hand-over to the autograd thread) in the backward -----------------------
-using torch::autograd::AutogradContext;
-using torch::autograd::tensor_list;
-
+// DiffRender.render / render_recon.  Outputs: rgba (B,H,W,4), face_normals (B,F,3), imnormal (B,H,W,3 or empty), face_idx (B,H,W) int32, then the
+// loss (gt given: the fused loss) or the deferred-fusion token (defer).  The backward returns the gradients of vertices, textures, lights, bg
+// (undefined unless no_mask), azimuths, elevations, distances, biases.
 class RenderNode : public torch::autograd::Function<RenderNode> {
  public:
     static tensor_list forward(AutogradContext* ctx, int64_t f_fwd, int64_t f_loss, int64_t f_bwd, int64_t f_status, std::string proto, int64_t ws_bytes,
@@ -233,63 +247,97 @@ class RenderNode : public torch::autograd::Function<RenderNode> {
                                at::Tensor elevations, at::Tensor distances, at::Tensor biases, c10::optional<at::Tensor> gt, bool want_imnormal,
                                double image_weight, bool defer) {
         TORCH_CHECK(azimuths.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
-        const DeviceGuard guard(azimuths.device());
-        // the camera scalars may arrive as (B), (B,1), ...: the kernels see (B), the gradients go back in the caller's shapes (advisor r05)
-        ctx->saved_data["shape_a"] = azimuths.sizes().vec(); ctx->saved_data["shape_e"] = elevations.sizes().vec(); ctx->saved_data["shape_d"] = distances.sizes().vec();
+        const c10::Device dev = azimuths.device();
+        const DeviceGuard guard(dev);
+        save_camera_shapes(ctx, azimuths, elevations, distances, biases);
         at::Tensor ws = at::empty({ws_bytes}, azimuths.options().dtype(at::kByte));   // (the caching allocator is the workspace pool)
-        auto out = render_forward(f_fwd, f_loss, proto, vertices, textures, lights, bg, azimuths, elevations, distances, biases, gt, want_imnormal,
-                                  image_weight, ws, current_stream(azimuths.device()));
-        const bool fused = out[13].defined();
+        MMRenderDesc d = proto_desc(proto);
+        const int64_t B = d.B, H = d.H, W = d.W;
+        const DenseInputs in = dense_inputs(dev, d, B, B, false, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
+        auto opts = in.vertices.options();
+        at::Tensor rgba = at::empty({B, H, W, 4}, opts), fn = at::empty({B, (int64_t)d.F, 3}, opts);
+        at::Tensor face_idx = at::empty({B, H, W}, opts.dtype(at::kInt));
+        at::Tensor imn = want_imnormal ? at::empty({B, H, W, 3}, opts) : at::empty({0}, opts);
+        at::Tensor loss, gtt;
+        bind_inputs(d, in); bind_workspace(d, ws);
+        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
+        const bool fused = gt.has_value() && gt->defined();
+        if (fused) {
+            gtt = dense_f32(*gt, dev, "gt_data");
+            TORCH_CHECK(gtt.dim() == 4 && gtt.size(0) == B && gtt.size(1) == 4 && gtt.size(2) == H && gtt.size(3) == W, "gt_data must be (B,4,", H, ",", W, "), got ", gtt.sizes());
+            loss = at::empty({}, opts);
+            d.fused_gt = fptr(gtt); d.fused_image_weight = (float)image_weight; d.fused_loss = mptr(loss);
+        }
+        void* stream = current_stream(dev);
+        check(((render_fwd_t)f_fwd)(&d, stream), "mm_render_forward");
+        if (fused) check(((render_fwd_t)f_loss)(&d, stream), "mm_render_fused_loss");
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto;
-        ctx->saved_data["image_weight"] = image_weight; ctx->saved_data["fused"] = fused;
-        // dense inputs, forward products the backward re-reads, and the workspace (alive until this node dies)
-        ctx->save_for_backward({out[5], out[6], out[7], out[8], out[9], out[10], out[11], out[12], out[3], out[1], out[13],
-                                at::Tensor(), ws});          // (the image is not saved: the caller may overwrite it)
-        ctx->mark_non_differentiable({out[3], out[2]});
+        ctx->saved_data["image_weight"] = image_weight;
+        tensor_list saved = in.list();
+        saved.insert(saved.end(), {face_idx, fn, ws, gtt});      // (enum Saved)
+        ctx->save_for_backward(saved);
+        ctx->mark_non_differentiable({face_idx, imn});
         ctx->set_materialize_grads(false);                       // an output nobody used arrives as an undefined gradient, not as a zero-filled tensor (three
                                                                  // allocations + fill launches per step when only the image feeds the loss)
-        if (fused) ctx->mark_non_differentiable({out[0]});
-        tensor_list ret = {out[0], out[1], out[2], out[3]};
-        if (fused) ret.push_back(out[4]);
+        if (fused) ctx->mark_non_differentiable({rgba});
+        tensor_list ret = {rgba, fn, imn, face_idx};
+        if (fused) ret.push_back(loss);
         else if (defer) {
             // deferred fusion: a fifth output whose only job is to carry dL/dloss of a later recon_data(image, gt) back into THIS node (never read, never
             // written: no launch), and the mailbox that recon_data finds through the image's address
             auto mb = std::make_shared<Mailbox>();
-            mb->rgba_ptr = out[0].data_ptr(); mb->B = out[0].size(0); mb->H = out[0].size(1); mb->W = out[0].size(2);
+            mb->rgba_ptr = rgba.data_ptr(); mb->B = B; mb->H = H; mb->W = W;
             mb->has_token = true;
             ctx->saved_data["mb"] = mailbox_holder(mb);
             { std::lock_guard<std::mutex> lock(g_mail_mutex);
               if (g_mail.size() > 256) for (auto it = g_mail.begin(); it != g_mail.end();) it = it->second.expired() ? g_mail.erase(it) : std::next(it);
               g_mail[mb->rgba_ptr] = mb; }
-            ret.push_back(at::empty({1}, out[0].options()));    // (declares output 4 and its metadata; dropped by render_node)
+            ret.push_back(at::empty({1}, opts));                 // (declares output 4 and its metadata; dropped by render_node)
         }
         return ret;
     }
 
     static tensor_list backward(AutogradContext* ctx, tensor_list g) {
         const auto sv = ctx->get_saved_variables();
-        const bool fused = ctx->saved_data["fused"].toBool();
-        const DeviceGuard guard(sv[4].device());
-        auto opt = [](const at::Tensor& t) { return t.defined() ? c10::optional<at::Tensor>(t) : c10::nullopt; };
+        const DenseInputs in = saved_inputs(sv);
+        const c10::Device dev = in.azimuths.device();
+        const DeviceGuard guard(dev);
+        const bool token_grad = g.size() > 4 && g[4].defined();  // of output 4: the fused loss, or the token a recon_data routed its dL/dloss through
         // deferred fusion: a recon_data consumed this render's image and its loss takes part in what is differentiated (the token has a gradient)
         std::shared_ptr<Mailbox> mb;
-        if (!fused && g.size() > 4 && g[4].defined() && ctx->saved_data.count("mb")) mb = mailbox_of(ctx->saved_data["mb"].toTensor());
+        if (!sv[S_GT].defined() && token_grad && ctx->saved_data.count("mb")) mb = mailbox_of(ctx->saved_data["mb"].toTensor());
         const bool deferred = mb && mb->gt.defined() && mb->totals != nullptr;
-        TORCH_CHECK(deferred || fused || g.size() <= 4 || !g[4].defined(), "a recon_data token carries a gradient but its render has no recon_data on record");
-        const int64_t f_bwd = ctx->saved_data["f_bwd"].toInt(), f_status = ctx->saved_data["f_status"].toInt();
-        auto gr = deferred
-            ? render_backward(f_bwd, f_status, ctx->saved_data["proto"].toStringRef(), sv[0], sv[1], sv[2], opt(sv[3]), sv[4], sv[5],
-                              sv[6], sv[7], sv[8], sv[9], opt(mb->gt), c10::nullopt, opt(g[0]), opt(g[1]), opt(g[4]), mb->image_weight, sv[12],
-                              current_stream(sv[4].device()), reinterpret_cast<int64_t>(mb->totals))
-            : render_backward(f_bwd, f_status, ctx->saved_data["proto"].toStringRef(), sv[0], sv[1], sv[2], opt(sv[3]), sv[4], sv[5],
-                              sv[6], sv[7], sv[8], sv[9], opt(sv[10]), opt(sv[11]), opt(g[0]), opt(g[1]),
-                              (fused && g.size() > 4) ? opt(g[4]) : c10::nullopt, ctx->saved_data["image_weight"].toDouble(), sv[12],
-                              current_stream(sv[4].device()), 0);
+        TORCH_CHECK(deferred || sv[S_GT].defined() || !token_grad, "a recon_data token carries a gradient but its render has no recon_data on record");
+        // deferred: target, weight and totals come from the recon_data that consumed the image; fused: from this node's own forward
+        const at::Tensor& gt = deferred ? mb->gt : sv[S_GT];
+        const double image_weight = deferred ? mb->image_weight : ctx->saved_data["image_weight"].toDouble();
+        const bool fused = gt.defined();
+        MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
+        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
+        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
+        d.rgba = nullptr; d.imnormal = nullptr;                  // the backward re-forms the prediction per pixel: the image is not read back (nor saved)
+        at::Tensor grgba, gfn, gloss;
+        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
+        if (fused) {
+            // An undefined gradient of the loss output means the loss took no part in what is being differentiated (materialize_grads is off):
+            // its gradient is ZERO, never one -- e.g. reg.backward() through attributes['face_normals'] only.
+            gloss = token_grad ? g[4].to(at::kFloat).reshape({}).contiguous() : at::zeros({}, in.vertices.options().dtype(at::kFloat));
+            d.fused_gt = fptr(gt); d.fused_image_weight = (float)image_weight; d.fused_grad_loss = fptr(gloss);
+            if (deferred) {
+                d.fused_totals = mb->totals; d.fused_contour = 0.f;
+                if (g[0].defined()) grgba = g[0].to(at::kFloat).contiguous();   // the image's other consumers: added by the kernel
+            }
+        } else {
+            grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({d.B, d.H, d.W, 4}, in.vertices.options());
+        }
+        RenderGrads gr(in, d.no_mask, grgba, gfn);
+        void* stream = current_stream(dev);
+        check(((render_bwd_t)ctx->saved_data["f_bwd"].toInt())(&d, &gr.abi, stream), "mm_render_backward");
+        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, d.B, 0, "mm_render_backward", "images");
+        restore_camera_shapes(ctx, gr);
         // one entry per forward argument: six non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, then four more
-        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr[0], gr[1], gr[2], gr[3],
-                gr[4].reshape(ctx->saved_data["shape_a"].toIntVector()), gr[5].reshape(ctx->saved_data["shape_e"].toIntVector()),
-                gr[6].reshape(ctx->saved_data["shape_d"].toIntVector()), gr[7],
-                at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr.vertices, gr.textures, gr.lights, gr.bg,
+                gr.azimuths, gr.elevations, gr.distances, gr.biases, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
 
@@ -304,10 +352,7 @@ class ReconDeferredNode : public torch::autograd::Function<ReconDeferredNode> {
         auto out = recon_forward(f_ws, f_fwd, pred, gt, image_weight, 0.0, current_stream(pred.device()));
         auto mb = mailbox_of(holder);
         TORCH_CHECK(mb, "deferred recon_data without its render's mailbox");
-        MMReconDesc d;
-        std::memset(&d, 0, sizeof d);
-        d.B = (int32_t)out[1].size(0); d.H = (int32_t)out[1].size(2); d.W = (int32_t)out[1].size(3);
-        d.workspace = out[3].data_ptr(); d.workspace_bytes = (size_t)out[3].numel();
+        const MMReconDesc d = recon_desc(out[1], out[2], out[3], image_weight, 0.0);
         typedef const float* (*totals_t)(const MMReconDesc*);
         mb->totals = ((totals_t)f_tot)(&d);
         TORCH_CHECK(mb->totals != nullptr, "mm_recon_data_totals failed");
@@ -335,10 +380,14 @@ class ReconNode : public torch::autograd::Function<ReconNode> {
         return out[0];
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list g) {
-        const auto sv = ctx->get_saved_variables();
-        const DeviceGuard guard(sv[0].device());
-        at::Tensor grad = recon_backward(ctx->saved_data["f_bwd"].toInt(), sv[0], sv[1], sv[2], g[0], ctx->saved_data["image_weight"].toDouble(),
-                                         ctx->saved_data["contour"].toDouble(), current_stream(sv[0].device()));
+        const auto sv = ctx->get_saved_variables();               // dense prediction, dense target, workspace
+        const at::Tensor& pred = sv[0];
+        const DeviceGuard guard(pred.device());
+        at::Tensor g_loss = g[0].to(pred.device(), at::kFloat).contiguous();
+        at::Tensor grad = at::empty_strided(pred.sizes(), pred.strides(), pred.options());
+        MMReconDesc d = recon_desc(pred, sv[1], sv[2], ctx->saved_data["image_weight"].toDouble(), ctx->saved_data["contour"].toDouble());
+        d.grad_loss = fptr(g_loss); d.grad_pred = mptr(grad);
+        check(((recon_t)ctx->saved_data["f_bwd"].toInt())(&d, current_stream(pred.device())), "mm_recon_data_backward");
         return {at::Tensor(), at::Tensor(), at::Tensor(), grad, at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
@@ -354,44 +403,35 @@ class GeometryNode : public torch::autograd::Function<GeometryNode> {
         const DeviceGuard guard(dev);
         MMRenderDesc d = proto_desc(proto);
         TORCH_CHECK(d.geometry_only == 1, "GeometryNode needs a geometry-only descriptor prototype");
-        vertices = dense_f32(vertices, dev, "vertices");
-        ctx->saved_data["shape_a"] = azimuths.sizes().vec(); ctx->saved_data["shape_e"] = elevations.sizes().vec(); ctx->saved_data["shape_d"] = distances.sizes().vec();
-        azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
-        distances = dense_f32(distances, dev, "distances").reshape({-1}); biases = dense_f32(biases, dev, "biases");
-        const int64_t B = azimuths.size(0);
-        TORCH_CHECK(B == d.B, "batch size ", B, " does not match the descriptor (", d.B, ")");
-        TORCH_CHECK(vertices.dim() == 3 && vertices.size(0) == B && vertices.size(1) == d.V && vertices.size(2) == 3, "vertices must be (B,", d.V, ",3), got ", vertices.sizes());
-        TORCH_CHECK(biases.dim() == 2 && biases.size(0) == B && biases.size(1) == 2 && elevations.size(0) == B && distances.size(0) == B,
-                    "biases (B,2), elevations/distances (B) expected");
+        save_camera_shapes(ctx, azimuths, elevations, distances, biases);
+        const DenseInputs in = dense_inputs(dev, d, d.B, d.B, false, vertices, at::Tensor(), at::Tensor(), c10::nullopt, azimuths, elevations, distances, biases);
         at::Tensor ws = at::empty({ws_bytes}, azimuths.options().dtype(at::kByte));
-        at::Tensor fn = at::empty({B, (int64_t)d.F, 3}, vertices.options());
-        d.vertices = fptr(vertices); d.azimuths = fptr(azimuths); d.elevations = fptr(elevations); d.distances = fptr(distances); d.biases = fptr(biases);
-        d.face_normals = mptr(fn); d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-        check(((render_fwd_t)f_fwd)(&d, (void*)current_stream(dev)), "mm_render_forward (geometry only)");
+        at::Tensor fn = at::empty({(int64_t)d.B, (int64_t)d.F, 3}, in.vertices.options());
+        bind_inputs(d, in); bind_workspace(d, ws);
+        d.face_normals = mptr(fn);
+        check(((render_fwd_t)f_fwd)(&d, current_stream(dev)), "mm_render_forward (geometry only)");
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["proto"] = proto;
-        ctx->save_for_backward({vertices, azimuths, elevations, distances, biases, ws});
+        tensor_list saved = in.list();
+        saved.insert(saved.end(), {at::Tensor(), at::Tensor(), ws});   // (enum Saved; the backward reads neither face_idx nor the normals)
+        ctx->save_for_backward(saved);
         ctx->set_materialize_grads(false);
         return fn;
     }
     static tensor_list backward(AutogradContext* ctx, tensor_list g) {
-        const auto sv = ctx->get_saved_variables();
         tensor_list none(9);
         if (!g[0].defined()) return none;                        // face_normals took no part in what is differentiated
-        const DeviceGuard guard(sv[1].device());
+        const auto sv = ctx->get_saved_variables();
+        const DenseInputs in = saved_inputs(sv);
+        const c10::Device dev = in.azimuths.device();
+        const DeviceGuard guard(dev);
         MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
         at::Tensor gfn = g[0].to(at::kFloat).contiguous();
-        at::Tensor ws = sv[5];
-        d.vertices = fptr(sv[0]); d.azimuths = fptr(sv[1]); d.elevations = fptr(sv[2]); d.distances = fptr(sv[3]); d.biases = fptr(sv[4]);
+        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
         d.face_normals = mptr(gfn);                              // (a valid pointer for the argument check; the backward does not read the normals)
-        d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-        at::Tensor gv = at::empty_like(sv[0]), ga = at::empty_like(sv[1]), ge = at::empty_like(sv[2]), gd = at::empty_like(sv[3]), gb = at::empty_like(sv[4]);
-        MMRenderGrads gr;
-        std::memset(&gr, 0, sizeof gr);
-        gr.grad_face_normals = fptr(gfn); gr.grad_vertices = mptr(gv); gr.grad_azimuths = mptr(ga); gr.grad_elevations = mptr(ge);
-        gr.grad_distances = mptr(gd); gr.grad_biases = mptr(gb);
-        check(((render_bwd_t)ctx->saved_data["f_bwd"].toInt())(&d, &gr, (void*)current_stream(sv[1].device())), "mm_render_backward (geometry only)");
-        none[4] = gv; none[5] = ga.reshape(ctx->saved_data["shape_a"].toIntVector()); none[6] = ge.reshape(ctx->saved_data["shape_e"].toIntVector());
-        none[7] = gd.reshape(ctx->saved_data["shape_d"].toIntVector()); none[8] = gb;
+        RenderGrads gr(in, false, at::Tensor(), gfn);
+        check(((render_bwd_t)ctx->saved_data["f_bwd"].toInt())(&d, &gr.abi, current_stream(dev)), "mm_render_backward (geometry only)");
+        restore_camera_shapes(ctx, gr);
+        none[4] = gr.vertices; none[5] = gr.azimuths; none[6] = gr.elevations; none[7] = gr.distances; none[8] = gr.biases;
         return none;
     }
 };
@@ -399,9 +439,6 @@ class GeometryNode : public torch::autograd::Function<GeometryNode> {
 // DiffRender.render_views (MMRenderViewsDesc: B samples x N views in one pass over B*N images; the per-sample tensors are read from their single
 // copy, their gradients are the view-order sums).  The prototype is the MMRenderDesc of the B*N images; the cameras arrive as (B,N) / (B,N,2)
 // (an expanded (B,) input gets its gradient through autograd's own expand); outputs are (B,N,...).  No fused loss, no deferred fusion.
-typedef int (*views_fwd_t)(const MMRenderViewsDesc*, void*);
-typedef int (*views_bwd_t)(const MMRenderViewsDesc*, const MMRenderGrads*, void*);
-
 class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
  public:
     static tensor_list forward(AutogradContext* ctx, int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t views, int64_t ws_bytes,
@@ -410,41 +447,26 @@ class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
         TORCH_CHECK(azimuths.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
         const c10::Device dev = azimuths.device();
         const DeviceGuard guard(dev);
-        MMRenderViewsDesc vd;
-        vd.render = proto_desc(proto); vd.views = (int32_t)views;
-        MMRenderDesc& d = vd.render;
+        MMRenderDesc d = proto_desc(proto);                          // (of the B*N images)
         const int64_t N = views, BN = d.B, H = d.H, W = d.W;
         TORCH_CHECK(N >= 1 && BN % N == 0, "render_views: ", BN, " images are not a multiple of ", N, " views");
         const int64_t B = BN / N;
-        ctx->saved_data["shape_a"] = azimuths.sizes().vec(); ctx->saved_data["shape_e"] = elevations.sizes().vec();
-        ctx->saved_data["shape_d"] = distances.sizes().vec(); ctx->saved_data["shape_b"] = biases.sizes().vec();
-        vertices = dense_f32(vertices, dev, "vertices"); textures = dense_f32(textures, dev, "textures"); lights = dense_f32(lights, dev, "lights");
-        azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
-        distances = dense_f32(distances, dev, "distances").reshape({-1}); biases = dense_f32(biases, dev, "biases").reshape({-1, 2});
-        at::Tensor bgt;
-        if (bg.has_value() && bg->defined()) bgt = dense_f32(*bg, dev, "bg");
-        TORCH_CHECK(azimuths.size(0) == BN && elevations.size(0) == BN && distances.size(0) == BN && biases.size(0) == BN,
-                    "render_views: the cameras must hold B*N = ", BN, " values each (biases B*N pairs)");
-        TORCH_CHECK(vertices.dim() == 3 && vertices.size(0) == B && vertices.size(1) == d.V && vertices.size(2) == 3, "vertices must be (", B, ",", d.V, ",3), got ", vertices.sizes());
-        TORCH_CHECK(textures.dim() == 4 && textures.size(0) == B && textures.size(1) == 3 && textures.size(2) == d.Ht && textures.size(3) == d.Wt,
-                    "textures must be (", B, ",3,", d.Ht, ",", d.Wt, "), got ", textures.sizes());
-        TORCH_CHECK(lights.dim() == 2 && lights.size(0) == B && lights.size(1) == 9, "lights must be (", B, ",9), got ", lights.sizes());
-        if (d.no_mask) TORCH_CHECK(bgt.defined() && bgt.dim() == 4 && bgt.size(0) == B && bgt.size(1) == 3 && bgt.size(2) == H && bgt.size(3) == W,
-                                   "bg must be (", B, ",3,", H, ",", W, ")");
-        auto opts = vertices.options();
+        save_camera_shapes(ctx, azimuths, elevations, distances, biases);
+        const DenseInputs in = dense_inputs(dev, d, B, BN, true, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
+        auto opts = in.vertices.options();
         at::Tensor rgba = at::empty({B, N, H, W, 4}, opts), fn = at::empty({B, N, (int64_t)d.F, 3}, opts);
         at::Tensor face_idx = at::empty({B, N, H, W}, opts.dtype(at::kInt));
         at::Tensor imn = want_imnormal ? at::empty({B, N, H, W, 3}, opts) : at::empty({0}, opts);
         at::Tensor ws = at::empty({ws_bytes}, opts.dtype(at::kByte));
-        d.vertices = fptr(vertices); d.textures = fptr(textures); d.lights = fptr(lights); d.bg = d.no_mask ? fptr(bgt) : nullptr;
-        d.azimuths = fptr(azimuths); d.elevations = fptr(elevations); d.distances = fptr(distances); d.biases = fptr(biases);
+        bind_inputs(d, in); bind_workspace(d, ws);
         d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
-        d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-        check(((views_fwd_t)f_fwd)(&vd, (void*)current_stream(dev)), "mm_render_views_forward");
+        const MMRenderViewsDesc vd{d, (int32_t)views};
+        check(((views_fwd_t)f_fwd)(&vd, current_stream(dev)), "mm_render_views_forward");
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto; ctx->saved_data["views"] = views;
         ctx->saved_data["staging_bytes"] = staging_bytes;            // the head of the workspace (the per-image gradients' staging): mm_render_status skips it
-        // the UN-replicated inputs, the forward products the backward re-reads, and the workspace (alive until this node dies)
-        ctx->save_for_backward({vertices, textures, lights, bgt, azimuths, elevations, distances, biases, face_idx, fn, ws});
+        tensor_list saved = in.list();                               // (the UN-replicated inputs)
+        saved.insert(saved.end(), {face_idx, fn, ws});               // (enum Saved)
+        ctx->save_for_backward(saved);
         ctx->mark_non_differentiable({face_idx, imn});
         ctx->set_materialize_grads(false);
         return {rgba, fn, imn, face_idx};
@@ -452,53 +474,34 @@ class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
 
     static tensor_list backward(AutogradContext* ctx, tensor_list g) {
         const auto sv = ctx->get_saved_variables();
-        const c10::Device dev = sv[4].device();
+        const DenseInputs in = saved_inputs(sv);
+        const c10::Device dev = in.azimuths.device();
         const DeviceGuard guard(dev);
-        MMRenderViewsDesc vd;
-        vd.render = proto_desc(ctx->saved_data["proto"].toStringRef()); vd.views = (int32_t)ctx->saved_data["views"].toInt();
-        MMRenderDesc& d = vd.render;
-        const int64_t N = vd.views, BN = d.B, B = BN / N, H = d.H, W = d.W;
-        at::Tensor fn = sv[9], ws = sv[10];
-        d.vertices = fptr(sv[0]); d.textures = fptr(sv[1]); d.lights = fptr(sv[2]); d.bg = d.no_mask ? fptr(sv[3]) : nullptr;
-        d.azimuths = fptr(sv[4]); d.elevations = fptr(sv[5]); d.distances = fptr(sv[6]); d.biases = fptr(sv[7]);
-        d.face_idx = sv[8].data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = nullptr; d.rgba = nullptr;
-        d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel();
-        at::Tensor grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({B, N, H, W, 4}, sv[0].options());
+        MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
+        const int64_t N = ctx->saved_data["views"].toInt(), BN = d.B, B = BN / N;
+        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
+        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
+        d.rgba = nullptr; d.imnormal = nullptr;
+        at::Tensor grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({B, N, (int64_t)d.H, (int64_t)d.W, 4}, in.vertices.options());
         at::Tensor gfn;
         if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
-        at::Tensor gv = at::empty_like(sv[0]), gt_ = at::empty_like(sv[1]), gl = at::empty_like(sv[2]), gbg;
-        if (d.no_mask) gbg = at::empty_like(sv[3]);
-        at::Tensor ga = at::empty_like(sv[4]), ge = at::empty_like(sv[5]), gd = at::empty_like(sv[6]), gb = at::empty_like(sv[7]);
-        MMRenderGrads gr;
-        gr.grad_rgba = fptr(grgba); gr.grad_face_normals = fptr(gfn); gr.grad_vertices = mptr(gv); gr.grad_textures = mptr(gt_);
-        gr.grad_lights = mptr(gl); gr.grad_bg = mptr(gbg); gr.grad_azimuths = mptr(ga); gr.grad_elevations = mptr(ge); gr.grad_distances = mptr(gd);
-        gr.grad_biases = mptr(gb);
-        const int64_t stream = current_stream(dev);
-        check(((views_bwd_t)ctx->saved_data["f_bwd"].toInt())(&vd, &gr, (void*)stream), "mm_render_views_backward");
-        if (const int64_t f_status = ctx->saved_data["f_status"].toInt()) {      // DiffRender.check_texture_records (synchronises): per IMAGE, as in render
-            std::vector<int32_t> dropped((size_t)BN);
-            const size_t head = (size_t)ctx->saved_data["staging_bytes"].toInt();
-            MMRenderDesc rd = d;                                     // the render workspace of the B*N images inside the multi-view workspace
-            rd.workspace = (char*)d.workspace + head; rd.workspace_bytes = d.workspace_bytes - head;
-            const int st = ((render_status_t)f_status)(&rd, (void*)stream, dropped.data());
-            std::string list;
-            bool any = false;
-            for (int32_t n : dropped) { list += (list.empty() ? "" : ", ") + std::to_string(n); any = any || n != 0; }
-            TORCH_CHECK(!(st == MM_ERR_WORKSPACE && any), "mm_render_views_backward: the texture-record pool overflowed (records dropped per image: [", list,
-                        "]); the texture gradients of those samples are NaN. Raise DiffRender.extra_texture_records_per_pixel.");
-            check(st, "mm_render_status");
-        }
+        RenderGrads gr(in, d.no_mask, grgba, gfn);
+        void* stream = current_stream(dev);
+        const MMRenderViewsDesc vd{d, (int32_t)N};
+        check(((views_bwd_t)ctx->saved_data["f_bwd"].toInt())(&vd, &gr.abi, stream), "mm_render_views_backward");
+        // per IMAGE, as in render: the render workspace of the B*N images lies behind the staging head of the multi-view workspace
+        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, BN, (size_t)ctx->saved_data["staging_bytes"].toInt(),
+                              "mm_render_views_backward", "samples");
+        restore_camera_shapes(ctx, gr);
         // one entry per forward argument: seven non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, want_imnormal
-        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gv, gt_, gl, gbg,
-                ga.reshape(ctx->saved_data["shape_a"].toIntVector()), ge.reshape(ctx->saved_data["shape_e"].toIntVector()),
-                gd.reshape(ctx->saved_data["shape_d"].toIntVector()), gb.reshape(ctx->saved_data["shape_b"].toIntVector()), at::Tensor()};
+        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr.vertices, gr.textures, gr.lights, gr.bg,
+                gr.azimuths, gr.elevations, gr.distances, gr.biases, at::Tensor()};
     }
 };
 
 tensor_list render_views_node(int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t views, int64_t ws_bytes, int64_t staging_bytes,
-                              at::Tensor vertices,
-                              at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths, at::Tensor elevations,
-                              at::Tensor distances, at::Tensor biases, bool want_imnormal) {
+                              at::Tensor vertices, at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths,
+                              at::Tensor elevations, at::Tensor distances, at::Tensor biases, bool want_imnormal) {
     return RenderViewsNode::apply(f_fwd, f_bwd, f_status, proto, views, ws_bytes, staging_bytes, vertices, textures, lights, bg, azimuths, elevations, distances, biases,
                                   want_imnormal);
 }
@@ -518,10 +521,7 @@ tensor_list render_node(int64_t f_fwd, int64_t f_loss, int64_t f_bwd, int64_t f_
     tensor_list out = RenderNode::apply(f_fwd, f_loss, f_bwd, f_status, proto, ws_bytes, vertices, textures, lights, bg, azimuths, elevations, distances,
                                         biases, gt, want_imnormal, image_weight, defer);
     if (defer && out.size() > 4) {
-        std::shared_ptr<Mailbox> mb;
-        { std::lock_guard<std::mutex> lock(g_mail_mutex);
-          auto it = g_mail.find(out[0].data_ptr());
-          if (it != g_mail.end()) mb = it->second.lock(); }
+        auto mb = find_mailbox(out[0].data_ptr());
         if (mb && out[0].grad_fn() && out[4].grad_fn().get() == out[0].grad_fn().get() && out[4].output_nr() == 4) {
             mb->node = out[0].grad_fn().get(); mb->version = out[0]._version();
         } else if (mb) mb->claimed = true;                       // nothing requires grad: no backward will ever run, nothing to defer
@@ -534,10 +534,7 @@ tensor_list render_node(int64_t f_fwd, int64_t f_loss, int64_t f_bwd, int64_t f_
 // seen as (B,4,H,W)) output 0 of a render node that handed out a token, float32, never modified in place since, not yet taken by another recon_data.
 std::shared_ptr<Mailbox> deferrable_render(const at::Tensor& pred) {
     if (!pred.defined() || !pred.is_cuda() || pred.scalar_type() != at::kFloat || pred.dim() != 4 || !pred.requires_grad() || !at::GradMode::is_enabled()) return nullptr;
-    std::shared_ptr<Mailbox> mb;
-    { std::lock_guard<std::mutex> lock(g_mail_mutex);
-      auto it = g_mail.find(pred.data_ptr());
-      if (it != g_mail.end()) mb = it->second.lock(); }
+    auto mb = find_mailbox(pred.data_ptr());
     if (!mb || mb->claimed || !mb->node || !mb->has_token) return nullptr;
     if (pred.size(0) != mb->B || pred.size(1) != 4 || pred.size(2) != mb->H || pred.size(3) != mb->W) return nullptr;
     if (pred.stride(0) != 4 * mb->H * mb->W || pred.stride(1) != 1 || pred.stride(2) != 4 * mb->W || pred.stride(3) != 4) return nullptr;

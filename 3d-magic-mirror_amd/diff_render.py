@@ -193,6 +193,12 @@ class DiffRender(object):
         d.rgba, d.face_idx, d.face_normals, d.imnormal = dp(rgba), dp(face_idx), dp(fn), dp(imn)
         return d
 
+    def _set_outputs(self, attributes, fn, imn, face_idx):
+        """What every render leaves beside its image: the two attributes networks.py:319-320 sets, and the face index map."""
+        attributes['face_normals'] = fn
+        attributes['imnormal'] = imn if self.emit_imnormal else None
+        self.last_face_idx = face_idx                   # kaolin returns it from dibr_rasterization; the reference drops it
+
     # ---- networks.py:258-324 -------------------------------------------------------------------------------------
     def render(self, no_mask=False, **attributes):
         azimuths = attributes['azimuths']
@@ -205,11 +211,8 @@ class DiffRender(object):
         lights = attributes['lights']
         rgba, fn, imn, face_idx = self._render_node(bool(no_mask), None, vertices, textures, lights, bg if no_mask else None,
                                                     azimuths, elevations, distances, biases)
-        rgbs = rgba.permute(0, 3, 1, 2)                 # (B,4,H,W) view of NHWC memory, like networks.py:317
-        attributes['face_normals'] = fn
-        attributes['imnormal'] = imn if self.emit_imnormal else None
-        self.last_face_idx = face_idx                   # kaolin returns it from dibr_rasterization; the reference drops it
-        return rgbs, attributes
+        self._set_outputs(attributes, fn, imn, face_idx)
+        return rgba.permute(0, 3, 1, 2), attributes     # (B,4,H,W) view of NHWC memory, like networks.py:317
 
     # ---- the same samples under several cameras (trainer.py:280-289,347 Ae / Ae90; :710-723 evaluation; :619-671 turntables) ----
     def _view_cameras(self, attributes):
@@ -276,9 +279,7 @@ class DiffRender(object):
             N.fn_addr("mm_render_views_forward"), N.fn_addr("mm_render_views_backward"),
             N.fn_addr("mm_render_status") if self.check_texture_records else 0, proto, n, nbytes + staging, staging,
             vertices, textures, lights, bg, azimuths, elevations, distances, biases, bool(self.emit_imnormal))
-        attributes['face_normals'] = fn
-        attributes['imnormal'] = imn if self.emit_imnormal else None
-        self.last_face_idx = face_idx
+        self._set_outputs(attributes, fn, imn, face_idx)
         return rgba.permute(0, 1, 4, 2, 3), attributes
 
     def _views_staging_bytes(self, proto, views):
@@ -310,13 +311,11 @@ class DiffRender(object):
                for k in keys}
         rgba, fn, imn, face_idx = self._render_node(bool(no_mask), None, cat['vertices'], cat['textures'], cat['lights'], cat.get('bg'),
                                                     cat['azimuths'], cat['elevations'], cat['distances'], cat['biases'])
-        self.last_face_idx = face_idx
         rgba_p = _SplitBatchFn.apply(rgba, *sizes) if len(sets) > 1 else (rgba,)
         fn_p = _SplitBatchFn.apply(fn, *sizes) if len(sets) > 1 else (fn,)
         out, o = [], 0
         for a, n, r, f in zip(sets, sizes, rgba_p, fn_p):
-            a['face_normals'] = f
-            a['imnormal'] = imn[o:o + n] if self.emit_imnormal else None
+            self._set_outputs(a, f, imn[o:o + n], face_idx)       # (last_face_idx: the whole batch's)
             out.append((r.permute(0, 3, 1, 2), a))
             o += n
         return out
@@ -356,9 +355,7 @@ class DiffRender(object):
         rgba, fn, imn, face_idx, loss = self._render_node(bool(no_mask), gt_data, a['vertices'], a['textures'], a['lights'],
                                                           a['bg'] if no_mask else None, a['azimuths'], a['elevations'], a['distances'], a['biases'],
                                                           contour)
-        attributes['face_normals'] = fn
-        attributes['imnormal'] = imn if self.emit_imnormal else None
-        self.last_face_idx = face_idx
+        self._set_outputs(attributes, fn, imn, face_idx)
         return loss, rgba.permute(0, 3, 1, 2), attributes
 
     # ---- networks.py:364-390 -------------------------------------------------------------------------------------

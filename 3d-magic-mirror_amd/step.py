@@ -118,10 +118,14 @@ class RenderLossStep:
         if self.fused:
             d.fused_gt = N.ptr(self.gt)
 
+    def _stream(self, stream):
+        """``stream`` (a torch.cuda.Stream; None: this device's current stream) as the C ABI's stream argument."""
+        return ctypes.c_void_p((stream or torch.cuda.current_stream(self.dev)).cuda_stream)
+
     def run(self, stream=None):
         """Enqueue one full step on ``stream`` (a torch.cuda.Stream; default: the current stream)."""
         L = N.lib()
-        s = ctypes.c_void_p((stream or torch.cuda.current_stream(self.dev)).cuda_stream)
+        s = self._stream(stream)
         N.check(L.mm_render_forward(ctypes.byref(self.d), s), "mm_render_forward")
         if not self.fused:
             N.check(L.mm_recon_data_forward(ctypes.byref(self.r), s), "mm_recon_data_forward")
@@ -134,7 +138,7 @@ class RenderLossStep:
         if self.fused or self.r.contour > 0:
             raise RuntimeError("run_deferred is the un-fused step without the contour term")
         L = N.lib()
-        s = ctypes.c_void_p((stream or torch.cuda.current_stream(self.dev)).cuda_stream)
+        s = self._stream(stream)
         N.check(L.mm_render_forward(ctypes.byref(self.d), s), "mm_render_forward")
         N.check(L.mm_recon_data_forward(ctypes.byref(self.r), s), "mm_recon_data_forward")
         d = self.render_desc()
@@ -157,7 +161,7 @@ class RenderLossStep:
     def run_forward(self, stream=None):
         """The forward half of run() (fused mode): render + recon_data value, on ``stream``."""
         L = N.lib()
-        s = ctypes.c_void_p((stream or torch.cuda.current_stream(self.dev)).cuda_stream)
+        s = self._stream(stream)
         N.check(L.mm_render_forward(ctypes.byref(self.d), s), "mm_render_forward")
         if self.fused:
             N.check(L.mm_render_fused_loss(ctypes.byref(self.d), s), "mm_render_fused_loss")
@@ -166,7 +170,7 @@ class RenderLossStep:
 
     def run_backward(self, stream=None):
         L = N.lib()
-        s = ctypes.c_void_p((stream or torch.cuda.current_stream(self.dev)).cuda_stream)
+        s = self._stream(stream)
         if not self.fused:
             N.check(L.mm_recon_data_backward(ctypes.byref(self.r), s), "mm_recon_data_backward")
         N.check(L.mm_render_backward(ctypes.byref(self.d), ctypes.byref(self.g), s), "mm_render_backward")
@@ -174,7 +178,7 @@ class RenderLossStep:
     def dropped_records(self, stream=None):
         """Per-image counts of texture-gradient records the last backward had no room for (mm_render_status; synchronises)."""
         out = (ctypes.c_int32 * self.d.B)()
-        N.lib().mm_render_status(ctypes.byref(self.d), ctypes.c_void_p((stream or torch.cuda.current_stream(self.dev)).cuda_stream), out)
+        N.lib().mm_render_status(ctypes.byref(self.d), self._stream(stream), out)
         return list(out)
 
     def capture(self):

@@ -8,6 +8,7 @@ view order in fp32 on the device.  One test anchors the whole against the CPU or
 compare the project with itself."""
 import ctypes
 import os
+import re
 
 import numpy as np
 import pytest
@@ -94,10 +95,10 @@ class Case:
         else:
             assert av["imnormal"] is None and ar["imnormal"] is None
 
-    def check_grads(self, what=""):
-        """the views path's gradients against the replicated path's leaf gradients"""
+    def check_grads(self, what="", keys=None):
+        """the views path's gradients (of `keys`; default: every leaf) against the replicated path's leaf gradients"""
         B, n = self.B, self.n
-        for k in self.leaves():
+        for k in keys or self.leaves():
             got, ref = self.views[k].grad, self.rep[k].grad
             assert got is not None and ref is not None, (what, k)
             ref = ref.reshape((B, n) + tuple(ref.shape[1:]))
@@ -236,6 +237,98 @@ def test_recon_data_on_a_view_slice(pkg, n):
     lr.backward()
     torch.cuda.synchronize()
     case.check_grads("recon_data on a slice")
+
+
+def _overflowing_case(pkg, extra, check):
+    """test_gpu_parity's record-overflow construction as 2 samples x 2 views: every face_uvs entry on the corner shared by four 32x32-texel tiles
+    (four texture-gradient records per covered pixel against room for 9/8 per pixel), the sphere at distance 1.9 in every image"""
+    case = Case(pkg, "sphere", 2, 64, 2, seed=12, knobs=dict(extra_texture_records_per_pixel=extra, check_texture_records=check))
+    Ht, Wt = case.att["textures"].shape[2:]
+    uv = torch.empty_like(case.dr.face_uvs)
+    uv[..., 0] = 32.0 / Wt                                           # texel coordinates (31.5, 31.5)
+    uv[..., 1] = 1.0 - 32.0 / Ht
+    case.dr.face_uvs = uv
+    with torch.no_grad():
+        case.views["distances"].fill_(1.9)
+        case.rep["distances"].fill_(1.9)
+    return case
+
+
+def test_texture_record_pool_overflow_through_render_views(pkg):
+    """The record check of RenderViewsNode's backward, whose render workspace starts behind the staging head of the multi-view workspace: silent
+    NaNs + the status word without the switch, the per-image counts in the message with it, and the replicated render's bits once the pool holds."""
+    B, n = 2, 2
+    case = _overflowing_case(pkg, 0.0, False)
+    w, _ = case.upstream(8)
+    rv, _ = case.dr.render_views(no_mask=True, **case.views)
+    covered = (case.dr.last_face_idx >= 0).float().mean(dim=(2, 3))
+    assert covered.shape == (B, n) and float(covered.min()) > 0.4      # 4 x 0.4 HW records per image against room for 9/8 HW
+    (rv * w).sum().backward()
+    torch.cuda.synchronize()
+    assert torch.isnan(case.views["textures"].grad).all()           # every sample: a NaN of one view's survives the sum over the views
+    assert case.dr.poll_dropped_records(reset=False) > 0
+    with pytest.raises(RuntimeError, match="dropped"):
+        case.dr.render_views(no_mask=True, **{k: v.detach() for k, v in case.views.items()})
+
+    case = _overflowing_case(pkg, 0.0, True)
+    rv, _ = case.dr.render_views(no_mask=True, **case.views)
+    with pytest.raises(RuntimeError, match="texture-record pool") as err:
+        (rv * w).sum().backward()
+    counts = [int(c) for c in re.search(r"\[([^\]]*)\]", str(err.value)).group(1).split(",")]
+    assert len(counts) == B * n and all(c > 0 for c in counts), str(err.value)
+
+    case = _overflowing_case(pkg, 3.0, True)                        # 4 1/8 records per pixel: enough for any image
+    v, r = case.render_both()
+    case.check_forward(v, r)
+    _backward_both(case, v, r, seed=8)
+    case.check_grads("a record pool that holds")
+
+
+def test_only_the_normals_are_differentiated(pkg):
+    """loss = (face_normals * w).sum() alone: the image's gradient arrives undefined at the node, which then differentiates a zero image gradient --
+    vertices and cameras get the replicated render's bits, textures, lights and bg exact zeros; render_geometry, which has no image at all, gives
+    the same bits as that render (test_gpu_parity's geometry-only test compares the two to 1e-6 of the maximum)"""
+    case = Case(pkg, "smpl_uv_642", 2, 64, 3, seed=41)
+    (_, av, _), (_, ar, _) = case.render_both()
+    _, wfn = case.upstream(6)
+    wfn_rep = wfn.reshape(case.B * case.n, -1, 3)
+    (av["face_normals"] * wfn).sum().backward()
+    (ar["face_normals"] * wfn_rep).sum().backward()
+    torch.cuda.synchronize()
+    geometry = ("vertices",) + CAMERAS
+    case.check_grads("normals only", keys=geometry)
+    for k in ("textures", "lights", "bg"):
+        for leaf in (case.views[k], case.rep[k]):
+            assert leaf.grad is not None and leaf.grad.shape == leaf.shape and int(torch.count_nonzero(leaf.grad)) == 0, k
+    geo = {k: case.rep[k].detach().clone().requires_grad_(True) for k in case.rep}
+    out = case.dr.render_geometry(**geo)
+    assert torch.equal(out["face_normals"].detach(), ar["face_normals"].detach())
+    (out["face_normals"] * wfn_rep).sum().backward()
+    torch.cuda.synchronize()
+    for k in geometry:
+        assert torch.equal(geo[k].grad, case.rep[k].grad), (k, float((geo[k].grad - case.rep[k].grad).abs().max()))
+    assert all(geo[k].grad is None for k in ("textures", "lights", "bg"))
+
+
+def test_broadcast_cameras_get_gradients_of_their_own_shapes(pkg):
+    """elevations, distances (B,) and biases (B,2) next to azimuths (B,N): every gradient has its leaf's shape and is, N being 2, the sum over the
+    views of the gradient the same call gives with every camera spelled out as (B,N) / (B,N,2) (two addends: no order to differ in)"""
+    B, n = 3, 2
+    case = Case(pkg, "sphere", B, 64, n, seed=23, only_azimuths=True)
+    assert [tuple(case.views[c].shape) for c in CAMERAS] == [(B, n), (B,), (B,), (B, 2)]
+    full = {k: v.detach().clone().requires_grad_(True) for k, v in case.views.items()}
+    for c in CAMERAS[1:]:
+        t = case.views[c].detach()
+        full[c] = t.unsqueeze(1).expand((B, n) + tuple(t.shape[1:])).contiguous().requires_grad_(True)
+    w, wfn = case.upstream(13)
+    for leaves in (case.views, full):
+        rv, av = case.dr.render_views(no_mask=True, **leaves)
+        ((rv * w).sum() + (av["face_normals"] * wfn).sum()).backward()
+    torch.cuda.synchronize()
+    for k in case.leaves():
+        got, ref = case.views[k].grad, full[k].grad
+        assert got.shape == case.views[k].shape and ref.shape == full[k].shape and float(ref.abs().max()) > 0, k
+        assert torch.equal(got, ref[:, 0] + ref[:, 1] if k in CAMERAS[1:] else ref), k
 
 
 def test_no_host_synchronisation(pkg):
