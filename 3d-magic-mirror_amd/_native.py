@@ -184,6 +184,12 @@ class MMCriticGrads(ctypes.Structure):
     _fields_ = [("g_batch", c_p), ("grad_er90", c_p), ("grad_ir", c_p), ("grad_er90_nhwc", c_i), ("grad_ir_nhwc", c_i)]
 
 
+class MMExportDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("N", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("nhwc", c_i), ("rounding", c_i), ("white", c_i),
+                ("as_float", c_i), ("nrow", c_i), ("padding", c_i), ("pad_value", c_f), ("x", c_p), ("out_rgb", c_p), ("out_mask", c_p),
+                ("out_rgba", c_p), ("out_grid", c_p)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -206,7 +212,7 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward",
            "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
            "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward",
-           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_struct_size",
+           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -302,6 +308,8 @@ def lib():
     L.mm_render_views_backward.argtypes = [P(MMRenderViewsDesc), P(MMRenderGrads), c_p]
     L.mm_critic_inputs_forward.argtypes = [P(MMCriticDesc), c_p]
     L.mm_critic_inputs_backward.argtypes = [P(MMCriticDesc), P(MMCriticGrads), c_p]
+    L.mm_export_images.argtypes = [P(MMExportDesc), c_p]
+    L.mm_export_grid.argtypes = [P(MMExportDesc), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -316,7 +324,7 @@ def lib():
     mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
                MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
-               MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads)
+               MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads, MMExportDesc)
     for i, cls in enumerate(mirrors):
         if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

@@ -43,6 +43,9 @@ int launch_collapse_resample(int B, int V, const float* dv, int* idx_a, int* idx
 int critic_chunks_per_image(const MMCriticDesc*);
 int launch_critic_fwd(const MMCriticDesc*, hipStream_t);
 int launch_critic_bwd(const MMCriticDesc*, const MMCriticGrads*, hipStream_t);
+void export_grid_geometry(const MMExportDesc*, long long* xmaps, long long* pad, long long* Hg, long long* Wg);
+int launch_export_images(const MMExportDesc*, hipStream_t);
+int launch_export_grid(const MMExportDesc*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -560,6 +563,42 @@ int mm_critic_inputs_backward(const MMCriticDesc* d, const MMCriticGrads* g, mm_
     return mm::launch_critic_bwd(d, g, (hipStream_t)stream);
 }
 
+// sizes and modes the two exports share
+static int export_shape(const MMExportDesc* d) {
+    if (d->B <= 0 || d->N <= 0 || d->H <= 0 || d->W <= 0 || (d->C != 3 && d->C != 4)) return MM_ERR_BAD_SHAPE;
+    if (d->C == 3 && (d->white || d->nhwc)) return MM_ERR_BAD_SHAPE;
+    if (d->rounding != 0 && d->rounding != 1) return MM_ERR_BAD_SHAPE;
+    return MM_OK;
+}
+
+int mm_export_images(const MMExportDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    const int st = export_shape(d);
+    if (st != MM_OK) return st;
+    if (!d->out_rgb && !d->out_mask && !d->out_rgba) return MM_ERR_BAD_SHAPE;     // no output requested
+    if (d->C == 3 && (d->out_mask || d->out_rgba)) return MM_ERR_BAD_SHAPE;
+    // groups of 16 pixels are counted in an int32
+    const long long images = (long long)d->B * d->N, HW = (long long)d->H * d->W;
+    if (images > (0x7fffffffLL * 16) / HW) return MM_ERR_UNSUPPORTED;
+    if (!d->x) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_export_images(d, (hipStream_t)stream);
+}
+
+int mm_export_grid(const MMExportDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    const int st = export_shape(d);
+    if (st != MM_OK) return st;
+    if (d->nrow < 1 || d->padding < 0) return MM_ERR_BAD_SHAPE;
+    long long xmaps, pad, Hg, Wg;
+    mm::export_grid_geometry(d, &xmaps, &pad, &Hg, &Wg);
+    const long long chunks = 0x7fffffffLL - 32;                   // 16-byte chunks of the sheets, and 32 items for the bytes around them
+    if (Hg > 0x7fffffffLL || Wg > 0x7fffffffLL || Hg > chunks * 16 / 3 / Wg || (long long)d->N > chunks * 16 / 3 / (Hg * Wg)) return MM_ERR_UNSUPPORTED;
+    if (!d->x || !d->out_grid) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_export_grid(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -630,7 +669,7 @@ size_t mm_struct_size(int which) {
         case 18: return sizeof(MMSsimDesc);     case 19: return sizeof(MMSsimGrads);    case 20: return sizeof(MMShapeFeatDesc);
         case 21: return sizeof(MMShapeFeatGrads); case 22: return sizeof(MMCameraFeatDesc); case 23: return sizeof(MMCameraFeatGrads);
         case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);  case 26: return sizeof(MMRenderViewsDesc);
-        case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);
+        case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);  case 29: return sizeof(MMExportDesc);
         default: return 0;
     }
 }

@@ -140,7 +140,7 @@ class TrainerStep:
         images.  Pays where a batch of 48 does not fill the chip (128x128); at 256x256 one pass over 144 images takes as long as three over 48
         and the concatenations cost more than the launches saved (profiles/r04_render_path.md).
         fused_critic: the stand-in critic's batch from critic_inputs (one launch each way, the renders' NHWC memory read as it is) instead of
-        torch.cat over two channel slices -- same values, same gradients."""
+        torch.cat over two channel slices -- same values, handed to the critic in the cat's channels-last memory format, so same losses too."""
         self.opt = opt or default_opt()
         self.dev, self.B = device, batch
         self.lean = bool(lean)                                   # render #4 geometry-only
@@ -206,7 +206,11 @@ class TrainerStep:
         else:
             _, Aire = self._render(3, Aire)                                                # render #4 (face_normals only)
         if self.fused_critic:
-            outs = self.critic(critic_inputs(self.Xa, Xer90, Xir, unmask=1, gp=False).g_batch)
+            # the batch in the memory format the cat below gives its own (channels-last, the renders'): the critic's convolutions are then
+            # the SAME MIOpen problem on the same values in both paths.  Fed NCHW, they are another problem, MIOpen may solve it with
+            # another kernel, and whether the two kernels round alike depends on which ones a given machine picks.
+            g_batch = critic_inputs(self.Xa, Xer90, Xir, unmask=1, gp=False).g_batch
+            outs = self.critic(g_batch.contiguous(memory_format=torch.channels_last))
         else:
             outs = self.critic(torch.cat((Xer90[:, :3], Xir[:, :3]), 0))
         o1, o2 = torch.split(outs, Bn, 0)

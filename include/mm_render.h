@@ -704,6 +704,42 @@ int mm_critic_inputs_forward(const MMCriticDesc* desc, mm_stream_t stream);
 int mm_critic_inputs_backward(const MMCriticDesc* desc, const MMCriticGrads* grads, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Export: float renders to 8-bit pixels on the device (what the reference's evaluation code does on the host: to_pil_image,
+ * make_grid + permute + (image * 255).astype(uint8), save_image; trainer.py:546-769).  The quantiser, every step rounded in fp32:
+ *   rounding 0 (trunc):   q = fl(x * 255)               -- pic.mul(255).byte(), (image * 255.0).astype(np.uint8)
+ *   rounding 1 (nearest): q = fl(fl(x * 255) + 0.5)     -- save_image
+ * then NaN -> 0, clamp to [0, 255], convert toward zero.  For x outside [0, 1] the reference's cast is undefined; this one SATURATES.
+ * white (C = 4 only) first composes the pixel over white with its own alpha: x_c <- fl(fl(x_c * m) + fl(1 - m)), m = x_3.
+ * The input is B * N images of (C,H,W) fp32, C 3 or 4, image b * N + n after image b * N + n - 1: NCHW-contiguous (nhwc 0) or, for
+ * C = 4, NHWC-dense (nhwc 1: what mm_render_forward and mm_render_views_forward write).
+ * mm_export_images writes any subset of out_rgb (B*N,H,W,3), out_mask (B*N,H,W) -- channel 3 --, out_rgba (B*N,H,W,4) as bytes in one
+ * launch from one read of each pixel; with as_float the same quantised values as fp32 fl(float(q) / 255) in planes: (B*N,3,H,W),
+ * (B*N,H,W), (B*N,4,H,W).  mm_export_grid writes out_grid (N,Hg,Wg,3) bytes, frame n = torchvision's
+ * make_grid(x[:, n, :3], nrow, padding, pad_value) in HWC, all frames in one launch: for B = 1 the image itself (Hg = H, Wg = W),
+ * otherwise xmaps = min(nrow, B), ymaps = ceil(B / xmaps), Hg = (H + padding) * ymaps + padding, Wg = (W + padding) * xmaps + padding,
+ * image k = y * xmaps + x at rows [y * (H + padding) + padding, ... + H) and columns [x * (W + padding) + padding, ... + W), every
+ * other byte (the empty cells of a short last row too) the quantised pad_value.
+ * No atomics, no workspace, no host synchronisation; bitwise reproducible.  16-byte aligned pointers move 16 bytes per access.  The
+ * 16-byte chunks of an output are counted in an int32 (MM_ERR_UNSUPPORTED otherwise).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct MMExportDesc {
+    int32_t B, N, C, H, W;          /* B * N images; grid mode: B cells per frame, N frames */
+    int32_t nhwc;                   /* layout flag of x; 1 needs C = 4 (MM_ERR_BAD_SHAPE otherwise) */
+    int32_t rounding;               /* 0 trunc, 1 nearest (MM_ERR_BAD_SHAPE otherwise) */
+    int32_t white;                  /* compose over white first; needs C = 4 */
+    int32_t as_float;               /* mm_export_images only: fp32 planes instead of bytes */
+    int32_t nrow, padding;          /* mm_export_grid only: nrow >= 1, padding >= 0 */
+    float pad_value;                /* mm_export_grid only */
+    const float* x;
+    void* out_rgb;                  /* mm_export_images: each NULL or an output; at least one */
+    void* out_mask;                 /* needs C = 4 */
+    void* out_rgba;                 /* needs C = 4 */
+    uint8_t* out_grid;              /* mm_export_grid */
+} MMExportDesc;
+int mm_export_images(const MMExportDesc* desc, mm_stream_t stream);
+int mm_export_grid(const MMExportDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -726,7 +762,8 @@ const char* mm_last_error_detail(void);
  * 5 MMAttLossDesc, 6 MMAttLossGrads, 7 MMTexFlowDesc, 8 MMTexFlowGrads, 9 MMPrepareDesc, 10 MMPrepareGrads, 11 MMDibrDesc,
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
- * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads. */
+ * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
+ * 29 MMExportDesc. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -737,7 +774,8 @@ size_t mm_struct_size(int which);
  * mm_attribute_mix_*, struct ids 24 and 25, which only add -- no existing struct, field or meaning changes; a binding detects them by
  * mm_struct_size(24) != 0; still 9: MMRenderViewsDesc and mm_render_views_*, struct id 26, additions again -- MMRenderDesc and
  * MMRenderGrads keep their layout and meaning; still 9: MMCriticDesc / Grads and mm_critic_inputs_forward / _backward, struct ids 27 and 28,
- * additions once more; a binding detects them by mm_struct_size(27) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * additions once more; a binding detects them by mm_struct_size(27) != 0; still 9: MMExportDesc and mm_export_images / mm_export_grid,
+ * struct id 29, an addition too, detected by mm_struct_size(29) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
