@@ -26,7 +26,7 @@ class MMRenderDesc(ctypes.Structure):
                 ("rgba", c_p), ("face_idx", c_p), ("face_normals", c_p), ("imnormal", c_p),
                 ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t), ("prof_events", c_p),
                 ("fused_gt", c_p), ("fused_image_weight", c_f), ("fused_loss", c_p), ("fused_grad_loss", c_p),
-                ("options", c_i), ("geometry_only", c_i), ("status_flag", c_p), ("fused_contour", c_f), ("fused_totals", c_p)]
+                ("options", c_i), ("geometry_only", c_i), ("status_flag", c_p), ("fused_contour", c_f), ("fused_totals", c_p), ("step_grads", c_p)]
 
 
 class MMRenderGrads(ctypes.Structure):
@@ -199,7 +199,7 @@ OPT_WALK_QUEUE, OPT_WALK_BATCH = 1 << 10, 1 << 11
 OPT_MANY_IN_FLIGHT = 1 << 12          # hint: several independent calls in flight (identical results; include/mm_render.h)
 PROF_RECON = ("recon_partial", "recon_final", "recon_bwd", "recon_contour")
 
-EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_render_status", "mm_render_fused_loss", "mm_debug_workspace_layout", "mm_recon_query_workspace",
+EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_render_status", "mm_render_fused_loss", "mm_render_step_mode", "mm_debug_step_layout", "mm_debug_workspace_layout", "mm_recon_query_workspace",
            "mm_recon_data_forward", "mm_recon_data_backward", "mm_recon_data_totals", "mm_build_vertex_corner_csr", "mm_build_vertex_corner_csr_device", "mm_build_vertex_corner_table", "mm_nearest_neighbour", "mm_chamfer_nearest", "mm_chamfer_backward", "mm_status_string", "mm_last_error_detail",
            "mm_mesh_reg_query_workspace", "mm_mesh_reg_forward", "mm_mesh_reg_backward", "mm_texture_flow_forward",
            "mm_texture_flow_backward", "mm_attribute_loss_query_workspace", "mm_attribute_loss_forward",
@@ -246,6 +246,8 @@ def lib():
     L.mm_render_forward.argtypes = [ctypes.POINTER(MMRenderDesc), c_p]
     L.mm_render_backward.argtypes = [ctypes.POINTER(MMRenderDesc), ctypes.POINTER(MMRenderGrads), c_p]
     L.mm_render_fused_loss.argtypes = [ctypes.POINTER(MMRenderDesc), c_p]
+    L.mm_render_step_mode.argtypes = [ctypes.POINTER(MMRenderDesc)]
+    L.mm_debug_step_layout.argtypes = [ctypes.POINTER(MMRenderDesc), ctypes.POINTER(ctypes.c_size_t)]
     L.mm_render_status.argtypes = [ctypes.POINTER(MMRenderDesc), c_p, ctypes.POINTER(ctypes.c_int32)]
     L.mm_recon_query_workspace.restype = ctypes.c_size_t
     L.mm_recon_query_workspace.argtypes = [ctypes.POINTER(MMReconDesc)]

@@ -81,13 +81,13 @@ extern "C" {
 
 size_t mm_query_workspace(const MMRenderDesc* d) {
     if (!d || d->B <= 0 || d->V <= 0 || d->F <= 0 || d->H <= 0 || d->W <= 0 || d->Ht <= 0 || d->Wt <= 0) return 0;
-    return mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, 0, d->geometry_only != 0).bytes;
+    return mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, 0, d->geometry_only != 0, d->step_grads != nullptr).bytes;
 }
 
 int mm_render_forward(const MMRenderDesc* d, mm_stream_t stream) {
     int st = check_render(d, false);
     if (st != MM_OK) return st;
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0);
+    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
     hipStream_t s = (hipStream_t)stream;
     mm::clear_stale_error();
     st = mm::launch_vertex_fwd(d, w, s);
@@ -99,18 +99,32 @@ int mm_render_fused_loss(const MMRenderDesc* d, mm_stream_t stream) {
     int st = check_render(d, false);
     if (st != MM_OK) return st;
     if (!d->fused_gt || !d->fused_loss) return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0);
+    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
     mm::clear_stale_error();
     return mm::launch_fused_loss(d, w, (hipStream_t)stream);
 }
 
 int mm_debug_workspace_layout(const MMRenderDesc* d, size_t* out5) {
     if (!d || !out5) return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt);
+    const mm::Workspace w = mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, 0, false, d->step_grads != nullptr);
     out5[0] = (size_t)((char*)w.chunkmap - (char*)nullptr); out5[1] = (size_t)((char*)w.items - (char*)nullptr);
     out5[2] = (size_t)((char*)w.nitems - (char*)nullptr); out5[3] = (size_t)((char*)w.part - (char*)nullptr); out5[4] = (size_t)w.item_cap;
     out5[5] = (size_t)((char*)w.gp - (char*)nullptr); out5[6] = (size_t)((char*)w.gp2 - (char*)nullptr); out5[7] = (size_t)((char*)w.soft - (char*)nullptr);
     out5[8] = (size_t)((char*)w.tcnt - (char*)nullptr); out5[9] = (size_t)w.ntiles; out5[10] = (size_t)w.trcap; out5[11] = (size_t)((char*)w.trcnt - (char*)nullptr);
+    return MM_OK;
+}
+
+int mm_render_step_mode(const MMRenderDesc* d) {
+    if (!d || d->B <= 0 || d->V <= 0 || d->F <= 0 || d->H <= 0 || d->W <= 0 || d->Ht <= 0 || d->Wt <= 0) return 0;
+    const mm::Workspace w = mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, 0, d->geometry_only != 0, d->step_grads != nullptr);
+    return mm::render_step_mode(d, w) ? 1 : 0;
+}
+
+int mm_debug_step_layout(const MMRenderDesc* d, size_t* out4) {
+    if (!d || !out4) return MM_ERR_NULL_POINTER;
+    const mm::Workspace w = mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
+    out4[0] = (size_t)((char*)w.nheavy - (char*)nullptr); out4[1] = (size_t)((char*)w.dl_tile - (char*)nullptr);
+    out4[2] = (size_t)((char*)w.runs - (char*)nullptr); out4[3] = (size_t)w.runcap;
     return MM_OK;
 }
 
@@ -119,7 +133,7 @@ int mm_render_status(const MMRenderDesc* d, mm_stream_t stream, int32_t* dropped
     if (d->B <= 0 || d->V <= 0 || d->F <= 0 || d->H <= 0 || d->W <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
     if (!d->workspace) return MM_ERR_NULL_POINTER;
     if (d->workspace_bytes < mm_query_workspace(d) || ((uintptr_t)d->workspace & 255)) return MM_ERR_BAD_SHAPE;   // (MM_ERR_WORKSPACE is this call's "records were dropped")
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0);
+    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
     std::vector<int32_t> h((size_t)d->B);
     if (hipMemcpyAsync(h.data(), w.tstatus, (size_t)d->B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) return MM_ERR_LAUNCH;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return MM_ERR_LAUNCH;
@@ -132,7 +146,7 @@ int mm_render_backward(const MMRenderDesc* d, const MMRenderGrads* g, mm_stream_
     int st = check_render(d, true);
     if (st != MM_OK) return st;
     if (!g || !g->grad_vertices || !g->grad_azimuths || !g->grad_elevations || !g->grad_distances || !g->grad_biases) return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0);
+    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
     hipStream_t s = (hipStream_t)stream;
     if (d->geometry_only) {                                       // nothing was rasterised: the gradient arrives through face_normals alone
         if (!g->grad_face_normals) return MM_ERR_NULL_POINTER;
@@ -169,6 +183,7 @@ static int check_render_views(const MMRenderViewsDesc* v, bool backward, MMRende
     if (d->fused_gt || d->fused_totals || d->geometry_only) return MM_ERR_UNSUPPORTED;    // fused / deferred losses and geometry-only over views: not built
     if ((size_t)3 * d->Ht * d->Wt > 0x7fffffff || (size_t)3 * d->H * d->W > 0x7fffffff || d->B / v->views > 65535) return MM_ERR_UNSUPPORTED;
     *r = *d;
+    r->step_grads = nullptr;                                     // (step mode is a single-view, fused mode: the field is ignored here)
     if (v->views > 1) {
         const size_t st = views_staging(d).bytes;
         r->workspace = d->workspace ? (char*)d->workspace + st : nullptr;      // (st is a multiple of 256: the alignment is the caller's)

@@ -1,5 +1,5 @@
 // mm_backward.h -- arguments shared by the two translation units of the pixel-stage backward:
-//   mm_pixel_bwd.hip  the pixel-major pass (+ the sweep plan in its grid), compiled like the FORWARD (no contraction, IEEE division): it
+//   mm_pixel_bwd.hip  the pixel-major pass (+ the sweep plan in its grid; not launched in step mode, where raster_fwd's epilogue does both), compiled like the FORWARD (no contraction, IEEE division): it
 //                     recomputes the forward's per-pixel quantities, and a recomputation that rounds differently picks the other bilinear
 //                     cell / the other side of torch.clamp for the rare pixel that sits within an ulp of a cell border or of 0 / 1 -- a
 //                     different (equally valid, but not the reference's) one-sided derivative there, 1e-3 on a vertex gradient when it happens
@@ -7,6 +7,7 @@
 //   mm_backward.hip   the gathers, held to 1e-4 and bound by instruction issue: fma contraction + 2.5-ulp division (a third fewer instructions)
 #pragma once
 #include "mm_device.h"
+#include "mm_plan.h"
 
 namespace mm {
 
@@ -58,7 +59,6 @@ __device__ inline void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#define MM_PLAN_WGS 4              // plan workgroups per image where faces are many (else one), see mm_pixel_bwd.hip
 int launch_pixel_bwd(const BwdArgs& a, const MMRenderDesc* d, hipStream_t s);     // mm_pixel_bwd.hip
 
 }  // namespace mm

@@ -18,6 +18,22 @@
 //         knum silhouette faces give K4; hits are ballot-compacted over the wave and finished by all 64 lanes into INT64 fixed-point per-item
 //         LDS sums; one plain store per item, added up per face in index order by the vertex backward.
 //   Integer adds commute exactly: the whole backward is bitwise reproducible.
+//
+//   STEP MODE (MMRenderDesc.step_grads: the fused loss without its contour term, dL/dloss known before the render, a shape the step kernel
+//   covers -- render_step_mode, mm_raster.hip).  There is no pass 1: raster_fwd's shade epilogue has gone on, from the values it held, into the
+//   pixel pass's arithmetic (step_pixel_pass, mm_raster_common.h; one text with pixel_bwd: mm_pixel_pass.h), and the first workgroups of ITS
+//   grid planned the face sweep.  What the gather finds instead of pixel_bwd's products:
+//     dL/dbg, gp / gp2 of covered pixels      as before, written by the epilogue (nothing is written for uncovered pixels)
+//     dL/dalpha of an uncovered pixel          formed HERE, per K4 hit, as ka * gm + kb * (1 - gm) from the ground-truth mask (loaded in the trip that
+//                                              loads the pixel's soft-mask state) and the image's loss totals (alpha_coef: wave-uniform)
+//     max |K2 number|                          gmax[.][0], integer atomic maxima of the epilogue's waves
+//     max |dL/dalpha|                          from the extremes of gm over the image's uncovered pixels, gmax[.][2..3] (face_sum_scale): the same
+//                                              maximum, hence the same fixed-point scale and the same face sums, bit for bit
+//     texture records                          in RUNS of consecutive slots taken from one cursor per image, listed per image {tile, first, count}:
+//                                              no per-tile counts, no offset scan, nothing to wait for (texture_gather_block_step)
+//     dL/dlights                               one row per screen tile; vertex_bwd adds a block's four as ((t0 + t1) + t2) + t3, pixel_bwd's order
+//   The forward's products are read, not consumed (the vertex backward leaves the counters alone in this mode): a second backward after the same
+//   forward gives the same gradients.  Nothing in step mode polls or spins on another workgroup's output.
 #include "mm_backward.h"
 
 #ifndef MM_ITEM_UNROLL
@@ -124,6 +140,36 @@ __device__ inline int compact_hits(const bool (&own)[MM_SWEEP], const bool (&opn
 }
 
 
+// STEP MODE (MMRenderDesc.step_grads): what the forward's epilogue left instead of pixel_bwd's products (see the head of this file)
+struct StepArgs {
+    const int2* runs; int runcap;                                // (B,runcap) {texture tile << 7 | records, first record}
+    const unsigned long long* rcur;                              // (B) {records taken, runs listed << 32}
+};
+// dL/dalpha of an uncovered pixel = ka * gm + kb * (1 - gm), the coefficients from the image's exact loss totals -- bit for bit what pixel_bwd
+// stores for such a pixel, in THIS translation unit's relaxed arithmetic: nothing here can be contracted differently (the one sum adds to an
+// exact product by 2^-32), and its two IEEE fp32 divisions are taken as the fp64 quotient rounded once more (53 >= 2 * 24 + 2 bits: the double rounding is innocuous, the result is the correctly rounded fp32 quotient).
+struct AlphaCoef { float ka, kb; };
+__device__ inline float div_ieee(float x, float y) { return (float)((double)x / (double)y); }
+__device__ inline AlphaCoef alpha_coef(const BwdArgs& a, int b) {
+MM_FP_EXACT
+    float l1s, up, un;
+    loss_totals(a.ltot, b, l1s, up, un);
+    const float U = un + 1e-10f;
+    const float gs = a.grad_loss ? a.grad_loss[0] : 1.f;
+    AlphaCoef k;
+    k.ka = div_ieee(-gs, (float)a.B * U);
+    k.kb = div_ieee(gs * up, (float)a.B * U * U);
+    return k;
+}
+__device__ inline float alpha_grad(const AlphaCoef& k, float gm) {
+    // (this file is compiled with -ffp-contract=fast, which fuses across statements whatever a pragma says: the two products are made opaque
+    //  to the optimiser, so each is rounded on its own before the sum, as pixel_bwd's translation unit rounds them)
+    float p = k.ka * gm, r = k.kb * (1.f - gm);
+    asm volatile("" : "+v"(p), "+v"(r));
+    return p + r;
+}
+__device__ inline float mask_ord_inv(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o); }
+
 // Fixed-point scale of an image's face sums.  The pixel pass left max |K2 number| and max |dL/dalpha| of the image (gmax); a K4
 // contribution is bounded by |dL/dalpha| * mult * sqrt(2 sigma' / e), sigma' = sigmainv / mult^2 (the maximum of d exp(-sigma' d^2)
 // times the constant factors of Appendix A.2).  A sum belongs to ONE sweep item and takes at most one contribution per pixel of the
@@ -131,13 +177,20 @@ __device__ inline int compact_hits(const bool (&own)[MM_SWEEP], const bool (&opn
 // L = ceil(log2 chunk_px), so that 2^L of them fit a 63-bit sum -- 2^55 for the usual 128-pixel chunk, i.e. the unit is 2^-55 of the
 // bound (rounds 2-5 placed it at 2^40 whatever the chunk, room for a 2048 x 2048 chunk nobody cuts: contributions below 2^-41 of the
 // bound were rounded to zero, which randomised cases with saturated silhouettes kept finding -- r06 seed 8809 case 254).
-__device__ inline float face_sum_scale(const BwdArgs& a, int b, int chunk_px, float& inv) {
+// Step mode: no pass left max |dL/dalpha|; ka * gm + kb * (1 - gm) is monotone in gm, also after its four roundings (both terms fall, or
+// both rise, with gm), so the maximum over the image's uncovered pixels is attained at their smallest or largest gm, which the epilogue kept:
+// the same maximum, the same scale, the same face sums as with pixel_bwd.
+template <bool kStep>
+__device__ inline float face_sum_scale(const BwdArgs& a, int b, int chunk_px, float& inv, const AlphaCoef& kc) {
     float m2 = 0.f, m4 = 0.f;
+    unsigned ghi = 0u, glo = 0u;
 #pragma unroll
     for (int sh = 0; sh < MM_GSHARD; ++sh) {
         m2 = fmaxf(m2, __uint_as_float(a.gmax[((size_t)b * MM_GSHARD + sh) * 8]));
-        m4 = fmaxf(m4, __uint_as_float(a.gmax[((size_t)b * MM_GSHARD + sh) * 8 + 1]));
+        if (!kStep) m4 = fmaxf(m4, __uint_as_float(a.gmax[((size_t)b * MM_GSHARD + sh) * 8 + 1]));
+        else { ghi = max(ghi, a.gmax[((size_t)b * MM_GSHARD + sh) * 8 + 2]); glo = max(glo, a.gmax[((size_t)b * MM_GSHARD + sh) * 8 + 3]); }
     }
+    if (kStep && ghi != 0u) m4 = fmaxf(fabsf(alpha_grad(kc, mask_ord_inv(ghi))), fabsf(alpha_grad(kc, mask_ord_inv(~glo))));
     const float sig = a.sigmainv / (a.mult * a.mult);
     const float M = fmaxf(m2, m4 * a.mult * sqrtf(2.f * sig * 0.36787944f) * 1.0001f);
     if (!(M > 0.f) || !(M < INFINITY)) { inv = 0.f; return 0.f; }
@@ -176,6 +229,39 @@ __device__ inline void tex_accumulate(const BwdArgs& a, int (*s_acc)[MM_TS * MM_
 
 __device__ inline float tex_record_max(const TexRecord& rc) { return fmaxf(fmaxf(fabsf(rc.d0), fabsf(rc.d1)), fabsf(rc.d2)); }
 
+// the tile's texels, once (also where nothing landed: no separate zero-fill of grad_textures); an image that lost records is poisoned and reported
+__device__ inline void texture_tile_store(const BwdArgs& a, int b, int T, int tx0, int ty0, int dropped, float inv, int (*s_acc)[MM_TS * MM_TS]) {
+    const int tid = threadIdx.x;
+    if (dropped != 0) {                                          // the image lost records: its texture gradient is NOT a gradient -- say so in every texel
+        inv = __builtin_nanf("");
+        if (T == 0 && tid == 0) {
+            a.tstatus[b] = dropped;
+            if (a.status_flag) __hip_atomic_fetch_add(a.status_flag, dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (the host may be polling it)
+        }
+    }
+    // write the tile once (also where nothing landed: no separate zero-fill of grad_textures): four texels of a row per thread and store
+    if ((a.Wt & 3) == 0 && (((size_t)a.grad_textures) & 15) == 0) {
+        for (int i = tid; i < 3 * MM_TS * MM_TS / 4; i += 256) {
+            const int c = i / (MM_TS * MM_TS / 4), r = i - c * (MM_TS * MM_TS / 4);
+            const int ly = r / (MM_TS / 4), lx = (r - ly * (MM_TS / 4)) * 4;
+            const int x = tx0 + lx, y = ty0 + ly;
+            if (x < a.Wt && y < a.Ht) {
+                const int4 v = *(const int4*)&s_acc[c][ly * MM_TS + lx];
+                *(float4*)(a.grad_textures + (((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x) =
+                    make_float4((float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv);
+            }
+        }
+    } else {
+        for (int i = tid; i < 3 * MM_TS * MM_TS; i += 256) {
+            const int c = i / (MM_TS * MM_TS), r = i - c * (MM_TS * MM_TS);
+            const int ly = r / MM_TS, lx = r - ly * MM_TS;
+            const int x = tx0 + lx, y = ty0 + ly;
+            if (x < a.Wt && y < a.Ht) a.grad_textures[(((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x] = (float)s_acc[c][r] * inv;
+        }
+    }
+}
+
+
 // 2a. texture gradient: one workgroup per (image, 32x32-texel tile) streams the records the pixel pass appended for the
 //     tile into LDS accumulators and writes every texel of the tile once.
 __device__ inline void texture_gather_block(const BwdArgs& a, int block, int (*s_acc)[MM_TS * MM_TS]) {
@@ -207,39 +293,100 @@ __device__ inline void texture_gather_block(const BwdArgs& a, int block, int (*s
         for (int r = tid; r < nrec; r += 256) tex_accumulate(a, s_acc, recs[r], tx0, ty0, scale);
         __syncthreads();
     }
-    if (dropped != 0) {                                          // the image lost records: its texture gradient is NOT a gradient -- say so in every texel
-        inv = __builtin_nanf("");
-        if (T == 0 && tid == 0) {
-            a.tstatus[b] = dropped;
-            if (a.status_flag) __hip_atomic_fetch_add(a.status_flag, dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (the host may be polling it)
+    texture_tile_store(a, b, T, tx0, ty0, dropped, inv, s_acc);
+}
+
+// 2a in STEP MODE: the tile's records lie in RUNS scattered over the image's array (raster_fwd's step epilogue, mm_raster_common.h).  The
+// workgroup reads the image's run list (a window of MM_RUN_WIN entries at a time: one trip for the shapes step mode covers), keeps its own
+// tile's runs in LDS, prefix-sums their lengths and streams the records exactly as above: the maximum first, then the integer accumulation.
+// Which thread meets which record differs from run to run; maxima and integer sums do not care.
+#define MM_RUN_WIN 512
+struct RunWindow { int off[MM_RUN_WIN]; int start[MM_RUN_WIN + 1]; int n; int wsum[4]; };
+// the runs of tile T among entries [r0, r0 + MM_RUN_WIN) of the list -> w (off, start = prefix of the clipped lengths); returns their records
+__device__ inline int run_window(const BwdArgs& a, const int2* runs, int nrun, int r0, int T, RunWindow& w) {
+    const int tid = threadIdx.x;
+    __syncthreads();                                             // (the previous window has been read)
+    if (tid == 0) w.n = 0;
+    __syncthreads();
+    int2 e[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) { const int r = r0 + u * 256 + tid; e[u] = r < nrun ? runs[r] : make_int2(-1, 0); }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if ((e[u].x >> 7) == T) {
+            const int k = atomicAdd(&w.n, 1);
+            w.off[k] = e[u].y;
+            w.start[k] = max(0, min(e[u].x & 127, a.trcap - e[u].y));     // (the run is cut where the array ends)
         }
     }
-    // write the tile once (also where nothing landed: no separate zero-fill of grad_textures): four texels of a row per thread and store
-    if ((a.Wt & 3) == 0 && (((size_t)a.grad_textures) & 15) == 0) {
-        for (int i = tid; i < 3 * MM_TS * MM_TS / 4; i += 256) {
-            const int c = i / (MM_TS * MM_TS / 4), r = i - c * (MM_TS * MM_TS / 4);
-            const int ly = r / (MM_TS / 4), lx = (r - ly * (MM_TS / 4)) * 4;
-            const int x = tx0 + lx, y = ty0 + ly;
-            if (x < a.Wt && y < a.Ht) {
-                const int4 v = *(const int4*)&s_acc[c][ly * MM_TS + lx];
-                *(float4*)(a.grad_textures + (((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x) =
-                    make_float4((float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv);
-            }
-        }
-    } else {
-        for (int i = tid; i < 3 * MM_TS * MM_TS; i += 256) {
-            const int c = i / (MM_TS * MM_TS), r = i - c * (MM_TS * MM_TS);
-            const int ly = r / MM_TS, lx = r - ly * MM_TS;
-            const int x = tx0 + lx, y = ty0 + ly;
-            if (x < a.Wt && y < a.Ht) a.grad_textures[(((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x] = (float)s_acc[c][r] * inv;
-        }
+    __syncthreads();
+    const int n = w.n;
+    // exclusive scan of the lengths in place: two entries per thread, wave scan, the four wave totals through LDS
+    const int l0 = 2 * tid < n ? w.start[2 * tid] : 0, l1 = 2 * tid + 1 < n ? w.start[2 * tid + 1] : 0;
+    int tot;
+    int ex = wave_prefix_excl(l0 + l1, tid & 63, tot);
+    if ((tid & 63) == 0) w.wsum[tid >> 6] = tot;
+    __syncthreads();
+    for (int k = 0; k < (tid >> 6); ++k) ex += w.wsum[k];
+    if (2 * tid < n) w.start[2 * tid] = ex;
+    if (2 * tid + 1 < n) w.start[2 * tid + 1] = ex + l0;
+    const int total = ((w.wsum[0] + w.wsum[1]) + w.wsum[2]) + w.wsum[3];
+    if (tid == 0) w.start[n] = total;
+    __syncthreads();
+    return total;
+}
+// record #i of the window: its run by bisection of the prefix (n <= 512: nine LDS reads)
+__device__ inline int run_record(const RunWindow& w, int i) {
+    int lo = 0, hi = w.n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (w.start[mid] <= i) lo = mid; else hi = mid - 1; }
+    return w.off[lo] + (i - w.start[lo]);
+}
+__device__ inline void texture_gather_block_step(const BwdArgs& a, const StepArgs& sa, int block, int (*s_acc)[MM_TS * MM_TS]) {
+    __shared__ float s_max[4];
+    __shared__ RunWindow s_win;
+    const int ntiles = a.ntx * a.nty;
+    int b, T;
+    map_block(block, a.B, ntiles, b, T);
+    const int tid = threadIdx.x;
+    const int tx0 = (T % a.ntx) * MM_TS, ty0 = (T / a.ntx) * MM_TS;
+    const int nrun = min((int)(sa.rcur[b] >> 32), sa.runcap);
+    const int dropped = a.tdrop[b];                              // records of the image its array (or run list) had no room for (raster_fwd)
+    const int2* runs = sa.runs + (size_t)b * sa.runcap;
+    const TexRecord* recs = a.trec + (size_t)b * a.trcap;
+    float mx = 0.f;
+    int nrec = 0, total = 0;
+    for (int r0 = 0; r0 < nrun; r0 += MM_RUN_WIN) {
+        total = run_window(a, runs, nrun, r0, T, s_win);
+        nrec += total;
+        for (int i = tid; i < total; i += 256) mx = fmaxf(mx, tex_record_max(recs[run_record(s_win, i)]));
     }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) s_max[tid >> 6] = mx;
+    for (int i = tid; i < 3 * MM_TS * MM_TS / 4; i += 256) ((int4*)&s_acc[0][0])[i] = make_int4(0, 0, 0, 0);   // (16-byte LDS stores)
+    __syncthreads();
+    mx = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    float inv = 0.f;
+    if (mx > 0.f && mx < INFINITY) {                             // workgroup-uniform; nothing to add up otherwise (about half of all tiles)
+        int e;
+        (void)frexpf((float)nrec * mx, &e);                      // records * max < 2^e
+        const int k2 = min(max(30 - e, -100), 120);
+        const float scale = ldexpf(1.f, k2);
+        inv = ldexpf(1.f, -k2);
+        for (int r0 = 0; r0 < nrun; r0 += MM_RUN_WIN) {
+            if (nrun > MM_RUN_WIN) total = run_window(a, runs, nrun, r0, T, s_win);   // (one window: it is still in LDS)
+            for (int i = tid; i < total; i += 256) tex_accumulate(a, s_acc, recs[run_record(s_win, i)], tx0, ty0, scale);
+        }
+        __syncthreads();
+    }
+    texture_tile_store(a, b, T, tx0, ty0, dropped, inv, s_acc);
 }
 
 struct ItemLoad { float4 q0, q1; float q2, sq; int lf, px, py, g; bool owned, live; };
 
 // one compacted hit of the sweep, its loads done: owned pixel -> add the pixel pass's nine K2 numbers; open pixel -> K4 (Appendix A.2)
-__device__ inline void item_finish(const BwdArgs& a, FaceSlot& fs, const ItemLoad& ld, float s2, float scale) {
+// kStep: an open pixel's q2 is its ground-truth mask, and dL/dalpha is formed here (kc: the image's coefficients)
+template <bool kStep>
+__device__ inline void item_finish(const BwdArgs& a, FaceSlot& fs, const ItemLoad& ld, float s2, float scale, const AlphaCoef& kc) {
     if (ld.owned) {
         const float4 q0 = ld.q0, q1 = ld.q1;
         fixed_add(&fs.acc[0], q0.x, scale); fixed_add(&fs.acc[1], q0.y, scale); fixed_add(&fs.acc[2], q0.z, scale);
@@ -247,7 +394,7 @@ __device__ inline void item_finish(const BwdArgs& a, FaceSlot& fs, const ItemLoa
         fixed_add(&fs.acc[6], q1.z, scale); fixed_add(&fs.acc[7], q1.w, scale); fixed_add(&fs.acc[8], ld.q2, scale);
         return;
     }
-    const float ga = ld.q2, sq = ld.sq;                           // uncovered pixels: the pixel pass left dL/dalpha here
+    const float ga = kStep ? alpha_grad(kc, ld.q2) : ld.q2, sq = ld.sq;   // uncovered pixels: the pixel pass left dL/dalpha here
     const float x0 = pixel_x_k(ld.px, a.W, a.kx), y0 = pixel_y_k(ld.py, a.H, a.ky);      // (the forward's centres, bit for bit; no division per item)
     const int bm = box_mode(a.options);
     const bool inbox = bm ? !(box_reject(x0, fs.box[0] - a.infl, fs.box[2] + a.infl, bm) || box_reject(y0, fs.box[1] - a.infl, fs.box[3] + a.infl, bm))
@@ -284,8 +431,8 @@ __device__ inline void item_finish(const BwdArgs& a, FaceSlot& fs, const ItemLoa
 //     gradient, uncovered pixels that hold it among their first knum soft-mask faces give K4.  The hits of a trip are
 //     ballot-compacted over the whole wave and finished by all 64 lanes (one round of loads per trip) into the per-face
 //     fixed-point LDS sums.  This lane's face is `f` of image `b`, and its group sweeps box pixels [lo, hi) of it.
-template <int FL>
-__device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, int f, int lane, const FaceBox& fb, int lo, int hi, float scale) {
+template <int FL, bool kStep>
+__device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, int f, int lane, const FaceBox& fb, int lo, int hi, float scale, const AlphaCoef& kc) {
     const int grp = lane / FL, sl = lane % FL;
     const size_t hw = (size_t)a.H * a.W;
     const float s2 = a.mult * a.mult;
@@ -343,7 +490,9 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
                 ld[u].owned = (it & 0x8000u) != 0;
                 ld[u].q0 = make_float4(0.f, 0.f, 0.f, 0.f); ld[u].q1 = ld[u].q0; ld[u].sq = 0.f; ld[u].lf = 0; ld[u].q2 = 0.f;
                 if (ld[u].live) {
-                    ld[u].q2 = a.gp2[pix];
+                    // (step mode: the mask plane of the image's ground truth stands in for the dL/dalpha the pixel pass used to leave in gp2)
+                    if (kStep) ld[u].q2 = ld[u].owned ? a.gp2[pix] : a.gt[((size_t)b * 4 + 3) * hw + (size_t)ld[u].py * a.W + ld[u].px];
+                    else ld[u].q2 = a.gp2[pix];
                     if (ld[u].owned) { ld[u].q0 = a.gp[pix * 2 + 0]; ld[u].q1 = a.gp[pix * 2 + 1]; }
                     else { const float2 sl2 = a.soft[pix]; ld[u].sq = sl2.x; ld[u].lf = __float_as_int(sl2.y); }
                 }
@@ -351,7 +500,7 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
 #pragma unroll
             for (int u = 0; u < MM_ITEM_UNROLL; ++u) {
                 if (u >= 1 && j0 + 64 * u >= n) break;
-                if (ld[u].live) item_finish(a, st->slot[ld[u].g], ld[u], s2, scale);
+                if (ld[u].live) item_finish<kStep>(a, st->slot[ld[u].g], ld[u], s2, scale, kc);
             }
         }
         wave_sync_lds();
@@ -361,7 +510,7 @@ __device__ inline void face_sweep(const BwdArgs& a, SweepStageT<FL>* st, int b, 
 // a wave takes MM_FPW consecutive sweep items of ONE image (consecutive faces, or consecutive chunks of a big face: neighbours on
 // the screen); waves walk the images round-robin.  The item's partial sums go to part[item]; the vertex backward adds the items
 // of a face up.
-template <int FL>
+template <int FL, bool kStep>
 __device__ inline void face_gather_block(const BwdArgs& a, int block, SweepStageT<FL>* s_stage) {
     constexpr int FPW = 64 / FL;                                 // items per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane / FL, sl = lane % FL;
@@ -387,8 +536,10 @@ __device__ inline void face_gather_block(const BwdArgs& a, int block, SweepStage
     const bool front = (a.options & MM_OPT_CULL_STRICT) ? fb.nz > 0.f : fb.nz >= 0.f;
     const int hi = live && (front || !(a.options & MM_OPT_SOFT_SKIP_CULLED)) ? min(fb.npx, lo + ni.y) : lo;
     float inv;
-    const float scale = face_sum_scale(a, b, ni.y, inv);
-    face_sweep(a, st, b, e.x, lane, fb, lo, hi, scale);
+    AlphaCoef kc = {0.f, 0.f};
+    if (kStep) kc = alpha_coef(a, b);                            // (wave-uniform: scalar loads and arithmetic once per wave)
+    const float scale = face_sum_scale<kStep>(a, b, ni.y, inv, kc);
+    face_sweep<FL, kStep>(a, st, b, e.x, lane, fb, lo, hi, scale, kc);
     if (live) for (int k = sl; k < 9; k += FL) a.part[((size_t)b * a.item_cap + item) * 12 + k] = (float)st->slot[grp].acc[k] * inv;
 }
 
@@ -412,8 +563,8 @@ __device__ inline float fused_loss_value(const long long* ltot, int B, int H, in
 #ifndef MM_GATHER_LB
 #define MM_GATHER_LB 8            // waves per SIMD the register allocation is held to (64 VGPRs, no spills)
 #endif
-template <int FL>
-__global__ __launch_bounds__(256, MM_GATHER_LB) void gather_bwd_kernel(BwdArgs a, int ntex) {
+template <int FL, bool kStep>
+__global__ __launch_bounds__(256, MM_GATHER_LB) void gather_bwd_kernel(BwdArgs a, int ntex, StepArgs sa) {
     // the two kinds of workgroup never coexist in one workgroup: their LDS is overlaid (more workgroups per CU)
     constexpr size_t kLds = sizeof(float) * 3 * MM_TS * MM_TS > sizeof(SweepStageT<FL>) * 4 ? sizeof(float) * 3 * MM_TS * MM_TS : sizeof(SweepStageT<FL>) * 4;
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kLds];
@@ -427,8 +578,8 @@ __global__ __launch_bounds__(256, MM_GATHER_LB) void gather_bwd_kernel(BwdArgs a
     //  then the rest of the face grid: 32.1 / 185.4 us against 29.7 / 176.6 at 128x128 B=48 / B=384.)  Measured alternatives (gather_bwd us at configs 2 / 3 / 5; this order 38.5 / 93.6 / 304): faces
     // first 35.9 / 104.4 / 293.5; the two kinds alternating 43.8 / 114.5 / 417 -- a CU that runs both code paths at once loses more than
     // the earlier start of the slowest workgroups gains.
-    if ((int)blockIdx.x < ntex) texture_gather_block(a, blockIdx.x, s_acc);
-    else face_gather_block(a, blockIdx.x - ntex, s_stage);
+    if ((int)blockIdx.x < ntex) { if (kStep) texture_gather_block_step(a, sa, blockIdx.x, s_acc); else texture_gather_block(a, blockIdx.x, s_acc); }
+    else face_gather_block<FL, kStep>(a, blockIdx.x - ntex, s_stage);
 }
 
 // the fused recon_data value on its own (mm_render_fused_loss): the same fixed-order sum over images the gather kernel's last
@@ -467,9 +618,16 @@ int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Works
     a.plan_chunkmap = w.chunkmap; a.plan_items = w.items; a.plan_nitems = w.nitems; a.plan_wgs = d->F > 4096 ? MM_PLAN_WGS : 1;
     a.ntx = (d->Wt + MM_TS - 1) / MM_TS; a.nty = (d->Ht + MM_TS - 1) / MM_TS;
     a.grad_textures = g->grad_textures;
-    // w.tcnt is zero here: cleared by the vertex stage of the forward and again by every vertex backward (no memset launch)
-    launch_pixel_bwd(a, d, s);
-    if (launch_ok("pixel_bwd") != MM_OK) return MM_ERR_LAUNCH;
+    // step mode (MMRenderDesc.step_grads): the forward's epilogue has left everything the pixel pass leaves -- there is no pixel launch, and
+    // the gather reads the run list and forms dL/dalpha itself (the profiling slot stays readable: an empty bracket)
+    const bool step = views == 1 && render_step_mode(d, w);
+    const StepArgs sa = {w.runs, w.runcap, w.rcur};
+    if (step) { ProfScope p(d->prof_events, MM_PROF_PIXEL_BWD, s); }
+    else {
+        // w.tcnt is zero here: cleared by the vertex stage of the forward and again by every vertex backward (no memset launch)
+        launch_pixel_bwd(a, d, s);
+        if (launch_ok("pixel_bwd") != MM_OK) return MM_ERR_LAUNCH;
+    }
     {
         ProfScope p(d->prof_events, MM_PROF_GATHER_BWD, s);
         const int ntex = a.ntx * a.nty * d->B;
@@ -480,8 +638,11 @@ int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Works
         const int fpw = fl4 ? 16 : MM_FPW;
         const long long nwaves = (long long)d->B * ((w.item_cap + fpw - 1) / fpw);          // (item group, image), sized for the cap: waves
         const unsigned nface = (unsigned)((nwaves + 3) / 4);                                // beyond an image's item count exit at once
-        if (fl4) hipLaunchKernelGGL(gather_bwd_kernel<4>, dim3(ntex + nface), dim3(256), 0, s, a, ntex);
-        else hipLaunchKernelGGL(gather_bwd_kernel<MM_FL>, dim3(ntex + nface), dim3(256), 0, s, a, ntex);
+        if (step) {
+            if (fl4) hipLaunchKernelGGL((gather_bwd_kernel<4, true>), dim3(ntex + nface), dim3(256), 0, s, a, ntex, sa);
+            else hipLaunchKernelGGL((gather_bwd_kernel<MM_FL, true>), dim3(ntex + nface), dim3(256), 0, s, a, ntex, sa);
+        } else if (fl4) hipLaunchKernelGGL((gather_bwd_kernel<4, false>), dim3(ntex + nface), dim3(256), 0, s, a, ntex, sa);
+        else hipLaunchKernelGGL((gather_bwd_kernel<MM_FL, false>), dim3(ntex + nface), dim3(256), 0, s, a, ntex, sa);
     }
     return launch_ok("raster_bwd");
 }

@@ -116,6 +116,12 @@ struct Workspace {
     float* part;           // (B,item_cap,12) per-item partial sums of dL/d(face xy) (6) and dL/d(unit normal) (3); the vertex backward adds a
                            //            face's items up in index order
     int item_cap;          // F + 16 H W / MM_CHUNK_PX: every face has an item, and sixteen screens' worth of box pixels are cut into chunks
+    // step mode (MMRenderDesc.step_grads; carved only when the field is set, between `part` and `trec`: nothing in front of them moves)
+    float* dl_tile;        // (B,4*blocks,12) dL/dlights of every screen TILE (9 used), left by the forward's shade epilogue in tile-slot order
+    int runcap;            // runs per image the list holds (the minimum record array's length)
+    int2* runs;            // (B,runcap) run descriptors {texture tile << 7 | records, first record} of the records the epilogue's waves appended
+    unsigned long long* rcur;  // (B)    the image's cursor: records taken (low word) and runs listed (high word).  The first words of tcur, which
+                           //            step mode does not use otherwise: cleared with the other counters by the vertex stage of the forward
     int ntiles;
     int bin_shift, nbx, nby, words;
     size_t binmask_bytes;
@@ -146,7 +152,7 @@ inline bool vertex_bwd_per_image(int B, int F, int vc_stride) {
 // geo_only (MMRenderDesc.geometry_only: nothing is rasterised): only what the vertex stage touches -- camera, face records, face flags, the counters it
 // clears, the dL/dT partials and ONE (never written, never used) row of item sums per image for the backward's unconditional loads; every other block
 // is empty.  3 MB instead of 71 MB at B=48, 1 280 faces, 128x128 (advisor r05: the lean trainer step keeps such a workspace alive per geometry render).
-__host__ __device__ inline Workspace carve_workspace(void* base, int B, int V, int F, int H, int W, int Ht, int Wt, size_t avail = 0, bool geo_only = false) {
+__host__ __device__ inline Workspace carve_workspace(void* base, int B, int V, int F, int H, int W, int Ht, int Wt, size_t avail = 0, bool geo_only = false, bool step = false) {
     Workspace w;
     char* p = (char*)base;
     size_t o = 0;
@@ -187,8 +193,15 @@ __host__ __device__ inline Workspace carve_workspace(void* base, int B, int V, i
     w.items = (int2*)(p + o);       o += align256(geo_only ? 0 : (size_t)B * w.item_cap * sizeof(int2));
     w.nitems = (int2*)(p + o);      o += align256(geo_only ? 0 : (size_t)B * sizeof(int2));
     w.part = (float*)(p + o);       o += align256((size_t)B * w.item_cap * 12 * sizeof(float));
-    w.trec = (TexRecord*)(p + o);                                 // (last: the record arrays take what the caller gives beyond the minimum)
+    step = step && !geo_only;
+    w.dl_tile = (float*)(p + o);    o += align256(step ? (size_t)B * 4 * w.blocks_per_image * 12 * sizeof(float) : 0);
     const size_t rc_min = geo_only ? 0 : ((size_t)H * W * 9 / 8 + 255) & ~(size_t)255;
+    // (a run holds at least one record: an image's runs never outnumber its record slots, and the list is as long as the array.  The minimum
+    //  array's list is carved here; a larger workspace enlarges the array only, and a run beyond the list is dropped and reported like a record)
+    w.runs = (int2*)(p + o);        o += align256(step ? (size_t)B * rc_min * sizeof(int2) : 0);
+    w.runcap = (int)rc_min;
+    w.rcur = (unsigned long long*)w.tcur;
+    w.trec = (TexRecord*)(p + o);                                 // (last: the record arrays take what the caller gives beyond the minimum)
     size_t rc = rc_min;
     const size_t need = o + align256((size_t)B * rc_min * sizeof(TexRecord));
     if (avail > need && !geo_only) rc += (avail - need) / ((size_t)B * sizeof(TexRecord));
@@ -198,6 +211,9 @@ __host__ __device__ inline Workspace carve_workspace(void* base, int B, int V, i
     w.bytes = o;
     return w;
 }
+
+// does this call take step mode (include/mm_render.h: MMRenderDesc.step_grads)?  One answer for the forward and the backward (mm_raster.hip)
+bool render_step_mode(const MMRenderDesc* d, const Workspace& w);
 
 // ---- camera: smr_utils.py:257-311 + networks.py:278-282 -----------------------------------------------------------
 struct Camera {

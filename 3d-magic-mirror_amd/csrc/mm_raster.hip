@@ -24,6 +24,7 @@
 //   * the epilogue (winner -> uv -> texels -> shade -> store) is written as TWO dependent trips to memory (mm_raster_common.h: shade_store).
 #include "mm_raster_walk.h"
 #include "mm_order.h"
+#include "mm_plan.h"
 
 namespace mm {
 
@@ -40,8 +41,13 @@ namespace mm {
 // kContour: the fused loss carries recon_data's contour term (host: fused_gt && fused_contour > 0)
 // kViews: a multi-view call (mm_render_views_forward, RasterArgs::views > 1; never with the fused loss): the shade epilogue reads bg, lights and
 // textures from the image's sample.  The instantiations mm_render_forward launches are the kViews = false ones and hold none of that code.
-template <bool kNoMask, bool kBlock, bool kQueue, bool kContour, bool kViews>
-__global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_eu(MM_RASTER_WPE, MM_RASTER_WPE))) void raster_fwd_kernel(RasterArgs a_) {   // kBlock: 5 waves per SIMD = 96 VGPRs, 5 x 32 KiB LDS per CU
+// kStep: step mode (MMRenderDesc.step_grads; kBlock, per-batch walk, no contour, one view): the epilogues run the backward's pixel pass
+// (step_pixel_pass, mm_raster_common.h) and the grid's first workgroups plan the backward's face sweep over the stage's LDS.
+#ifndef MM_RASTER_WPE_STEP
+#define MM_RASTER_WPE_STEP 4              // the pixel pass's live values on top of the epilogue's: 128 VGPRs (see profiles/fused_step_kernel_stats.md)
+#endif
+template <bool kNoMask, bool kBlock, bool kQueue, bool kContour, bool kViews, bool kStep = false>
+__global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_eu(kStep ? MM_RASTER_WPE_STEP : MM_RASTER_WPE, kStep ? MM_RASTER_WPE_STEP : MM_RASTER_WPE))) void raster_fwd_kernel(RasterArgs a_) {   // kBlock: 5 waves per SIMD = 96 VGPRs, 5 x 32 KiB LDS per CU
 #ifndef __HIP_DEVICE_COMPILE__
     const RasterArgs& a = a_;
 #else
@@ -52,13 +58,25 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
     const RasterArgs& a = *(const RasterArgs*)__builtin_amdgcn_kernarg_segment_ptr();   // (the kernel's only parameter: the segment starts with it)
 #endif
     __shared__ WaveStage s_stage[kBlock ? 4 : 1];
+    // step mode: the grid's FIRST workgroups plan the backward's face sweep (they need the face records only, and started first they run beside
+    // the walk; behind it they were the launch's tail: +4.7 us at 128x128, profiles/fused_step_kernel_stats.md).  plan_first = how many they
+    // are, a multiple of 8: the walk's workgroups keep their place in the dispatcher's round over the XCDs (walk_image_rank).
+    if (kStep && (int)blockIdx.x < a.plan_first) {               // (workgroup-uniform)
+        static_assert(!kStep || sizeof(s_stage) >= sizeof(int) * MM_PLAN_WGS * 4 + sizeof(unsigned short) * MM_PLAN_LDS_FACES, "the plan's LDS overlays the stage");
+        const int k = (int)blockIdx.x;
+        if (k >= a.plan_wgs * a.B) return;
+        plan_sweep_items<false>(a, k / a.plan_wgs, k % a.plan_wgs, reinterpret_cast<int (*)[4]>(&s_stage[0]),
+                                reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(&s_stage[0]) + sizeof(int) * MM_PLAN_WGS * 4));
+        return;
+    }
+    const int bid = kStep ? (int)blockIdx.x - a.plan_first : (int)blockIdx.x;
     const int wv = kBlock ? threadIdx.x >> 6 : 0;               // (MM_WAVE_UNIFORM here and on the order entry: 83 instead of 96 VGPRs, but 1-3 % SLOWER at every size)
     int limit = 4 * a.blocks_per_image, rank = -1;               // rank: this workgroup's index among its image's walking workgroups (-1: from blockIdx)
     if (a.order) {
         // workgroups of image b, in launch order: heavy tiles (one each), the other non-empty tiles (four each, or one), then the empty
         // tiles four per WAVE (shade_empty_tiles); the grid is sized for "no tile is empty", workgroups behind the last one exit
         int b, j;
-        walk_image_rank((int)blockIdx.x, a.B, a.spread, b, j);
+        walk_image_rank(bid, a.B, a.spread, b, j);
         const int nh = kBlock ? a.nheavy[4 * b] : 0, nne = a.nheavy[4 * b + 1];
         const int W1 = kBlock ? nh + (max(nne - nh, 0) + 3) / 4 : nne;       // workgroups that walk: heavy tiles one each, the others four each (or one)
         const int per = kBlock ? 16 : 4, W2 = (4 * a.blocks_per_image - nne + per - 1) / per;   // workgroups that shade empty tiles
@@ -66,13 +84,13 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
         if (j >= W1) {                                           // (interleaving the two kinds of workgroup evenly was measured: no gain at 512x512,
             if (j - W1 >= W2) return;                            //  slower at 128x128, where every walking workgroup is resident from the start)
             const int e0 = nne + (j - W1) * per + wv * 4, ne = min(4, 4 * a.blocks_per_image - e0);
-            if (ne > 0) shade_empty_tiles<kNoMask, kContour, kViews>(a, b, e0, ne, threadIdx.x & 63);
+            if (ne > 0) shade_empty_tiles<kNoMask, kContour, kViews, kStep>(a, b, e0, ne, threadIdx.x & 63);
             return;
         }
         rank = j;
     }
     bool valid, coop;
-    const TileCtx t = make_tile<kBlock>(a, wv, rank, valid, coop, limit);    // coop is workgroup-uniform; !valid only in the last workgroup of the non-empty tiles
+    const TileCtx t = make_tile<kBlock>(a, wv, rank, valid, coop, limit, kStep ? bid : -1);    // coop is workgroup-uniform; !valid only in the last workgroup of the non-empty tiles
     unsigned long long key;
     SoftState ss;
     if (kBlock && coop) {
@@ -83,7 +101,7 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
         if (kQueue) tile_walk(a, t, &s_stage[wv], key, ss);
         else tile_walk_batch(a, t, &s_stage[wv], key, ss);
     }
-    shade_store<kNoMask, kContour, kViews>(a, t, key, ss);
+    shade_store<kNoMask, kContour, kViews, kStep>(a, t, key, ss);
     flush_taken_last(a, t, &s_stage[(kBlock && coop) ? 0 : wv]);
 }
 
@@ -175,7 +193,24 @@ RasterArgs make_raster_args(const MMRenderDesc* d, const Workspace& w) {
     a.block_sort = 0;
     a.feats = nullptr; a.D = 0; a.interp = nullptr; a.soft_out = nullptr; a.face_idx64 = nullptr; a.options = d->options;
     a.views = 1;
+    a.step = 0; a.grad_loss = nullptr; a.image_weight = 0.f; a.grad_bg = nullptr; a.gp = nullptr; a.gp2 = nullptr; a.dl_tile = nullptr; a.gmax = nullptr;
+    a.rcur = nullptr; a.runs = nullptr; a.runcap = 0; a.trec = nullptr; a.trcap = 0; a.tdrop = nullptr;
+    a.plan_first = 0; a.plan_wgs = 1; a.sweep_sx = a.sweep_sy = 0; a.item_cap = 0; a.plan_chunkmap = nullptr; a.plan_items = nullptr; a.plan_nitems = nullptr;
     return a;
+}
+
+// Does this call take step mode (include/mm_render.h: MMRenderDesc.step_grads)?  Asked by the forward and by the backward, of the same descriptor.
+bool render_step_mode(const MMRenderDesc* d, const Workspace& w) {
+    if (!d->step_grads || !d->fused_gt || d->fused_contour != 0.f || d->fused_totals || d->geometry_only) return false;
+    if (d->no_mask && !d->step_grads->grad_bg) return false;
+    RasterArgs a = make_raster_args(d, w);
+    const int nslot = 4 * a.blocks_per_image;
+    if (nslot > MM_ORDER_MAX_SLOTS || nslot > 0x7FFF) return false;              // no tile order (launch_order)
+    a.order = w.order;
+    a.block_sort = walk_block_sort(a) ? 1 : 0;
+    // the 256-thread per-batch walk over a tile order, chosen by the shape itself: 8-pixel bins, one batch in flight, nothing forced
+    if (d->options & (MM_OPT_WALK_BLOCK | MM_OPT_WALK_WAVE | MM_OPT_WALK_QUEUE | MM_OPT_WALK_BATCH | MM_OPT_MANY_IN_FLIGHT)) return false;
+    return a.bin_shift == 3 && walk_block_mode(a) && !walk_queue_mode(a);
 }
 
 const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nheavy, int* bincount, int B, void** prof_events, hipStream_t s) {
@@ -205,6 +240,19 @@ int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, 
     // 8-pixel bins: the bin is the tile, nothing to compact -> the per-batch walk, no face flags (every face gets its sweep items)
     const bool queue = walk_queue_mode(a);
     if (!queue) a.fflag = nullptr;
+    if (views == 1 && render_step_mode(d, w)) {                  // step mode: + the pixel pass in the epilogues, + the plan workgroups behind the walk
+        a.step = 1;
+        a.grad_loss = d->fused_grad_loss; a.image_weight = d->fused_image_weight;
+        a.grad_bg = d->step_grads->grad_bg; a.gp = w.gp; a.gp2 = w.gp2; a.dl_tile = w.dl_tile; a.gmax = w.gmax;
+        a.rcur = w.rcur; a.runs = w.runs; a.runcap = w.runcap; a.trec = w.trec; a.trcap = w.trcap; a.tdrop = w.tdrop;
+        a.plan_wgs = d->F > 4096 ? MM_PLAN_WGS : 1; a.plan_first = (a.plan_wgs * d->B + 7) & ~7;
+        a.sweep_sx = sweep_shrink(d->boxlen, d->W); a.sweep_sy = sweep_shrink(d->boxlen, d->H);
+        a.item_cap = w.item_cap; a.plan_chunkmap = w.chunkmap; a.plan_items = w.items; a.plan_nitems = w.nitems;
+        const dim3 sgrid(grid.x + (unsigned)a.plan_first);
+        if (d->no_mask) hipLaunchKernelGGL((raster_fwd_kernel<true, true, false, false, false, true>), sgrid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((raster_fwd_kernel<false, true, false, false, false, true>), sgrid, dim3(256), 0, s, a);
+        return launch_ok("raster_fwd");
+    }
 #define MM_LAUNCH_RASTER2(NM, BL, QU, CO, VI) hipLaunchKernelGGL((raster_fwd_kernel<NM, BL, QU, CO, VI>), grid, dim3(BL ? 256 : 64), 0, s, a)
 #define MM_LAUNCH_RASTER(NM, BL, QU) do { if (views > 1) MM_LAUNCH_RASTER2(NM, BL, QU, false, true); else if (a.contour > 0.f) MM_LAUNCH_RASTER2(NM, BL, QU, true, false); \
                                           else MM_LAUNCH_RASTER2(NM, BL, QU, false, false); } while (0)

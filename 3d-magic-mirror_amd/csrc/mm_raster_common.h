@@ -5,6 +5,7 @@
 #pragma once
 #include "mm_device.h"
 #include "mm_order.h"
+#include "mm_pixel_pass.h"
 
 namespace mm {
 
@@ -41,7 +42,28 @@ struct RasterArgs {
     int options;                            // MM_OPT_* bits
     int views;                              // multi-view calls (mm_render_views_*): images per sample -- textures, lights and bg hold B / views rows and image b
                                             // reads row b / views (kViews instantiations only; 1 everywhere else)
+    // STEP MODE (MMRenderDesc.step_grads, kStep instantiation only): the shade epilogue goes on into the backward's pixel pass from the values it
+    // holds (step_pixel_pass / shade_empty_tiles), and the first workgroups of the grid plan the backward's face sweep
+    int step;
+    const float* grad_loss; float image_weight;                  // dL/dloss (nullptr: 1) and the image term's weight: kl1 of the pixel pass
+    float* grad_bg; float4* gp; float* gp2;                      // dL/dbg; the K2 numbers of covered pixels (nothing is written for uncovered ones)
+    float* dl_tile;                                              // (B,4*blocks,12) the tile's nine light sums, one row per tile slot
+    unsigned* gmax;                                              // (B,MM_GSHARD,8) [0] max |K2 number|; [2], [3] the largest / smallest ground-truth mask of the
+                                                                 // image's uncovered pixels, as ordered bits (mask_ord): the gather forms max |dL/dalpha| from them
+    unsigned long long* rcur; int2* runs; int runcap;            // texture records: the image's cursor {records, runs << 32}, its run list
+    TexRecord* trec; int trcap; int* tdrop;
+    int plan_first, plan_wgs, sweep_sx, sweep_sy, item_cap;      // sweep plan: workgroups [0, plan_wgs * B) of the grid; the walk starts at workgroup plan_first
+    int2* plan_chunkmap; int2* plan_items; int2* plan_nitems;
 };
+
+// order-preserving bits of a ground-truth mask value (0 is kept for "none"): the step epilogue leaves the two extremes of an image's uncovered
+// pixels with integer atomic maxima -- of mask_ord(gm) and of ~mask_ord(gm)
+__device__ inline unsigned mask_ord(float v) {
+    const unsigned b = __float_as_uint(v + 0.f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ inline float mask_ord_inv(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o); }
+__device__ inline unsigned wave_max_u32(unsigned v) { return ~wave_min_u32(~v); }
 
 #ifndef MM_PAIR_ROUND
 #define MM_PAIR_ROUND 512
@@ -388,6 +410,103 @@ __device__ inline float contour_term(float alpha, float gm, bool in_img, int lan
     return (cp - cg) * (cp - cg);
 }
 
+// ---- STEP MODE: the backward's pixel pass, continued from the shade epilogue's registers (MMRenderDesc.step_grads; mm_backward.hip has the
+// data flow).  Nothing is loaded: the winner's records, the barycentrics, the footprint and its twelve texels, lights, background and ground
+// truth are the epilogue's own; the arithmetic is mm_pixel_pass.h, one text with pixel_bwd_kernel, so every number is the one that kernel
+// would have written.  What leaves the wave: dL/dbg, the K2 numbers of covered pixels, the texture records, and per tile the nine light sums,
+// per image (integer atomic maxima, order-free) the largest |K2 number| and the extremes of the ground-truth mask over uncovered pixels.
+// Texture records are placed WITHOUT a scan of per-tile counts: a group of lanes under the same texture tile takes a run of consecutive
+// slots from the image's one cursor -- one returning 64-bit atomic per (wave, tile), which also numbers the run -- stores its records there
+// and lists the run {tile, first record, records}; the tile's workgroup of the gather picks its runs out of the image's list.
+__device__ inline void step_store_light_row(const RasterArgs& a, int b, int slot, const float (&dl)[9]) {
+    float* row = a.dl_tile + ((size_t)b * 4 * a.blocks_per_image + slot) * 12;
+    *(float4*)(row + 0) = make_float4(dl[0], dl[1], dl[2], dl[3]);
+    *(float4*)(row + 4) = make_float4(dl[4], dl[5], dl[6], dl[7]);
+    row[8] = dl[8];
+}
+__device__ inline PixelLoss step_pixel_loss(const RasterArgs& a, const float (&gtv)[4]) {
+    PixelLoss pl;
+    const float gs = a.grad_loss ? a.grad_loss[0] : 1.f;
+    pl.kl1 = gs * a.image_weight / ((float)a.B * 3.f * (float)a.H * (float)a.W);
+    const float gm = gtv[3];
+    pl.gmv = gm;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { pl.gi3[c] = gtv[c] * gm + 1.f * (1.f - gm); pl.gin[c] = 0.f; }
+    pl.gsw = 0.f; pl.cnt = 1.f;
+    return pl;
+}
+// the image's mask extremes over the wave's uncovered pixels (open: this lane has one, gm its mask)
+__device__ inline void step_mask_extremes(const RasterArgs& a, int b, int blk, bool open, float gm, int lane) {
+    const unsigned o = mask_ord(gm);
+    const unsigned hi = wave_max_u32(open ? o : 0u), lo = wave_max_u32(open ? ~o : 0u);
+    if (lane == 0 && hi != 0u) {
+        unsigned* g = a.gmax + ((size_t)b * MM_GSHARD + (blk & (MM_GSHARD - 1))) * 8;
+        atomicMax(g + 2, hi); atomicMax(g + 3, lo);
+    }
+}
+template <bool kNoMask>
+__device__ inline void step_pixel_pass(const RasterArgs& a, const TileCtx& t, int hfw, int sb, const PixelShade& shw, const Bilin& s, const float (&tq)[3][4],
+                                       const float (&L)[9], const float (&bgv)[3], const float (&gtv)[4], size_t pix, size_t pin, size_t hw) {
+    (void)sb;
+    const int hf = t.in_img ? hfw : -1;                          // (lanes outside a ragged image: not pixels)
+    const bool any_covered = __ballot(hf >= 0) != 0;             // wave-uniform; pixel_bwd's own test
+    const PixelLoss pl = step_pixel_loss(a, gtv);
+    float dcs = 0.f, snx = 0.f, sny = 0.f, snz = 0.f, m2 = 0.f;
+    PixelGrad pg;
+    pg.rtile[0] = pg.rtile[1] = pg.rtile[2] = pg.rtile[3] = -1;
+    if (!any_covered) {
+        if (kNoMask && t.in_img) {
+            const float coef = MM_SH_C0 * L[0] + (0.f - MM_SH_C6B) * L[6];
+            float gbg[3];
+            dcs = pixel_pass_background<false>(pl, true, bgv, coef, gbg);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.grad_bg[((size_t)t.b * 3 + c) * hw + pin] = gbg[c];
+        }
+    } else if (t.in_img && (hf >= 0 || kNoMask)) {
+        PixelShade sh = shw;
+        sh.hf = hf;
+        pixel_pass_shaded<kNoMask, false>(pl, true, sh, s, tq, L, bgv, a.Ht, a.Wt, a.ntx_tex, a.mult, pg);
+        if (kNoMask) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.grad_bg[((size_t)t.b * 3 + c) * hw + pin] = pg.gbg[c];
+        }
+        dcs = pg.dcs; snx = sh.nx; sny = sh.ny; snz = sh.nz;
+        if (hf >= 0) { a.gp[pix * 2 + 0] = pg.k0; a.gp[pix * 2 + 1] = pg.k1; a.gp2[pix] = pg.k2; m2 = pg.m2; }
+    }
+    // the runs' slots: all leaders of a footprint corner in one instruction, the four corners' atomics in flight together
+    int leader[4], rank[4], size[4];
+    unsigned long long got[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        leader[c] = -1; rank[c] = 0; size[c] = 0; got[c] = 0ull;
+        if (!any_covered) continue;                              // wave-uniform: nothing to append
+        tile_groups(pg.rtile[c], leader[c], rank[c], size[c]);
+        if (leader[c] == t.lane) got[c] = atomicAdd(a.rcur + t.b, (1ull << 32) | (unsigned long long)size[c]);
+    }
+    // (the slots are on their way: the tile's light sums and the image's maxima meanwhile)
+    float dl[9];
+    wave_light_sums(any_covered, dcs, snx, sny, snz, a.options, dl);
+    if (t.lane == 0) step_store_light_row(a, t.b, t.blk * 4 + t.wave, dl);
+    m2 = wave_max(m2);
+    if (t.lane == 0 && m2 > 0.f) atomicMax(a.gmax + ((size_t)t.b * MM_GSHARD + (t.blk & (MM_GSHARD - 1))) * 8, __float_as_uint(m2));
+    step_mask_extremes(a, t.b, t.blk, t.in_img && hf < 0, gtv[3], t.lane);
+    if (!any_covered) return;
+    int ndrop = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int src = leader[c] < 0 ? t.lane : leader[c];
+        const unsigned first = (unsigned)__shfl((int)(unsigned)got[c], src, 64), run = (unsigned)__shfl((int)(unsigned)(got[c] >> 32), src, 64);
+        if (pg.rtile[c] >= 0) {
+            const unsigned pos = first + (unsigned)rank[c];
+            // inside the image's array, in a run the list has room for; otherwise dropped and reported (the texture gather poisons the image's gradient)
+            if (pos < (unsigned)a.trcap && run < (unsigned)a.runcap) a.trec[(size_t)t.b * a.trcap + pos] = pg.rec;
+            else ++ndrop;
+            if (leader[c] == t.lane && run < (unsigned)a.runcap) a.runs[(size_t)t.b * a.runcap + run] = make_int2((pg.rtile[c] << 7) | size[c], (int)first);
+        }
+    }
+    if (__builtin_expect(__ballot(ndrop != 0) != 0ull, 0)) { if (ndrop) atomicAdd(a.tdrop + t.b, ndrop); }
+}
+
 // ---- shading (a9-a11), stores, fused recon_data partial sums.  Uncovered pixels carry zero features exactly like kaolin's
 // interpolated_features.  key = the pixel's depth key after the walk (0: uncovered).
 // (lanes outside a ragged image only stay for the fused loss reduction: they address a clamped pixel and store nothing)
@@ -397,9 +516,12 @@ __device__ inline float contour_term(float alpha, float gm, bool in_img, int lan
 //   trip 1  everything that depends on the winner's id alone: its geometry, normal and corner uvs, plus background / ground truth
 //   trip 2  the twelve texels, from clamped (always valid) addresses, unconditionally; a corner outside contributes an exact zero
 // The arithmetic (expressions, order, roundings) is unchanged.
+// kStep (step mode, MMRenderDesc.step_grads): nothing of the above changes; behind the stores the wave continues into the backward's pixel
+// pass with the winner's records, barycentrics, footprint, texels, lights, background and ground truth it already holds (step_pixel_pass
+// above) -- no further load, one returning atomic for its record slots -- and the per-tile counts at the end are not taken.
 // kContour: the fused loss carries recon_data's contour term (a.contour > 0; chosen by the host -- the reference's default is none, train.py:115)
 // kViews: a multi-view call -- the per-sample inputs (bg, lights, textures) are addressed by the image's SAMPLE, a wave-uniform division per tile
-template <bool kNoMask, bool kContour, bool kViews = false>
+template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false>
 __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsigned long long key, const SoftState& ss) {
     if (!t.in_img && !a.gt) return;
     const int sb = kViews ? t.b / a.views : t.b;                 // the row of the per-sample inputs
@@ -438,6 +560,9 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
 #pragma unroll                                                   // the user's lights 2 / 3 with the y / z bands instead
     for (int i = 0; i < 9; ++i) L[i] = a.lights[sb * 9 + i];
     if (a.options & MM_OPT_SH_ORDER_XYZ) { const float tmp = L[2]; L[2] = L[3]; L[3] = tmp; }
+    PixelShade sh;                                               // (step mode: what the pixel pass takes over; dead otherwise)
+    Bilin s;
+    float tq[3][4];
     if (!any) {
         // No lane of the tile is covered.  The general path below then computes, per lane,
         //   m = 0, n = 0  ->  coef = C0*L0 + (0 - C6B)*L6   (the other seven bands are products with 0)
@@ -455,6 +580,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
             float w0, w1, w2, nrm;                               // barycentrics of the winner (same expressions, same values as the walk's)
             bary_weights(p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, t.x0, t.y0, a.eps, (a.options & MM_OPT_BARY_ONE_MINUS) != 0, w0, w1, w2, nrm);
             if (h.f >= 0) { h.w0 = w0; h.w1 = w1; h.w2 = w2; }
+            if (kStep) sh.nrm = nrm;
         }
         if (h.f >= 0) {
             m = (h.w0 + h.w1) + h.w2;
@@ -464,14 +590,13 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
             ny = (h.w0 * n1 + h.w1 * n1) + h.w2 * n1;
             nz = (h.w0 * n2 + h.w1 * n2) + h.w2 * n2;
         }
-        const Bilin s = bilin_setup(u, v, a.Ht, a.Wt);
+        s = bilin_setup(u, v, a.Ht, a.Wt);
         const bool inw = s.x0 < a.Wt && s.y0 < a.Ht, ine = s.x1 < a.Wt && s.y0 < a.Ht;
         const bool isw = s.x0 < a.Wt && s.y1 < a.Ht, ise = s.x1 < a.Wt && s.y1 < a.Ht;
         if (h.f >= 0 && t.in_img) { fpx0 = s.x0; fpy0 = s.y0; fpx1 = s.x1; fpy1 = s.y1; }
         // ---- trip 2: twelve loads in flight together
         const int cx0 = min(max(s.x0, 0), a.Wt - 1), cx1 = min(max(s.x1, 0), a.Wt - 1);
         const int cy0 = min(max(s.y0, 0), a.Ht - 1), cy1 = min(max(s.y1, 0), a.Ht - 1);
-        float tq[3][4];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* tex = a.textures + ((size_t)sb * 3 + c) * a.Ht * a.Wt;
@@ -483,6 +608,12 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
         float coef = 0.f;
 #pragma unroll
         for (int i = 0; i < 9; ++i) coef += bnd[i] * L[i];
+        if (kStep) {                                             // (the pixel pass continues from exactly these values)
+            sh.p0 = p0; sh.p1 = p1; sh.n0 = n0; sh.n1 = n1; sh.n2 = n2;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sh.fu[i] = fu[i];
+            sh.w0 = h.w0; sh.w1 = h.w1; sh.w2 = h.w2; sh.m = m; sh.nx = nx; sh.ny = ny; sh.nz = nz; sh.x0 = t.x0; sh.y0 = t.y0; sh.coef = coef;
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float tc = 0.f;                                      // (x + 0*w = x exactly: a corner outside the texture leaves the sum as it was)
@@ -535,6 +666,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     // Last (nothing waits for these): the texture tiles under the covered pixels' bilinear footprints, one non-returning add per (wave, tile) -- the
     // lengths (an upper bound: a pixel with no texture gradient appends nothing) of the backward's record lists, which it packs by their prefix sums.
     // The same tiles, from the same footprint, as the pixel backward's rtile[] (mm_pixel_bwd.hip).
+    if (kStep) { step_pixel_pass<kNoMask>(a, t, h.f, sb, sh, s, tq, L, bgv, gtv, pix, pin, hw); return; }   // (places its records itself: no counts)
     if (any && a.trcnt) {
         const bool has = fpx0 >= 0;
         const int tcx0 = fpx0 / MM_UV_TILE, tcy0 = fpy0 / MM_UV_TILE;
@@ -560,7 +692,8 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
 // tile of its own wave pays the wave's fixed costs (launch, two dependent trips to memory, the store drain) for ~40 instructions of
 // work.  Here the four tiles' loads are in flight together.  Per pixel exactly what shade_store's uncovered-tile path computes
 // (m = 0, n = 0, soft-mask state "nothing taken"); the four tiles' recon_data terms go to ltot as one exact integer add per sum.
-template <bool kNoMask, bool kContour, bool kViews = false>
+// Step mode: each of the four tiles also gets the pixel pass of a tile without a covered pixel (dL/dbg, the two constant light bands, its row).
+template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false>
 __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int ne, int lane) {
     const int nslot = 4 * a.blocks_per_image;
     const int sb = kViews ? b / a.views : b;                     // the row of the per-sample inputs (lights, bg)
@@ -594,6 +727,19 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
             const float val = kNoMask ? bgv[q][c] * coef : 1.f;
             out[c] = val < 0.f ? 0.f : (val > 1.f ? 1.f : val);
         }
+        if (kStep) {                                             // (every lane: the tile's sums are wave-wide)
+            float dcs = 0.f;
+            if (kNoMask && in[q]) {
+                const PixelLoss pl = step_pixel_loss(a, gtv[q]);
+                float gbg[3];
+                dcs = pixel_pass_background<false>(pl, true, bgv[q], coef, gbg);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a.grad_bg[((size_t)b * 3 + c) * hw + pin[q]] = gbg[c];
+            }
+            float dl[9];
+            wave_light_sums(false, dcs, 0.f, 0.f, 0.f, a.options, dl);
+            if (lane == 0 && q < ne) step_store_light_row(a, b, (int)sl[q], dl);
+        }
         if (!in[q]) continue;
         const size_t pix = (size_t)b * hw + pin[q];
         *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], 1.f - 1.f);
@@ -609,6 +755,16 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
                 l1 += fabsf(pi - gi);
             }
             down += (0.f + gm) - 0.f * gm;                       // alpha = 0: up = 0, down = gm
+        }
+    }
+    if (kStep) {                                                 // every pixel here is uncovered: the image's mask extremes (one pair of atomics per wave)
+        unsigned hi = 0u, lo = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const unsigned o = mask_ord(gtv[q][3]); hi = max(hi, in[q] ? o : 0u); lo = max(lo, in[q] ? ~o : 0u); }
+        hi = wave_max_u32(hi); lo = wave_max_u32(lo);
+        if (lane == 0 && hi != 0u) {
+            unsigned* g = a.gmax + ((size_t)b * MM_GSHARD + ((sl[0] >> 2) & (MM_GSHARD - 1))) * 8;
+            atomicMax(g + 2, hi); atomicMax(g + 3, lo);
         }
     }
     if (a.gt) {

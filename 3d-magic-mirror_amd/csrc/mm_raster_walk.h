@@ -76,15 +76,16 @@ __device__ inline void flush_taken_last(const RasterArgs& a, const TileCtx& t, W
 //   limit: tiles [0, limit) of the order are walked by this mapping (the fused kernel shades the empty ones behind them four per wave)
 //   rank: the workgroup's index among its image's walking workgroups if the caller has worked it out (the fused kernel interleaves them
 //   with the workgroups that shade empty tiles), -1: straight from blockIdx
+//   bid: the workgroup's index in the walk's launch order if it is not blockIdx.x (step mode: the plan workgroups come first in the grid)
 template <bool kBlock>
-__device__ inline TileCtx make_tile(const RasterArgs& a, int wv, int rank, bool& valid, bool& coop, int limit) {
+__device__ inline TileCtx make_tile(const RasterArgs& a, int wv, int rank, bool& valid, bool& coop, int limit, int bid = -1) {
     TileCtx t;
     int blk;
     valid = true; coop = false;
     if (a.order) {
         const int nslot = 4 * a.blocks_per_image;
         int j;
-        walk_image_rank((int)blockIdx.x, a.B, a.spread, t.b, j);
+        walk_image_rank(bid >= 0 ? bid : (int)blockIdx.x, a.B, a.spread, t.b, j);
         if (rank >= 0) j = rank;
         const int nh = kBlock ? a.nheavy[4 * t.b] : 0;
         int idx;

@@ -139,6 +139,7 @@ struct VertexBwdArgs {
     unsigned* ticket;       // (B) zeroed arrival counter
     int* tcnt; int ntcnt;   // texture-record counters, consumed by the gather before this kernel: cleared for the next backward
     const float* dl_part;   // (B,blocks,12) partial dL/dlights of the pixel backward
+    int dl_tiles;           // step mode: dl_part holds one row per TILE, (B,4*blocks,12); a block's row is ((t0 + t1) + t2) + t3, pixel_bwd's own order
     int geometry_only;      // nothing was rasterised (MMRenderDesc.geometry_only): no face has sweep items, no light gradient is written
     int blocks_per_image;
     float* grad_lights;
@@ -292,9 +293,12 @@ __global__ __launch_bounds__(256) void MM_VX(vertex_bwd_kernel)(VertexBwdArgs a)
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int k = k0 + 64 * u;
-                    const float* row = a.dl_part + ((size_t)b * a.blocks_per_image + min(k, a.blocks_per_image - 1)) * 12 + (wv - 1) * 3;
+                    const float* row = a.dl_part + ((size_t)b * a.blocks_per_image + min(k, a.blocks_per_image - 1)) * (a.dl_tiles ? 48 : 12) + (wv - 1) * 3;
                     const bool ok = k < a.blocks_per_image;
-                    r[u][0] = ok ? row[0] : 0.f; r[u][1] = ok ? row[1] : 0.f; r[u][2] = ok ? row[2] : 0.f;
+                    if (a.dl_tiles) {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) r[u][i] = ok ? ((row[i] + row[12 + i]) + row[24 + i]) + row[36 + i] : 0.f;
+                    } else { r[u][0] = ok ? row[0] : 0.f; r[u][1] = ok ? row[1] : 0.f; r[u][2] = ok ? row[2] : 0.f; }
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { sum[0] += r[u][0]; sum[1] += r[u][1]; sum[2] += r[u][2]; }
@@ -513,9 +517,12 @@ __global__ __launch_bounds__(1024) void MM_VX(vertex_image_bwd_kernel)(VertexBwd
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int kk = k0 + 64 * u;
-                    const float* row = a.dl_part + ((size_t)b * a.blocks_per_image + min(kk, a.blocks_per_image - 1)) * 12 + (wv - 13) * 3;
+                    const float* row = a.dl_part + ((size_t)b * a.blocks_per_image + min(kk, a.blocks_per_image - 1)) * (a.dl_tiles ? 48 : 12) + (wv - 13) * 3;
                     const bool ok = kk < a.blocks_per_image;
-                    r4[u][0] = ok ? row[0] : 0.f; r4[u][1] = ok ? row[1] : 0.f; r4[u][2] = ok ? row[2] : 0.f;
+                    if (a.dl_tiles) {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) r4[u][i] = ok ? ((row[i] + row[12 + i]) + row[24 + i]) + row[36 + i] : 0.f;
+                    } else { r4[u][0] = ok ? row[0] : 0.f; r4[u][1] = ok ? row[1] : 0.f; r4[u][2] = ok ? row[2] : 0.f; }
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { sum[0] += r4[u][0]; sum[1] += r4[u][1]; sum[2] += r4[u][2]; }
@@ -581,7 +588,12 @@ int MM_VX(launch_vertex_bwd)(const MMRenderDesc* d, const MMRenderGrads* g, cons
     a.T = w.T; a.cam = w.cam; a.chunkmap = w.chunkmap; a.part = w.part; a.item_cap = w.item_cap; a.gfn = g->grad_face_normals;
     a.dTpart = w.dTpart; a.ticket = w.ticket;
     a.tcnt = w.tcnt; a.ntcnt = w.ntcnt;
-    a.dl_part = w.dl_part; a.blocks_per_image = w.blocks_per_image; a.grad_lights = g->grad_lights;
+    a.dl_part = w.dl_part; a.dl_tiles = 0; a.blocks_per_image = w.blocks_per_image; a.grad_lights = g->grad_lights;
+    if (views == 1 && !d->geometry_only && render_step_mode(d, w)) {
+        // step mode: the light rows are the forward's, per tile; and what the forward left in the counters (the images' maxima, cursors and drop
+        // counts) is READ by the backward, not consumed -- a second backward after the same forward finds it; the next forward clears it
+        a.dl_part = w.dl_tile; a.dl_tiles = 1; a.ntcnt = 0;
+    }
     a.grad_vertices = g->grad_vertices;
     a.grad_azim = g->grad_azimuths; a.grad_elev = g->grad_elevations; a.grad_dist = g->grad_distances; a.grad_bias = g->grad_biases;
     a.faces = d->faces; a.geometry_only = d->geometry_only;

@@ -46,7 +46,7 @@ class HipEvents:
 
 
 class RenderLossStep:
-    def __init__(self, dr, attributes, gt, no_mask=True, contour=0.0, emit_imnormal=False, loss_scale=None, fused=False):
+    def __init__(self, dr, attributes, gt, no_mask=True, contour=0.0, emit_imnormal=False, loss_scale=None, fused=False, step_mode=True):
         dev = attributes["azimuths"].device
         N.require_device(*[attributes[k] for k in LEAVES if attributes.get(k) is not None], gt)
         self.dr, self.dev, self.no_mask = dr, dev, bool(no_mask)
@@ -64,8 +64,6 @@ class RenderLossStep:
         i = self.inp
         self.d = dr._desc(st, B, no_mask, i["vertices"], i["textures"], i["lights"], i["bg"] if no_mask else None, i["azimuths"],
                           i["elevations"], i["distances"], i["biases"], self.rgba, self.face_idx, self.face_normals, self.imnormal)
-        self.ws = torch.empty(dr.workspace_bytes(self.d), device=dev, dtype=torch.uint8)
-        self.d.workspace, self.d.workspace_bytes = N.ptr(self.ws), self.ws.numel()
         self.grad_rgba = torch.empty_like(self.rgba)
         self.grads = {k: (torch.empty_like(v) if v is not None and (k != "bg" or no_mask) else None) for k, v in self.inp.items()}
         g = self.grads
@@ -93,6 +91,14 @@ class RenderLossStep:
             self.d.fused_image_weight = float(dr.image_weight)
             self.d.fused_loss = N.ptr(self.loss)
             self.d.fused_grad_loss = N.ptr(self.loss_scale)
+        # step mode (MMRenderDesc.step_grads): dL/dloss is known before the render here, so the forward's shade epilogue also runs the backward's
+        # pixel pass and mm_render_backward launches only the gathers and the vertex backward.  The field is set for both calls of the step; the
+        # library takes the mode where the shape is covered (no contour term, 8-pixel screen bins, ...) and ignores the field elsewhere.
+        self.step_mode = self.fused and bool(step_mode) and not contour > 0
+        if self.step_mode:
+            self.d.step_grads = ctypes.addressof(self.g)
+        self.ws = torch.empty(dr.workspace_bytes(self.d), device=dev, dtype=torch.uint8)        # (sized with the field set: the step arrays)
+        self.d.workspace, self.d.workspace_bytes = N.ptr(self.ws), self.ws.numel()
         self.graph = None
         self.ev_render = self.ev_recon = None
 
@@ -147,6 +153,10 @@ class RenderLossStep:
         g = self.grads_struct()
         g.grad_rgba = None
         N.check(L.mm_render_backward(ctypes.byref(d), ctypes.byref(g), s), "mm_render_backward (deferred)")
+
+    def step_mode_taken(self):
+        """True if the library runs this step in step mode (mm_render_step_mode: the field is set AND the shape is covered)."""
+        return bool(N.lib().mm_render_step_mode(ctypes.byref(self.d)))
 
     def render_desc(self):
         """a copy of this step's MMRenderDesc (tests poke at the copy)"""

@@ -118,6 +118,18 @@ typedef struct MMRenderDesc {
      * image's other consumers).  fused_contour must be 0 (the contour term's gradient is formed in another order by the fused kernels: use
      * mm_recon_data_backward for it); fused_loss is not written; the forward of this render ran WITHOUT fused_gt.  NULL: off. */
     const float* fused_totals;
+    /* STEP MODE of the fused loss (NULL: off): the gradients of the step, named already for the FORWARD.  Where dL/dloss is known before the
+     * render (a training step's loss_scale: not an autograd graph, whose dL/dloss arrives later), the pixel pass of the backward depends on
+     * nothing the forward's shade epilogue does not hold in registers, so mm_render_forward runs it there and mm_render_backward launches only
+     * the gathers and the vertex backward -- one kernel and one pass over the pixels less per step.
+     * Contract: the field is set, to the same MMRenderGrads, for BOTH calls of a step.  mm_render_forward reads it for grad_bg (written there
+     * under no_mask) and reads *fused_grad_loss, which must hold its value by then; mm_render_backward is given the same MMRenderGrads.  What the
+     * forward leaves is read, not consumed: mm_render_backward may be called again after one forward.
+     * Taken only with fused_gt set, fused_contour == 0, no fused_totals, no geometry_only, one view, and a shape the step kernel covers (the
+     * 256-thread per-batch walk over a tile order: 8-pixel screen bins, a batch below the one-tile-per-workgroup threshold, no
+     * MM_OPT_MANY_IN_FLIGHT, no forced walk form); in every other case the forward ignores the field and the backward is the usual one, with the
+     * usual bits.  mm_query_workspace accounts for the step arrays when the field is set, whether the shape takes step mode or not. */
+    const struct MMRenderGrads* step_grads;
 } MMRenderDesc;
 
 /* MMRenderDesc.options / MMDibrDesc.options: 0 = the semantics of SURVEY.md 8(a) (the oracle's defaults).  The bits switch,
@@ -181,6 +193,12 @@ int mm_render_status(const MMRenderDesc* desc, mm_stream_t stream, int32_t* drop
  * (networks.py:364-390, contour = 0) to desc->fused_loss from the sums the forward left in the workspace -- for callers that need
  * the loss before they run the backward (the autograd API DiffRender.render_recon).  mm_render_backward writes the same value. */
 int mm_render_fused_loss(const MMRenderDesc* desc, mm_stream_t stream);
+/* 1 if mm_render_forward / mm_render_backward take STEP MODE for this descriptor (MMRenderDesc.step_grads set and every condition listed there
+ * met), 0 if they ignore the field.  Looks at sizes, options and which pointers are set only; nothing is launched. */
+int mm_render_step_mode(const MMRenderDesc* desc);
+/* tests: byte offsets, in a workspace of this descriptor, of the tile order's per-image counts {cooperatively walked tiles, non-empty tiles, -, -}
+ * (B,4) int32 [0], of the step arrays' light rows [1] and run list [2], and the run list's length per image [3] */
+int mm_debug_step_layout(const MMRenderDesc* desc, size_t* out4);
 /* Tools only (profiles/tools): byte offsets inside the render workspace of out[0] = chunkmap (B,F) int2, out[1] = sweep items (B,item_cap)
  * int2, out[2] = nitems (B) int2, out[3] = per-item partial sums (B,item_cap,12) float; out[4] = item_cap; out[5] = gp (B,H,W,2) float4,
  * out[6] = gp2 (B,H,W) float, out[7] = soft (B,H,W) float2, out[8] = per-texture-tile record counts of the last backward (B,ntiles) int
@@ -775,7 +793,9 @@ size_t mm_struct_size(int which);
  * mm_struct_size(24) != 0; still 9: MMRenderViewsDesc and mm_render_views_*, struct id 26, additions again -- MMRenderDesc and
  * MMRenderGrads keep their layout and meaning; still 9: MMCriticDesc / Grads and mm_critic_inputs_forward / _backward, struct ids 27 and 28,
  * additions once more; a binding detects them by mm_struct_size(27) != 0; still 9: MMExportDesc and mm_export_images / mm_export_grid,
- * struct id 29, an addition too, detected by mm_struct_size(29) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * struct id 29, an addition too, detected by mm_struct_size(29) != 0; still 9: MMRenderDesc.step_grads, appended behind fused_totals -- no
+ * existing field moves or changes meaning and NULL is the old behaviour; the struct grows by one pointer, which a binding built against the
+ * shorter struct finds out from mm_struct_size(0), as every binding must check).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
