@@ -148,6 +148,10 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_tile_kernel(SsimIn X, SsimIn 
     if (tid < 2) partial[(size_t)blockIdx.x * 2 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
+// nonnegative_ssim's relu as torch.relu computes it: a negative value becomes 0 and a NaN (a diverged render) stays NaN -- fmaxf would
+// return the 0 and score the plane a silent 0
+__device__ inline float ssim_relu(float v, int nonneg) { return (nonneg && v < 0.f) ? 0.f : v; }
+
 // ---- forward fold: one workgroup, every sum in a fixed order ------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void ssim_fold_kernel(const float* partial, int planes, int ntiles, int C, float P, int nonneg,
                                                          float* ssim, float* cs, float* mean_c, float* mean_all) {
@@ -174,7 +178,7 @@ __global__ __launch_bounds__(1024) void ssim_fold_kernel(const float* partial, i
             float s = 0.f;
             for (int c = 0; c < C; ++c) {
                 const float v = ssim[(size_t)n * C + c];
-                s += nonneg ? fmaxf(v, 0.f) : v;
+                s += ssim_relu(v, nonneg);
             }
             mean_c[n] = s / (float)C;
         }
@@ -183,7 +187,7 @@ __global__ __launch_bounds__(1024) void ssim_fold_kernel(const float* partial, i
         float s = 0.f;
         for (int p = lane; p < planes; p += 64) {
             const float v = ssim[p];
-            s += nonneg ? fmaxf(v, 0.f) : v;
+            s += ssim_relu(v, nonneg);
         }
         s = wave_sum(s);
         if (lane == 0) mean_all[0] = s / (float)planes;

@@ -13,7 +13,7 @@ Semantics, recalled (pytorch_msssim is not vendored; tools/mint_msssim_fixture.p
   R5 maps     cs_map = (2 sxy + C2) / (sx2 + sy2 + C2), ssim_map = (2 mx my + C1) / (mx^2 + my^2 + C1) * cs_map.
   R6 reduce   per channel: the mean over the valid spatial extent; size_average=True: the mean over (N,C); False: over C, shape (N,).
   R7 shapes   trailing singleton dims past dim 1 are squeezed; X and Y must have equal shapes.
-  R8 nonnegative_ssim: relu on the per-channel ssim.
+  R8 nonnegative_ssim: relu on the per-channel ssim (torch.relu: a NaN stays NaN and its gradient passes).
   R9 ms_ssim  weights [0.0448, 0.2856, 0.3001, 0.2363, 0.1333]; asserts min(H,W) > (win_size-1) 2^4; levels 1-4 take relu(cs) and
               then avg_pool2d(kernel 2, padding [s % 2 for s in spatial]); the last level takes relu(ssim per channel); the result is
               prod(stack ** weights), then the same mean.
@@ -93,7 +93,7 @@ class _SsimFn(torch.autograd.Function):
             g_s = (g_red.reshape(Nn, 1) if ctx.mean_c else g_red.reshape(1, 1)) / (C if ctx.mean_c else Nn * C)
             g_s = g_s.expand(Nn, C)
             if ctx.nonneg:
-                g_s = g_s * (ssim_pc > 0)
+                g_s = g_s * ~(ssim_pc <= 0)          # torch.relu's backward: cut where the value is <= 0, so a NaN plane passes
         if g_pc is not None:
             g_s = g_pc if g_s is None else g_s + g_pc
         if (g_s is None and g_cs is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
