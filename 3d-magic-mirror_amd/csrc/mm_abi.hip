@@ -46,6 +46,9 @@ int launch_critic_bwd(const MMCriticDesc*, const MMCriticGrads*, hipStream_t);
 void export_grid_geometry(const MMExportDesc*, long long* xmaps, long long* pad, long long* Hg, long long* Wg);
 int launch_export_images(const MMExportDesc*, hipStream_t);
 int launch_export_grid(const MMExportDesc*, hipStream_t);
+struct BatchArgs;
+long long batch_lds_bytes(const MMBatchDesc*, BatchArgs*);
+int launch_assemble_batch(const MMBatchDesc*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -614,6 +617,28 @@ int mm_export_grid(const MMExportDesc* d, mm_stream_t stream) {
     return mm::launch_export_grid(d, (hipStream_t)stream);
 }
 
+int mm_assemble_batch(const MMBatchDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (!d->images || !d->segs || !d->offsets || !d->sizes || !d->records_host || !d->records || !d->out) return MM_ERR_NULL_POINTER;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->n_images <= 0) return MM_ERR_BAD_SHAPE;
+    const int32_t lim = 1 << 24;                                  // sums of two coordinates stay far inside an int32
+    for (int b = 0; b < d->B; ++b) {
+        const int32_t* r = d->records_host + (size_t)b * 16;
+        if (r[0] < 0 || r[0] >= d->n_images || r[4] < 1 || r[5] < 1 || r[10] < 1 || r[11] < 1) return MM_ERR_BAD_SHAPE;
+        if ((r[1] != 0 && r[1] != 1) || (r[14] != 0 && r[14] != 1)) return MM_ERR_BAD_SHAPE;
+        for (int i = 2; i < 14; ++i)
+            if (r[i] > lim || r[i] < -lim) return MM_ERR_BAD_SHAPE;
+    }
+    if (d->B > 65535) return MM_ERR_UNSUPPORTED;
+    for (int b = 0; b < d->B; ++b) {
+        const int32_t* r = d->records_host + (size_t)b * 16;
+        if (r[4] > (int64_t)MM_BATCH_MAX_RATIO * r[10] || r[5] > (int64_t)MM_BATCH_MAX_RATIO * r[11]) return MM_ERR_UNSUPPORTED;
+    }
+    if (mm::batch_lds_bytes(d, nullptr) > 160 * 1024) return MM_ERR_UNSUPPORTED;
+    mm::clear_stale_error();
+    return mm::launch_assemble_batch(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -685,6 +710,7 @@ size_t mm_struct_size(int which) {
         case 21: return sizeof(MMShapeFeatGrads); case 22: return sizeof(MMCameraFeatDesc); case 23: return sizeof(MMCameraFeatGrads);
         case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);  case 26: return sizeof(MMRenderViewsDesc);
         case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);  case 29: return sizeof(MMExportDesc);
+        case 30: return sizeof(MMBatchDesc);
         default: return 0;
     }
 }

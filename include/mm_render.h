@@ -758,6 +758,47 @@ int mm_export_images(const MMExportDesc* desc, mm_stream_t stream);
 int mm_export_grid(const MMExportDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Batch assembly: training batches (B,4,H,W) fp32 from device-resident 8-bit images, what the reference's DataLoader workers do per
+ * sample in Pillow (datasets/bird.py:69-136, datasets/market.py:77-145), in one launch.  The decoded images lie packed in `images`
+ * (rgb bytes, image i at byte 3 * offsets[i]) and `segs` (one byte per pixel, image i at byte offsets[i]) without padding; sizes holds
+ * rows (H_i, W_i).  Each sample is one canonical record of 16 int32:
+ *    0 img        source image
+ *    1 flip_src   read the source mirrored in x; the coordinates below are in the mirrored image
+ *    2 x0  3 y0  4 Wc  5 Hc     the canvas window, which may hang over any edge
+ *    6 cx0 7 cy0 8 cx1 9 cy1    the clip rectangle [cx0,cx1) x [cy0,cy1): a canvas pixel outside it or outside the image is 0 (rgb and mask)
+ *   10 Wr 11 Hr   the canvas is resized to (Wr,Hr): rgb by Pillow's antialiased bicubic (22-bit fixed point, the horizontal pass to
+ *                 clamped bytes, then the vertical pass), the mask by Pillow's nearest, then 255 if m > 160 else 0
+ *   12 dx 13 dy   output pixel (x,y) reads resized (x + dx, y + dy), 0 outside
+ *   14 flip_out   ... of the output mirrored in x: resized (W - 1 - x + dx, y + dy)
+ *   15 reserved
+ * then v = fl(q / 255); rgb = m ? v : 1.0 unless bg; channel 3 = m as 0.0 / 1.0.  out is dense NCHW.
+ * records_host is the host's copy of the device table `records` (the caller uploads it, e.g. one non-blocking copy from pinned memory):
+ * it is validated and sizes the kernel's LDS before anything is launched.  MM_ERR_BAD_SHAPE: B, H, W, n_images < 1, img outside
+ * [0, n_images), Wc, Hc, Wr or Hr < 1, a flag that is not 0 / 1, a coordinate beyond +-2^24.  MM_ERR_UNSUPPORTED: Wc > MM_BATCH_MAX_RATIO * Wr
+ * or Hc > MM_BATCH_MAX_RATIO * Hr (any upscale is allowed), B > 65535, or tap tables and row buffer beyond the 160 KiB of LDS:
+ *   4 * (Wr * ksx + MM_BATCH_ROWS * ksy + 3 * Wr + 3 * MM_BATCH_ROWS) + 3 * Wr * rows bytes (rounded up to 4), with per axis
+ *   ks = 2 * ceil(2 * max(in / out, 1)) + 1 and rows = floor((MM_BATCH_ROWS - 1) * Hc / Hr) + ksy + 1, each the largest of the batch:
+ *   1024 -> 128 (8:1) takes 53 KiB; at 16:1 outputs at least 190 wide fit.
+ * No workspace, no atomics, no host synchronisation; bitwise reproducible.  Not differentiable.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_BATCH_MAX_RATIO 16
+#define MM_BATCH_ROWS 8             /* output rows per workgroup */
+typedef struct MMBatchDesc {
+    int32_t B, H, W;                /* the output batch (B,4,H,W) */
+    int32_t n_images;               /* images in the pool */
+    int32_t bg;                     /* keep the background: rgb = v everywhere */
+    int32_t reserved;
+    const uint8_t* images;
+    const uint8_t* segs;
+    const int64_t* offsets;         /* (n_images) pixel offsets */
+    const int32_t* sizes;           /* (n_images,2) rows (H_i, W_i) */
+    const int32_t* records_host;    /* (B,16), host memory */
+    const int32_t* records;         /* (B,16), device memory, the same values */
+    float* out;
+} MMBatchDesc;
+int mm_assemble_batch(const MMBatchDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -781,7 +822,7 @@ const char* mm_last_error_detail(void);
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
- * 29 MMExportDesc. */
+ * 29 MMExportDesc, 30 MMBatchDesc. */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -795,7 +836,8 @@ size_t mm_struct_size(int which);
  * additions once more; a binding detects them by mm_struct_size(27) != 0; still 9: MMExportDesc and mm_export_images / mm_export_grid,
  * struct id 29, an addition too, detected by mm_struct_size(29) != 0; still 9: MMRenderDesc.step_grads, appended behind fused_totals -- no
  * existing field moves or changes meaning and NULL is the old behaviour; the struct grows by one pointer, which a binding built against the
- * shorter struct finds out from mm_struct_size(0), as every binding must check).  Bindings must refuse a library whose version differs from what they mirror. */
+ * shorter struct finds out from mm_struct_size(0), as every binding must check; still 9: MMBatchDesc and mm_assemble_batch, struct id 30, an
+ * addition, detected by mm_struct_size(30) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
