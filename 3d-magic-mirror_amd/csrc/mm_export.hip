@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_quant.h"                                         // quant / unquant: shared with mm_composite.hip
 
 #define MM_EXPORT_BLOCK 256
 #define MM_EXPORT_GRID 2048                                   // 256 CUs x 8 workgroups (cdna_hip_programming.md, Guideline 11)
@@ -41,14 +42,6 @@ struct ExportArgs {
     float pad_value;
     long long nchunk;
 };
-
-__device__ inline unsigned quant(float x, int nearest) {
-    MM_FP_EXACT
-    float q = x * 255.0f;
-    if (nearest) q = q + 0.5f;
-    q = fminf(fmaxf(q, 0.0f), 255.0f);                        // fmaxf returns the operand that is not NaN: NaN -> 0
-    return (unsigned)q;                                       // toward zero
-}
 
 __device__ inline float4 over_white(float4 v) {
     MM_FP_EXACT
@@ -152,8 +145,6 @@ __global__ __launch_bounds__(MM_EXPORT_BLOCK) void export_u8_kernel(ExportArgs a
 }
 
 // ---- image mode, fp32 planes ------------------------------------------------------------------------------------------------------
-__device__ inline float unquant(unsigned q) { MM_FP_EXACT return (float)q / 255.0f; }
-
 template <int NHWC, bool VEC>
 __global__ __launch_bounds__(MM_EXPORT_BLOCK) void export_f32_kernel(ExportArgs a) {
     const long long HW = a.HW;

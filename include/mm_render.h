@@ -799,6 +799,58 @@ typedef struct MMBatchDesc {
 int mm_assemble_batch(const MMBatchDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Composite: renders composed over blurred backgrounds as 8-bit frames, what the reference's dataset-generation scripts do on the host per
+ * image after every render (generate_market++.py:308-349, generate_market_new_class9.py:323-347, tool/generate_market.py:293-313), in one
+ * launch: B frames (B,H,W,3) bytes -- or, with as_float, (B,3,H,W) fp32 planes fl(float(q) / 255) -- from `renders`, n_fg images (4,H,W)
+ * fp32, NCHW-contiguous (fg_nhwc 0) or NHWC-dense (fg_nhwc 1: what mm_render_forward and mm_render_views_forward write), and
+ * `backgrounds`, n_bg images (bg_C,H,W) fp32 NCHW-contiguous, bg_C 3 or 4, of which channels 0-2 are read.  Per frame o, all in fp32,
+ * every operation rounded as written, every sum taken in ascending tap index starting from 0:
+ *   mask      m = channel 3 of render fg_index[o].  fill_holes: s = the sum of the 3x3 neighbourhood's pixels inside the image, row by row,
+ *             s = fl(s / 9), then 1 if s > 0.7, 0 if s <= 0.7 (NaN stays).  Blur: sum_j fl(k[j] * m[R(x + j - r)]) along x, then the same
+ *             along y, k = the frame's mask_k taps, r = (mask_k - 1) / 2, R reflecting at the image's edge.  mask_pad p: the blurred mask
+ *             replicate-padded by p and resized (H + 2p, W + 2p) -> (H,W): sum_t fl(w[x][t] * b[C(start[x] + t - p)]) along x, then along y.
+ *   bg        plane c of background bg_index[o] behind the reflection pad bg_pad = (left, right, top, bottom): a virtual image
+ *             (H + top + bottom, W + left + right) that is index arithmetic only; blurred with the frame's bg_k taps, reflecting at the
+ *             VIRTUAL image's edge (an index may be reflected twice); resized to (H,W) like the mask.
+ *   blend     out_c = fl(fl(fg_c * m') + fl(bg'_c * fl(1 - m'))), fg_c = channel c of the render, then the Export quantiser above,
+ *             unchanged: rounding 0 trunc / 1 nearest, NaN -> 0, saturating.
+ * A stage a caller does not want is the identity in this form: one blur tap of 1.0; a resize row {start i, 1 tap, 1.0}.
+ * params is ONE table of 32-bit words (floats by their bits) that the caller uploads; params_host is the host's copy of it, which is
+ * validated and sizes the kernel's LDS before anything is launched:
+ *   fg_index (B) | bg_index (B) | mask taps (B,mask_k) | bg taps (B,bg_k) | resize rows: mask y (H), mask x (W), bg y (H), bg x (W)
+ * a resize row being MM_COMPOSITE_ROW_WORDS words {start, n, w[0..8)}: output index i reads inputs [start, start + n) of the padded axis.
+ * MM_ERR_BAD_SHAPE: B, H, W, n_fg, n_bg < 1; bg_C not 3 or 4; a kernel that is even, < 1 or > MM_COMPOSITE_MAX_KERNEL; a negative pad; a
+ * reflection pad >= the dimension it reflects in, a blur radius >= the (virtual) dimension it reflects in; an index outside [0, n_fg) /
+ * [0, n_bg); a resize row with n outside [1, MM_COMPOSITE_MAX_TAPS] or taps outside the padded axis; rounding not 0 / 1.
+ * MM_ERR_UNSUPPORTED: more than the 160 KiB of LDS -- 8 * (rows * width of the largest plane of any band: the blurred rows its vertical
+ * taps read + kernel - 1, times the virtual width) + 4 * MM_COMPOSITE_ROWS * W + 24 * W + 32 bytes, rounded up; kernel 31 behind a pad of 16 at 128 x 128
+ * takes 60 KiB, kernel 5 at 128 x 64 behind (8,8,16,16) 14 KiB --, or more than 2^31 - 1 workgroups.
+ * No workspace, no atomics, no host synchronisation; bitwise reproducible.  Not differentiable.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_COMPOSITE_ROWS 8         /* output rows per workgroup */
+#define MM_COMPOSITE_MAX_KERNEL 31
+#define MM_COMPOSITE_MAX_TAPS 8     /* resize taps per output index */
+#define MM_COMPOSITE_ROW_WORDS 10
+typedef struct MMCompositeDesc {
+    int32_t B, H, W;                /* the frames */
+    int32_t n_fg, n_bg, bg_C;       /* images in renders / backgrounds; channels of a background */
+    int32_t fg_nhwc;                /* layout flag of renders */
+    int32_t fill_holes;
+    int32_t mask_k, bg_k;           /* blur taps per frame: odd, 1 = none (the tap is 1.0) */
+    int32_t mask_pad;               /* replicate pad of the blurred mask before its resize */
+    int32_t bg_pad[4];              /* reflection pad of the background: left, right, top, bottom */
+    int32_t rounding;               /* 0 trunc, 1 nearest */
+    int32_t as_float;               /* fp32 planes (B,3,H,W) instead of bytes (B,H,W,3) */
+    int32_t reserved;
+    const float* renders;
+    const float* backgrounds;
+    const int32_t* params_host;     /* host memory */
+    const int32_t* params;          /* device memory, the same words */
+    void* out;
+} MMCompositeDesc;
+int mm_composite_frames(const MMCompositeDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -822,7 +874,7 @@ const char* mm_last_error_detail(void);
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
- * 29 MMExportDesc, 30 MMBatchDesc. */
+ * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc (31 is unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -837,7 +889,8 @@ size_t mm_struct_size(int which);
  * struct id 29, an addition too, detected by mm_struct_size(29) != 0; still 9: MMRenderDesc.step_grads, appended behind fused_totals -- no
  * existing field moves or changes meaning and NULL is the old behaviour; the struct grows by one pointer, which a binding built against the
  * shorter struct finds out from mm_struct_size(0), as every binding must check; still 9: MMBatchDesc and mm_assemble_batch, struct id 30, an
- * addition, detected by mm_struct_size(30) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * addition, detected by mm_struct_size(30) != 0; still 9: MMCompositeDesc and mm_composite_frames, struct id 32 -- id 31 stays unassigned and
+ * returns 0 --, an addition, detected by mm_struct_size(32) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
