@@ -2,7 +2,7 @@
 C ABI; the host side mirrors the reference's DiffRender API).  Import as ``importlib.import_module('3d-magic-mirror_amd')``
 or through the root-level ``mm_amd`` alias."""
 from . import encoder_features, interpolate, mesh_reg, obj_io, template, texture_flow, synthetic  # noqa: F401
-from .diff_render import DiffRender, deep_copy  # noqa: F401
+from .diff_render import DiffRender, check_render_index, deep_copy, grid_index  # noqa: F401
 from .obj_io import import_mesh, save_mesh  # noqa: F401
 from .texture_flow import sample_texture  # noqa: F401
 from .encoder_features import camera_features, shape_features  # noqa: F401

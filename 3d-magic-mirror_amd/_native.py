@@ -39,6 +39,10 @@ class MMRenderViewsDesc(ctypes.Structure):
     _fields_ = [("render", MMRenderDesc), ("views", c_i)]
 
 
+class MMRenderIndexedDesc(ctypes.Structure):
+    _fields_ = [("render", MMRenderDesc), ("rows", c_i * 4), ("index", c_p * 4), ("backward", c_i), ("status_flag", c_p)]
+
+
 class MMReconDesc(ctypes.Structure):
     _fields_ = [("B", c_i), ("H", c_i), ("W", c_i), ("pred", c_p), ("pred_strides", ctypes.c_int64 * 4), ("gt", c_p),
                 ("image_weight", c_f), ("contour", c_f), ("loss", c_p), ("grad_loss", c_p), ("grad_pred", c_p),
@@ -223,6 +227,7 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward",
            "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
            "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward",
+           "mm_render_indexed_query_workspace", "mm_render_indexed_forward", "mm_render_indexed_backward",
            "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_assemble_batch", "mm_composite_frames", "mm_struct_size",
            "mm_abi_version")
 
@@ -319,6 +324,10 @@ def lib():
     L.mm_render_views_query_workspace.argtypes = [P(MMRenderViewsDesc)]
     L.mm_render_views_forward.argtypes = [P(MMRenderViewsDesc), c_p]
     L.mm_render_views_backward.argtypes = [P(MMRenderViewsDesc), P(MMRenderGrads), c_p]
+    L.mm_render_indexed_query_workspace.restype = ctypes.c_size_t
+    L.mm_render_indexed_query_workspace.argtypes = [P(MMRenderIndexedDesc)]
+    L.mm_render_indexed_forward.argtypes = [P(MMRenderIndexedDesc), c_p]
+    L.mm_render_indexed_backward.argtypes = [P(MMRenderIndexedDesc), P(MMRenderGrads), c_p]
     L.mm_critic_inputs_forward.argtypes = [P(MMCriticDesc), c_p]
     L.mm_critic_inputs_backward.argtypes = [P(MMCriticDesc), P(MMCriticGrads), c_p]
     L.mm_export_images.argtypes = [P(MMExportDesc), c_p]
@@ -340,7 +349,7 @@ def lib():
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
                MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
                MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads, MMExportDesc, MMBatchDesc,
-               None, MMCompositeDesc)                             # (id 31 is unassigned)
+               None, MMCompositeDesc, MMRenderIndexedDesc)        # (id 31 is unassigned)
     for i, cls in enumerate(mirrors):
         if cls is not None and L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

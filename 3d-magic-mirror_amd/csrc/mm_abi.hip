@@ -9,9 +9,14 @@ namespace mm {
 // views: images per sample of a multi-view call (the per-sample inputs then hold B / views rows); 1 = mm_render_forward / mm_render_backward
 int launch_vertex_fwd(const MMRenderDesc*, const Workspace&, hipStream_t, int views = 1);
 int launch_vertex_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t, int views = 1);
-int launch_raster_fwd(const MMRenderDesc*, const Workspace&, hipStream_t, int views = 1);
-int launch_raster_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t, int views = 1);
+// index_table: the plan's table of an indexed call (mm_indexed.hip; views == 1 then), nullptr everywhere else
+int launch_raster_fwd(const MMRenderDesc*, const Workspace&, hipStream_t, int views = 1, const int* index_table = nullptr);
+int launch_raster_bwd(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t, int views = 1, const int* index_table = nullptr);
 int launch_view_sum(int B, int views, const float* const* staging, float* const* out, const int* len, hipStream_t);
+int launch_vertex_fwd_indexed(const MMRenderDesc*, const Workspace&, hipStream_t, const int* vrow);
+int launch_vertex_bwd_indexed(const MMRenderDesc*, const MMRenderGrads*, const Workspace&, hipStream_t, const int* vrow);
+int launch_index_plan(int M, const int32_t* const* index, const int* rows, const IndexPlan&, int32_t* status, hipStream_t);
+int launch_index_sum(int M, const int* rows, const float* const* staging, float* const* out, const int* len, const IndexPlan&, const MMRenderGrads*, hipStream_t);
 int launch_fused_loss(const MMRenderDesc*, const Workspace&, hipStream_t);
 size_t recon_workspace_bytes(const MMReconDesc*);
 int launch_recon_fwd(const MMReconDesc*, hipStream_t);
@@ -253,6 +258,119 @@ int mm_render_views_backward(const MMRenderViewsDesc* v, const MMRenderGrads* g,
     if (st != MM_OK || v->views == 1) return st;
     float* out[4] = {g->grad_vertices, g->grad_textures, g->grad_lights, r.no_mask ? g->grad_bg : nullptr};
     return mm::launch_view_sum(r.B / v->views, v->views, staging, out, stg.len, s);
+}
+
+// ---- indexed render (include/mm_render.h: MMRenderIndexedDesc) --------------------------------------------------------------------------
+// The HEAD of an indexed workspace: the plan (mm_indexed.hip) -- the table (5, M), then per tensor offsets (rows + 1), cursors (rows) and
+// images (M) -- and, for a call with a backward, the staging areas of the per-image gradients as views_staging lays them out (M rows each).
+// The render workspace of the M images follows with exactly the bytes that are left.  rows[]: the row counts the kernels go by (bg without
+// no_mask: M rows, the identity, never summed).
+struct IndexedHead { size_t table, offsets[4], cursor[4], images[4], staging[4], bytes; int rows[4], len[4]; };
+static IndexedHead indexed_head(const MMRenderIndexedDesc* v) {
+    IndexedHead h;
+    const MMRenderDesc* d = &v->render;
+    const size_t M = (size_t)d->B;
+    size_t o = 0;
+    h.table = o; o += mm::align256(5 * M * sizeof(int));
+    for (int t = 0; t < 4; ++t) {
+        h.rows[t] = (t == 3 && !d->no_mask) ? d->B : v->rows[t];
+        const size_t R = (size_t)(h.rows[t] > 0 ? h.rows[t] : 0);
+        h.offsets[t] = o; o += mm::align256((R + 1) * sizeof(int));
+        h.cursor[t] = o; o += mm::align256(R * sizeof(int));
+        h.images[t] = o; o += mm::align256(M * sizeof(int));
+    }
+    const ViewsStaging st = views_staging(d);
+    for (int t = 0; t < 4; ++t) { h.staging[t] = o + st.off[t]; h.len[t] = st.len[t]; }
+    if (v->backward) o += st.bytes;
+    h.bytes = o;
+    return h;
+}
+static mm::IndexPlan indexed_plan(const IndexedHead& h, void* workspace) {
+    mm::IndexPlan p;
+    char* base = (char*)workspace;
+    p.table = (int*)(base + h.table);
+    for (int t = 0; t < 4; ++t) { p.offsets[t] = (int*)(base + h.offsets[t]); p.cursor[t] = (int*)(base + h.cursor[t]); p.images[t] = (int*)(base + h.images[t]); }
+    return p;
+}
+// the sizes alone (what the query can refuse): MM_OK, or why not
+static int indexed_shape(const MMRenderIndexedDesc* v) {
+    if (!v) return MM_ERR_NULL_POINTER;
+    const MMRenderDesc* d = &v->render;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->V <= 0 || d->F <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
+    if (d->B > 65535) return MM_ERR_UNSUPPORTED;                  // (rows and images are 16-bit keys of the plan; rows are the sum's grid y)
+    for (int t = 0; t < 4; ++t) {
+        if (t == 3 && !d->no_mask) continue;                      // (no bg in this call: its row count is not looked at)
+        if (v->rows[t] < 1) return MM_ERR_BAD_SHAPE;
+        if (v->rows[t] > 65535) return MM_ERR_UNSUPPORTED;
+    }
+    if ((size_t)3 * d->Ht * d->Wt > 0x7fffffff || (size_t)3 * d->H * d->W > 0x7fffffff) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+// everything checked before any launch; *r = the descriptor of the M images as the render kernels take it (the workspace without the head)
+static int check_render_indexed(const MMRenderIndexedDesc* v, bool backward, MMRenderDesc* r, IndexedHead* h) {
+    int st = indexed_shape(v);
+    if (st != MM_OK) return st;
+    const MMRenderDesc* d = &v->render;
+    if (d->fused_gt || d->fused_totals || d->geometry_only) return MM_ERR_UNSUPPORTED;    // fused / deferred losses and geometry-only over indices: not built
+    for (int t = 0; t < 4; ++t)
+        if (!(t == 3 && !d->no_mask) && !v->index[t] && v->rows[t] != d->B) return MM_ERR_BAD_SHAPE;   // the identity needs a row per image
+    if (backward && !v->backward) return MM_ERR_WORKSPACE;       // a forward-only call left no staging
+    *h = indexed_head(v);
+    *r = *d;
+    r->step_grads = nullptr;                                     // (step mode is a fused mode: the field is ignored here)
+    r->workspace = d->workspace ? (char*)d->workspace + h->bytes : nullptr;      // (the head is a multiple of 256: the alignment is the caller's)
+    r->workspace_bytes = d->workspace_bytes > h->bytes ? d->workspace_bytes - h->bytes : 0;
+    return check_render(r, backward);
+}
+
+size_t mm_render_indexed_query_workspace(const MMRenderIndexedDesc* v) {
+    if (indexed_shape(v) != MM_OK) return 0;
+    const size_t base = mm_query_workspace(&v->render);
+    if (base == 0) return 0;
+    return base + indexed_head(v).bytes;
+}
+
+int mm_render_indexed_forward(const MMRenderIndexedDesc* v, mm_stream_t stream) {
+    MMRenderDesc r;
+    IndexedHead h;
+    int st = check_render_indexed(v, false, &r, &h);
+    if (st != MM_OK) return st;
+    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    const mm::IndexPlan p = indexed_plan(h, v->render.workspace);
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t* index[4] = {v->index[0], v->index[1], v->index[2], r.no_mask ? v->index[3] : nullptr};
+    mm::clear_stale_error();
+    st = mm::launch_index_plan(r.B, index, h.rows, p, v->status_flag, s);
+    if (st != MM_OK) return st;
+    st = mm::launch_vertex_fwd_indexed(&r, w, s, p.table);       // (the table's first row: the images' vertices)
+    if (st != MM_OK) return st;
+    return mm::launch_raster_fwd(&r, w, s, 1, p.table);
+}
+
+int mm_render_indexed_backward(const MMRenderIndexedDesc* v, const MMRenderGrads* g, mm_stream_t stream) {
+    MMRenderDesc r;
+    IndexedHead h;
+    int st = check_render_indexed(v, true, &r, &h);
+    if (st != MM_OK) return st;
+    if (!g || !g->grad_vertices || !g->grad_azimuths || !g->grad_elevations || !g->grad_distances || !g->grad_biases || !g->grad_rgba ||
+        !g->grad_textures || !g->grad_lights || (r.no_mask && !g->grad_bg))
+        return MM_ERR_NULL_POINTER;
+    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    const mm::IndexPlan p = indexed_plan(h, v->render.workspace);
+    hipStream_t s = (hipStream_t)stream;
+    MMRenderGrads gi = *g;                                        // the per-image gradients the kernels write
+    float* staging[4];
+    for (int t = 0; t < 4; ++t) staging[t] = (float*)((char*)v->render.workspace + h.staging[t]);
+    gi.grad_vertices = staging[0]; gi.grad_textures = staging[1]; gi.grad_lights = staging[2];
+    gi.grad_bg = r.no_mask ? staging[3] : nullptr;
+    mm::clear_stale_error();
+    st = mm::launch_raster_bwd(&r, &gi, w, s, 1, p.table);
+    if (st != MM_OK) return st;
+    st = mm::launch_vertex_bwd_indexed(&r, &gi, w, s, p.table);
+    if (st != MM_OK) return st;
+    float* out[4] = {g->grad_vertices, g->grad_textures, g->grad_lights, r.no_mask ? g->grad_bg : nullptr};
+    return mm::launch_index_sum(r.B, h.rows, staging, out, h.len, p, g, s);
 }
 
 size_t mm_recon_query_workspace(const MMReconDesc* d) {
@@ -744,6 +862,7 @@ size_t mm_struct_size(int which) {
         case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);  case 26: return sizeof(MMRenderViewsDesc);
         case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);  case 29: return sizeof(MMExportDesc);
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
+        case 33: return sizeof(MMRenderIndexedDesc);
         default: return 0;
     }
 }

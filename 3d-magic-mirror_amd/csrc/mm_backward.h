@@ -47,11 +47,14 @@ struct BwdArgs {
     int views;                                                   // multi-view calls (mm_render_views_backward): images per sample -- textures, lights and bg hold
                                                                  // B / views rows, image b reads row b / views (pixel_bwd's kViews instantiations only); every
                                                                  // gradient stays per image.  (Here it fills the padding in front of the pointer: no offset moves.)
+                                                                 // 0: an indexed call (mm_render_indexed_backward): the rows come from the plan's table, which
+                                                                 // travels in `ltot` (indexed_table below; such a call is never fused)
     float* grad_textures;
 };
 
 #define MM_INT_DEFERRED (1 << 30)   // BwdArgs::options, set by launch_raster_bwd (not an MM_OPT_* bit of the ABI)
 __device__ inline const float* deferred_totals(const BwdArgs& a) { return reinterpret_cast<const float*>(a.ltot); }
+__device__ inline const int* indexed_table(const BwdArgs& a) { return reinterpret_cast<const int*>(a.ltot); }
 
 __device__ inline void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

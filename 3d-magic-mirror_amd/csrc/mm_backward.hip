@@ -594,9 +594,9 @@ int launch_fused_loss(const MMRenderDesc* d, const Workspace& w, hipStream_t s) 
     return launch_ok("fused_loss");
 }
 
-int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views) {
+int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views, const int* index_table) {
     BwdArgs a;
-    a.views = views;
+    a.views = index_table ? 0 : views;                          // (0: an indexed call, BwdArgs::views)
     a.B = d->B; a.H = d->H; a.W = d->W; a.F = d->F; a.Ht = d->Ht; a.Wt = d->Wt; a.knum = d->knum;
     a.blocks_x = (d->W + MM_BLOCK_PX - 1) / MM_BLOCK_PX;
     a.blocks_per_image = w.blocks_per_image; a.options = d->options;
@@ -614,13 +614,14 @@ int launch_raster_bwd(const MMRenderDesc* d, const MMRenderGrads* g, const Works
     a.gt = d->fused_gt; a.rgba = d->rgba; a.grad_loss = d->fused_grad_loss; a.loss = d->fused_totals ? nullptr : d->fused_loss;
     a.image_weight = d->fused_image_weight; a.contour = d->fused_gt ? d->fused_contour : 0.f; a.ltot = w.ltot;
     if (d->fused_gt && d->fused_totals) { a.options |= MM_INT_DEFERRED; a.ltot = reinterpret_cast<const long long*>(d->fused_totals); }   // (deferred fusion: see BwdArgs::ltot)
+    if (index_table) a.ltot = reinterpret_cast<const long long*>(index_table);    // (indexed calls are never fused: see indexed_table)
     a.items = w.items; a.nitems = w.nitems; a.part = w.part; a.item_cap = w.item_cap;
     a.plan_chunkmap = w.chunkmap; a.plan_items = w.items; a.plan_nitems = w.nitems; a.plan_wgs = d->F > 4096 ? MM_PLAN_WGS : 1;
     a.ntx = (d->Wt + MM_TS - 1) / MM_TS; a.nty = (d->Ht + MM_TS - 1) / MM_TS;
     a.grad_textures = g->grad_textures;
     // step mode (MMRenderDesc.step_grads): the forward's epilogue has left everything the pixel pass leaves -- there is no pixel launch, and
     // the gather reads the run list and forms dL/dalpha itself (the profiling slot stays readable: an empty bracket)
-    const bool step = views == 1 && render_step_mode(d, w);
+    const bool step = views == 1 && !index_table && render_step_mode(d, w);
     const StepArgs sa = {w.runs, w.runcap, w.rcur};
     if (step) { ProfScope p(d->prof_events, MM_PROF_PIXEL_BWD, s); }
     else {

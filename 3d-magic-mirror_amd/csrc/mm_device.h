@@ -465,6 +465,15 @@ inline int launch_ok(const char* what) {
 // errors left behind by the caller's own earlier runtime calls (e.g. hipEventQuery -> hipErrorNotReady) are not ours
 inline void clear_stale_error() { (void)hipGetLastError(); }
 
+// ---- indexed calls (mm_render_indexed_*, mm_indexed.hip): image b reads row table[t][b] of tensor t -------------------------------------
+// The plan's table is (5, M) int32 in the workspace's head: the sanitised rows of vertices, textures, lights and bg (always valid rows), then
+// the images' bad flags (an index entry was out of range: the image is stored as NaN / face_idx -1 and left out of every gradient sum).
+enum { MM_IX_VERTICES = 0, MM_IX_TEXTURES = 1, MM_IX_LIGHTS = 2, MM_IX_BG = 3, MM_IX_BAD = 4 };
+__device__ inline int index_row(const int* table, int M, int t, int b) { return table[(size_t)t * M + b]; }
+struct IndexPlan {                 // the plan's arrays (mm_abi.hip carves them): the table; per tensor the CSR of the backward's sum and its fill cursors
+    int* table; int* offsets[4]; int* cursor[4]; int* images[4];
+};
+
 // number of set bits of a ballot below this lane: two v_mbcnt instructions (a 64-bit shift/and/popcount sequence costs ~10x)
 __device__ inline int ballot_rank(uint64_t bal) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));

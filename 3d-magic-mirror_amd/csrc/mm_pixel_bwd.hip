@@ -23,7 +23,9 @@ namespace mm {
 // that kernel would have written -- plus the caller's grad_rgba if there is one.  Never together with kContour.
 // kViews: a multi-view call (BwdArgs::views > 1; never fused): bg, lights and textures are read from the image's SAMPLE (row b / views); what is
 // written -- grad_bg included -- stays per image.  mm_render_backward launches the kViews = false instantiations, which hold none of that code.
-template <bool kNoMask, bool kContour, bool kDeferred, bool kViews>
+// kIndexed: an indexed call (mm_render_indexed_backward; never fused, one view): bg, lights and textures are read from the image's rows in the plan's
+// table, which travels in BwdArgs::ltot (indexed_table).  A trailing parameter: every other instantiation keeps its code.
+template <bool kNoMask, bool kContour, bool kDeferred, bool kViews, bool kIndexed = false>
 __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) {
     __shared__ float s_dl[MM_BLOCK_WAVES][9];
     __shared__ float s_gm[MM_BLOCK_WAVES][2];
@@ -43,6 +45,9 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     const size_t hw = (size_t)a.H * a.W, pin = (size_t)py * a.W + px;
     const size_t pix = (size_t)b * hw + pin;
     const int sb = kViews ? b / a.views : b;                      // the row of the per-sample inputs
+    const int sb_t = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_TEXTURES, b) : sb;
+    const int sb_l = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_LIGHTS, b) : sb;
+    const int sb_g = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_BG, b) : sb;
     if (blk == 0 && threadIdx.x == 0) a.ticket[b] = 0u;           // arrival counter of the vertex backward, used after this kernel
     // The pass is a chain of dependent trips to memory; it is written so that four remain: (1) everything addressed by the pixel
     // alone -- face_idx, prediction, ground truth, background; (2) what the winner's id addresses -- geometry, normal, corner uvs;
@@ -51,7 +56,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     float bgv[3] = {0.f, 0.f, 0.f};
     if (kNoMask && in_img) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)sb * 3 + c) * hw + pin];
+        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)sb_g * 3 + c) * hw + pin];
     }
     float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
     int hf = -1;
@@ -133,7 +138,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
     const bool any_covered = __ballot(in_img && hf >= 0) != 0;   // wave-uniform
     if (!any_covered) {
         if (kNoMask && in_img) {
-            const float* L = a.lights + sb * 9;                  // (bands 0 and 6 only: the same lights whatever the band order)
+            const float* L = a.lights + sb_l * 9;                 // (bands 0 and 6 only: the same lights whatever the band order)
             const float coef = MM_SH_C0 * L[0] + (0.f - MM_SH_C6B) * L[6];
             float gbg[3];
             dcs = pixel_pass_background<kDeferred>(pl, fused, bgv, coef, gbg);      // (normal 0: bands 0 and 6 only)
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
             const int cy0 = min(max(s.y0, 0), a.Ht - 1), cy1 = min(max(s.y1, 0), a.Ht - 1);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float* tex = a.textures + ((size_t)sb * 3 + c) * a.Ht * a.Wt;
+                const float* tex = a.textures + ((size_t)sb_t * 3 + c) * a.Ht * a.Wt;
                 tq[c][0] = tex[(size_t)cy0 * a.Wt + cx0]; tq[c][1] = tex[(size_t)cy0 * a.Wt + cx1];
                 tq[c][2] = tex[(size_t)cy1 * a.Wt + cx0]; tq[c][3] = tex[(size_t)cy1 * a.Wt + cx1];
             }
@@ -186,7 +191,7 @@ __global__ __launch_bounds__(256, MM_PIXEL_LB) void pixel_bwd_kernel(BwdArgs a) 
         sh_bands(nx, ny, nz, bnd);
         float L[9];                                              // lights in sh_bands' order (see shade_store)
 #pragma unroll
-        for (int i = 0; i < 9; ++i) L[i] = a.lights[sb * 9 + i];
+        for (int i = 0; i < 9; ++i) L[i] = a.lights[sb_l * 9 + i];
         if (a.options & MM_OPT_SH_ORDER_XYZ) { const float tmp = L[2]; L[2] = L[3]; L[3] = tmp; }
         float coef = 0.f;
 #pragma unroll
@@ -291,6 +296,11 @@ int launch_pixel_bwd(const BwdArgs& a, const MMRenderDesc* d, hipStream_t s) {
     ProfScope p(d->prof_events, MM_PROF_PIXEL_BWD, s);
     dim3 grid(a.blocks_per_image * d->B + a.plan_wgs * d->B);    // + the plan workgroups, in front
     const bool contour = a.gt != nullptr && a.contour > 0.f;
+    if (a.views == 0) {                                          // indexed (BwdArgs::views; never fused: mm_render_indexed_backward refuses it)
+        if (d->no_mask) hipLaunchKernelGGL((pixel_bwd_kernel<true, false, false, false, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, false, false, true>), grid, dim3(256), 0, s, a);
+        return MM_OK;
+    }
     if (a.views > 1) {                                           // multi-view (never fused: mm_render_views_backward refuses it)
         if (d->no_mask) hipLaunchKernelGGL((pixel_bwd_kernel<true, false, false, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((pixel_bwd_kernel<false, false, false, true>), grid, dim3(256), 0, s, a);

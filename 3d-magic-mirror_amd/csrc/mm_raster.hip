@@ -41,12 +41,15 @@ namespace mm {
 // kContour: the fused loss carries recon_data's contour term (host: fused_gt && fused_contour > 0)
 // kViews: a multi-view call (mm_render_views_forward, RasterArgs::views > 1; never with the fused loss): the shade epilogue reads bg, lights and
 // textures from the image's sample.  The instantiations mm_render_forward launches are the kViews = false ones and hold none of that code.
+// kIndexed: an indexed call (mm_render_indexed_forward, RasterArgs::ltot = the plan's table; never fused, one view, no step mode): the shade epilogue
+// reads bg, lights and textures from the image's rows in the table and stores a bad image as NaN.  A trailing parameter: every other instantiation
+// keeps its code.
 // kStep: step mode (MMRenderDesc.step_grads; kBlock, per-batch walk, no contour, one view): the epilogues run the backward's pixel pass
 // (step_pixel_pass, mm_raster_common.h) and the grid's first workgroups plan the backward's face sweep over the stage's LDS.
 #ifndef MM_RASTER_WPE_STEP
 #define MM_RASTER_WPE_STEP 4              // the pixel pass's live values on top of the epilogue's: 128 VGPRs (see profiles/fused_step_kernel_stats.md)
 #endif
-template <bool kNoMask, bool kBlock, bool kQueue, bool kContour, bool kViews, bool kStep = false>
+template <bool kNoMask, bool kBlock, bool kQueue, bool kContour, bool kViews, bool kStep = false, bool kIndexed = false>
 __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_eu(kStep ? MM_RASTER_WPE_STEP : MM_RASTER_WPE, kStep ? MM_RASTER_WPE_STEP : MM_RASTER_WPE))) void raster_fwd_kernel(RasterArgs a_) {   // kBlock: 5 waves per SIMD = 96 VGPRs, 5 x 32 KiB LDS per CU
 #ifndef __HIP_DEVICE_COMPILE__
     const RasterArgs& a = a_;
@@ -84,7 +87,7 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
         if (j >= W1) {                                           // (interleaving the two kinds of workgroup evenly was measured: no gain at 512x512,
             if (j - W1 >= W2) return;                            //  slower at 128x128, where every walking workgroup is resident from the start)
             const int e0 = nne + (j - W1) * per + wv * 4, ne = min(4, 4 * a.blocks_per_image - e0);
-            if (ne > 0) shade_empty_tiles<kNoMask, kContour, kViews, kStep>(a, b, e0, ne, threadIdx.x & 63);
+            if (ne > 0) shade_empty_tiles<kNoMask, kContour, kViews, kStep, kIndexed>(a, b, e0, ne, threadIdx.x & 63);
             return;
         }
         rank = j;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(kBlock ? 256 : 64) __attribute__((amdgpu_waves_per_
         if (kQueue) tile_walk(a, t, &s_stage[wv], key, ss);
         else tile_walk_batch(a, t, &s_stage[wv], key, ss);
     }
-    shade_store<kNoMask, kContour, kViews, kStep>(a, t, key, ss);
+    shade_store<kNoMask, kContour, kViews, kStep, kIndexed>(a, t, key, ss);
     flush_taken_last(a, t, &s_stage[(kBlock && coop) ? 0 : wv]);
 }
 
@@ -228,9 +231,10 @@ const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nh
     return order;
 }
 
-int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views) {
+int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views, const int* index_table) {
     RasterArgs a = make_raster_args(d, w);
     a.views = views;
+    if (index_table) a.ltot = reinterpret_cast<long long*>(const_cast<int*>(index_table));   // (indexed calls: see indexed_table; views == 1, no fused loss)
     a.order = launch_order(a, w.order, w.nheavy, w.bincount, d->B, d->prof_events, s);     // heavy-first launch order
     a.spread = walk_spread(a);
     a.nheavy = w.nheavy;
@@ -240,7 +244,7 @@ int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, 
     // 8-pixel bins: the bin is the tile, nothing to compact -> the per-batch walk, no face flags (every face gets its sweep items)
     const bool queue = walk_queue_mode(a);
     if (!queue) a.fflag = nullptr;
-    if (views == 1 && render_step_mode(d, w)) {                  // step mode: + the pixel pass in the epilogues, + the plan workgroups behind the walk
+    if (views == 1 && !index_table && render_step_mode(d, w)) {  // step mode: + the pixel pass in the epilogues, + the plan workgroups behind the walk
         a.step = 1;
         a.grad_loss = d->fused_grad_loss; a.image_weight = d->fused_image_weight;
         a.grad_bg = d->step_grads->grad_bg; a.gp = w.gp; a.gp2 = w.gp2; a.dl_tile = w.dl_tile; a.gmax = w.gmax;
@@ -254,7 +258,8 @@ int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, 
         return launch_ok("raster_fwd");
     }
 #define MM_LAUNCH_RASTER2(NM, BL, QU, CO, VI) hipLaunchKernelGGL((raster_fwd_kernel<NM, BL, QU, CO, VI>), grid, dim3(BL ? 256 : 64), 0, s, a)
-#define MM_LAUNCH_RASTER(NM, BL, QU) do { if (views > 1) MM_LAUNCH_RASTER2(NM, BL, QU, false, true); else if (a.contour > 0.f) MM_LAUNCH_RASTER2(NM, BL, QU, true, false); \
+#define MM_LAUNCH_RASTER(NM, BL, QU) do { if (index_table) hipLaunchKernelGGL((raster_fwd_kernel<NM, BL, QU, false, false, false, true>), grid, dim3(BL ? 256 : 64), 0, s, a); \
+                                          else if (views > 1) MM_LAUNCH_RASTER2(NM, BL, QU, false, true); else if (a.contour > 0.f) MM_LAUNCH_RASTER2(NM, BL, QU, true, false); \
                                           else MM_LAUNCH_RASTER2(NM, BL, QU, false, false); } while (0)
     if (block) {
         if (queue) { if (d->no_mask) MM_LAUNCH_RASTER(true, true, true); else MM_LAUNCH_RASTER(false, true, true); }

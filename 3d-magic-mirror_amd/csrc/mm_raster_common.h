@@ -56,6 +56,10 @@ struct RasterArgs {
     int2* plan_chunkmap; int2* plan_items; int2* plan_nitems;
 };
 
+// indexed calls (kIndexed instantiations; never fused, so the fused sums' pointer is free): RasterArgs::ltot carries the plan's table (mm_device.h:
+// index_row) -- one more pointer in this struct would move the members behind it for every kernel that takes it
+__device__ inline const int* indexed_table(const RasterArgs& a) { return reinterpret_cast<const int*>(a.ltot); }
+
 // order-preserving bits of a ground-truth mask value (0 is kept for "none"): the step epilogue leaves the two extremes of an image's uncovered
 // pixels with integer atomic maxima -- of mask_ord(gm) and of ~mask_ord(gm)
 __device__ inline unsigned mask_ord(float v) {
@@ -521,10 +525,16 @@ __device__ inline void step_pixel_pass(const RasterArgs& a, const TileCtx& t, in
 // above) -- no further load, one returning atomic for its record slots -- and the per-tile counts at the end are not taken.
 // kContour: the fused loss carries recon_data's contour term (a.contour > 0; chosen by the host -- the reference's default is none, train.py:115)
 // kViews: a multi-view call -- the per-sample inputs (bg, lights, textures) are addressed by the image's SAMPLE, a wave-uniform division per tile
-template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false>
+// kIndexed: an indexed call (mm_render_indexed_forward; never fused, never with kViews or kStep) -- textures, lights and bg are addressed by the
+// image's rows in the plan's table (indexed_table: wave-uniform loads per tile), and a bad image is stored as NaN / face_idx -1
+template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false, bool kIndexed = false>
 __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsigned long long key, const SoftState& ss) {
     if (!t.in_img && !a.gt) return;
     const int sb = kViews ? t.b / a.views : t.b;                 // the row of the per-sample inputs
+    const int sb_t = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_TEXTURES, t.b) : sb;
+    const int sb_l = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_LIGHTS, t.b) : sb;
+    const int sb_g = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_BG, t.b) : sb;
+    const bool bad = kIndexed && index_row(indexed_table(a), a.B, MM_IX_BAD, t.b) != 0;
     const int cpx = min(t.px, a.W - 1), cpy = min(t.py, a.H - 1);
     const size_t pix = ((size_t)t.b * a.H + cpy) * a.W + cpx;
     const size_t hw = (size_t)a.H * a.W, pin = (size_t)cpy * a.W + cpx;
@@ -535,7 +545,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     float bgv[3] = {0.f, 0.f, 0.f}, gtv[4] = {0.f, 0.f, 0.f, 0.f};
     if (kNoMask) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)sb * 3 + c) * hw + pin];
+        for (int c = 0; c < 3; ++c) bgv[c] = a.bg[((size_t)sb_g * 3 + c) * hw + pin];
     }
     if (a.gt) {                                                  // (clamped pixel: a valid address in every lane)
 #pragma unroll
@@ -558,7 +568,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     float out[4];
     float L[9];                                                  // lights in the order of sh_bands (x, z, y): MM_OPT_SH_ORDER_XYZ pairs
 #pragma unroll                                                   // the user's lights 2 / 3 with the y / z bands instead
-    for (int i = 0; i < 9; ++i) L[i] = a.lights[sb * 9 + i];
+    for (int i = 0; i < 9; ++i) L[i] = a.lights[sb_l * 9 + i];
     if (a.options & MM_OPT_SH_ORDER_XYZ) { const float tmp = L[2]; L[2] = L[3]; L[3] = tmp; }
     PixelShade sh;                                               // (step mode: what the pixel pass takes over; dead otherwise)
     Bilin s;
@@ -599,7 +609,7 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
         const int cy0 = min(max(s.y0, 0), a.Ht - 1), cy1 = min(max(s.y1, 0), a.Ht - 1);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float* tex = a.textures + ((size_t)sb * 3 + c) * a.Ht * a.Wt;
+            const float* tex = a.textures + ((size_t)sb_t * 3 + c) * a.Ht * a.Wt;
             tq[c][0] = tex[(size_t)cy0 * a.Wt + cx0]; tq[c][1] = tex[(size_t)cy0 * a.Wt + cx1];
             tq[c][2] = tex[(size_t)cy1 * a.Wt + cx0]; tq[c][3] = tex[(size_t)cy1 * a.Wt + cx1];
         }
@@ -633,6 +643,10 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
     }
     const float keepprod = ss.zeros > 0 ? 0.f : ss.qnz;
     out[3] = (h.f >= 0) ? 1.f : (1.f - keepprod);
+    if (kIndexed && bad) {                                       // (wave-uniform) an index entry of this image was out of range: nothing of it is an image
+        out[0] = out[1] = out[2] = out[3] = __uint_as_float(0x7FC00000u);
+        h.f = -1;
+    }
     if (t.in_img) {
         *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], out[3]);
         a.face_idx[pix] = h.f;
@@ -693,15 +707,18 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
 // work.  Here the four tiles' loads are in flight together.  Per pixel exactly what shade_store's uncovered-tile path computes
 // (m = 0, n = 0, soft-mask state "nothing taken"); the four tiles' recon_data terms go to ltot as one exact integer add per sum.
 // Step mode: each of the four tiles also gets the pixel pass of a tile without a covered pixel (dL/dbg, the two constant light bands, its row).
-template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false>
+template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false, bool kIndexed = false>
 __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int ne, int lane) {
     const int nslot = 4 * a.blocks_per_image;
     const int sb = kViews ? b / a.views : b;                     // the row of the per-sample inputs (lights, bg)
+    const int sb_l = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_LIGHTS, b) : sb;      // (indexed calls: see shade_store)
+    const int sb_g = kIndexed ? index_row(indexed_table(a), a.B, MM_IX_BG, b) : sb;
+    const bool bad = kIndexed && index_row(indexed_table(a), a.B, MM_IX_BAD, b) != 0;
     const size_t hw = (size_t)a.H * a.W;
     unsigned sl[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) sl[q] = a.order[(size_t)b * nslot + min(e0 + q, nslot - 1)] & 0x7FFFu;
-    const float coef = MM_SH_C0 * a.lights[sb * 9] + (0.f - MM_SH_C6B) * a.lights[sb * 9 + 6];   // (bands 0 and 6: the same lights whatever the band order)
+    const float coef = MM_SH_C0 * a.lights[sb_l * 9] + (0.f - MM_SH_C6B) * a.lights[sb_l * 9 + 6];   // (bands 0 and 6: the same lights whatever the band order)
     bool in[4];
     size_t pin[4];
     float bgv[4][3], gtv[4][4];
@@ -713,7 +730,7 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
         in[q] = q < ne && px < a.W && py < a.H;
         pin[q] = (size_t)min(py, a.H - 1) * a.W + min(px, a.W - 1);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) bgv[q][c] = kNoMask ? a.bg[((size_t)sb * 3 + c) * hw + pin[q]] : 0.f;
+        for (int c = 0; c < 3; ++c) bgv[q][c] = kNoMask ? a.bg[((size_t)sb_g * 3 + c) * hw + pin[q]] : 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) gtv[q][c] = a.gt ? a.gt[((size_t)b * 4 + c) * hw + pin[q]] : 0.f;
     }
@@ -742,7 +759,8 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
         }
         if (!in[q]) continue;
         const size_t pix = (size_t)b * hw + pin[q];
-        *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], 1.f - 1.f);
+        if (kIndexed && bad) { const float nan = __uint_as_float(0x7FC00000u); *(float4*)(a.rgba + pix * 4) = make_float4(nan, nan, nan, nan); }
+        else *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], 1.f - 1.f);
         a.face_idx[pix] = -1;
         a.soft[pix] = make_float2(1.f, __int_as_float(0x7FFFFFFF));
         if (a.imnormal) { a.imnormal[pix * 3] = 0.f; a.imnormal[pix * 3 + 1] = 0.f; a.imnormal[pix * 3 + 2] = 0.f; }

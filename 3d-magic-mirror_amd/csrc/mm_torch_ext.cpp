@@ -1,4 +1,5 @@
-// mm_torch_ext.cpp -- the autograd nodes of the class API (DiffRender.render / render_views / render_geometry / recon_data / render_recon).
+// mm_torch_ext.cpp -- the autograd nodes of the class API (DiffRender.render / render_views / render_indexed / render_geometry / recon_data /
+// render_recon).
 //
 // The C ABI of libmm_render.so stays the boundary; this file is PLUMBING above it, compiled with the host compiler only (no device
 // code, no HIP headers): one C++ call per autograd node allocates the outputs with ATen, fills the descriptor and enqueues the
@@ -67,6 +68,8 @@ typedef size_t (*recon_ws_t)(const MMReconDesc*);
 typedef int (*render_status_t)(const MMRenderDesc*, void*, int32_t*);
 typedef int (*views_fwd_t)(const MMRenderViewsDesc*, void*);
 typedef int (*views_bwd_t)(const MMRenderViewsDesc*, const MMRenderGrads*, void*);
+typedef int (*indexed_fwd_t)(const MMRenderIndexedDesc*, void*);
+typedef int (*indexed_bwd_t)(const MMRenderIndexedDesc*, const MMRenderGrads*, void*);
 
 const float* fptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 float* mptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
@@ -499,6 +502,115 @@ class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
     }
 };
 
+// DiffRender.render_indexed (MMRenderIndexedDesc: M images in one pass, each reading the row of vertices / textures / lights / bg its index names;
+// the gradients of those four are the sums over each row's images in ascending image order and have the inputs' own shapes).  The prototype is the
+// MMRenderDesc of the M images; an index is an (M) int32 tensor on the device or undefined (the identity).  backward: an input requires grad -- only
+// then does the workspace (ws_bytes, sized by the caller for that flag) hold the staging areas.  head_bytes: the workspace's head (plan + staging),
+// which mm_render_status skips; status_word: the address the plan adds its count of out-of-range index entries to.
+struct IndexTensors { at::Tensor t[4]; };
+void bind_indexed(MMRenderIndexedDesc& vd, const MMRenderDesc& d, const DenseInputs& in, const IndexTensors& ix, bool backward, int64_t status_word) {
+    vd.render = d;
+    vd.rows[0] = (int32_t)in.vertices.size(0); vd.rows[1] = (int32_t)in.textures.size(0); vd.rows[2] = (int32_t)in.lights.size(0);
+    vd.rows[3] = in.bg.defined() ? (int32_t)in.bg.size(0) : d.B;
+    for (int k = 0; k < 4; ++k) vd.index[k] = ix.t[k].defined() ? ix.t[k].data_ptr<int32_t>() : nullptr;
+    vd.backward = backward ? 1 : 0;
+    vd.status_flag = (int32_t*)status_word;
+}
+
+class RenderIndexedNode : public torch::autograd::Function<RenderIndexedNode> {
+ public:
+    static tensor_list forward(AutogradContext* ctx, int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t ws_bytes, int64_t head_bytes,
+                               int64_t status_word, bool backward, at::Tensor vertices, at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg,
+                               at::Tensor azimuths, at::Tensor elevations, at::Tensor distances, at::Tensor biases, c10::optional<at::Tensor> idx_vertices,
+                               c10::optional<at::Tensor> idx_textures, c10::optional<at::Tensor> idx_lights, c10::optional<at::Tensor> idx_bg,
+                               bool want_imnormal) {
+        TORCH_CHECK(azimuths.is_cuda(), "the MI355X render path needs tensors in device memory; there is no CPU fallback");
+        const c10::Device dev = azimuths.device();
+        const DeviceGuard guard(dev);
+        MMRenderDesc d = proto_desc(proto);                          // (of the M images)
+        const int64_t M = d.B, H = d.H, W = d.W;
+        save_camera_shapes(ctx, azimuths, elevations, distances, biases);
+        DenseInputs in;
+        in.vertices = dense_f32(vertices, dev, "vertices"); in.textures = dense_f32(textures, dev, "textures"); in.lights = dense_f32(lights, dev, "lights");
+        if (bg.has_value() && bg->defined()) in.bg = dense_f32(*bg, dev, "bg");
+        in.azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); in.elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
+        in.distances = dense_f32(distances, dev, "distances").reshape({-1}); in.biases = dense_f32(biases, dev, "biases").reshape({-1, 2});
+        TORCH_CHECK(in.azimuths.size(0) == M && in.elevations.size(0) == M && in.distances.size(0) == M && in.biases.size(0) == M,
+                    "render_indexed: the cameras must hold M = ", M, " values each (biases M pairs)");
+        TORCH_CHECK(in.vertices.dim() == 3 && in.vertices.size(0) >= 1 && in.vertices.size(1) == d.V && in.vertices.size(2) == 3, "vertices must be (R,", d.V, ",3), got ", in.vertices.sizes());
+        TORCH_CHECK(in.textures.dim() == 4 && in.textures.size(0) >= 1 && in.textures.size(1) == 3 && in.textures.size(2) == d.Ht && in.textures.size(3) == d.Wt,
+                    "textures must be (R,3,", d.Ht, ",", d.Wt, "), got ", in.textures.sizes());
+        TORCH_CHECK(in.lights.dim() == 2 && in.lights.size(0) >= 1 && in.lights.size(1) == 9, "lights must be (R,9), got ", in.lights.sizes());
+        TORCH_CHECK(!d.no_mask || (in.bg.defined() && in.bg.dim() == 4 && in.bg.size(0) >= 1 && in.bg.size(1) == 3 && in.bg.size(2) == H && in.bg.size(3) == W),
+                    "bg must be (R,3,", H, ",", W, ")");
+        IndexTensors ix;
+        const c10::optional<at::Tensor>* given[4] = {&idx_vertices, &idx_textures, &idx_lights, &idx_bg};
+        for (int k = 0; k < 4; ++k) {
+            if (!given[k]->has_value() || !(*given[k])->defined() || (k == 3 && !d.no_mask)) continue;
+            const at::Tensor& t = **given[k];
+            TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.dim() == 1 && t.size(0) == M,
+                        "render_indexed: an index must be a contiguous (", M, ") int32 tensor in device memory");
+            ix.t[k] = t;
+        }
+        auto opts = in.vertices.options();
+        at::Tensor rgba = at::empty({M, H, W, 4}, opts), fn = at::empty({M, (int64_t)d.F, 3}, opts);
+        at::Tensor face_idx = at::empty({M, H, W}, opts.dtype(at::kInt));
+        at::Tensor imn = want_imnormal ? at::empty({M, H, W, 3}, opts) : at::empty({0}, opts);
+        at::Tensor ws = at::empty({ws_bytes}, opts.dtype(at::kByte));
+        bind_inputs(d, in); bind_workspace(d, ws);
+        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
+        MMRenderIndexedDesc vd{};
+        bind_indexed(vd, d, in, ix, backward, status_word);
+        check(((indexed_fwd_t)f_fwd)(&vd, current_stream(dev)), "mm_render_indexed_forward");
+        ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto;
+        ctx->saved_data["head_bytes"] = head_bytes; ctx->saved_data["status_word"] = status_word; ctx->saved_data["backward"] = backward;
+        tensor_list saved = in.list();                               // (the UN-gathered inputs)
+        saved.insert(saved.end(), {face_idx, fn, ws, at::Tensor(), ix.t[0], ix.t[1], ix.t[2], ix.t[3]});     // (enum Saved, then the four indices)
+        ctx->save_for_backward(saved);
+        ctx->mark_non_differentiable({face_idx, imn});
+        ctx->set_materialize_grads(false);
+        return {rgba, fn, imn, face_idx};
+    }
+
+    static tensor_list backward(AutogradContext* ctx, tensor_list g) {
+        const auto sv = ctx->get_saved_variables();
+        const DenseInputs in = saved_inputs(sv);
+        const c10::Device dev = in.azimuths.device();
+        const DeviceGuard guard(dev);
+        TORCH_CHECK(ctx->saved_data["backward"].toBool(), "render_indexed: the forward ran without an input that requires grad and kept no staging");
+        MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
+        const int64_t M = d.B;
+        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
+        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
+        d.rgba = nullptr; d.imnormal = nullptr;
+        at::Tensor grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({M, (int64_t)d.H, (int64_t)d.W, 4}, in.vertices.options());
+        at::Tensor gfn;
+        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
+        RenderGrads gr(in, d.no_mask, grgba, gfn);                   // (the indexed inputs' gradients in the inputs' own shapes)
+        void* stream = current_stream(dev);
+        IndexTensors ix;
+        for (int k = 0; k < 4; ++k) ix.t[k] = sv[S_GT + 1 + k];
+        MMRenderIndexedDesc vd{};
+        bind_indexed(vd, d, in, ix, true, ctx->saved_data["status_word"].toInt());
+        check(((indexed_bwd_t)ctx->saved_data["f_bwd"].toInt())(&vd, &gr.abi, stream), "mm_render_indexed_backward");
+        // per IMAGE, as in render: the render workspace of the M images lies behind the head of the indexed workspace
+        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, M, (size_t)ctx->saved_data["head_bytes"].toInt(),
+                              "mm_render_indexed_backward", "images");
+        restore_camera_shapes(ctx, gr);
+        // one entry per forward argument: eight non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, four indices, want_imnormal
+        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr.vertices, gr.textures, gr.lights,
+                gr.bg, gr.azimuths, gr.elevations, gr.distances, gr.biases, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+tensor_list render_indexed_node(int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t ws_bytes, int64_t head_bytes, int64_t status_word,
+                                bool backward, at::Tensor vertices, at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths,
+                                at::Tensor elevations, at::Tensor distances, at::Tensor biases, c10::optional<at::Tensor> idx_vertices,
+                                c10::optional<at::Tensor> idx_textures, c10::optional<at::Tensor> idx_lights, c10::optional<at::Tensor> idx_bg, bool want_imnormal) {
+    return RenderIndexedNode::apply(f_fwd, f_bwd, f_status, proto, ws_bytes, head_bytes, status_word, backward, vertices, textures, lights, bg, azimuths, elevations,
+                                    distances, biases, idx_vertices, idx_textures, idx_lights, idx_bg, want_imnormal);
+}
+
 tensor_list render_views_node(int64_t f_fwd, int64_t f_bwd, int64_t f_status, std::string proto, int64_t views, int64_t ws_bytes, int64_t staging_bytes,
                               at::Tensor vertices, at::Tensor textures, at::Tensor lights, c10::optional<at::Tensor> bg, at::Tensor azimuths,
                               at::Tensor elevations, at::Tensor distances, at::Tensor biases, bool want_imnormal) {
@@ -575,6 +687,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("recon_data", &recon_node);
     m.def("render_geometry", &geometry_node);
     m.def("render_views", &render_views_node);
+    m.def("render_indexed", &render_indexed_node);
     m.def("desc_bytes", []() { return (int64_t)sizeof(MMRenderDesc); });
     m.def("deferrable", [](at::Tensor pred) { return deferrable_render(pred) != nullptr; });   // tests / diagnostics: would recon_data(pred, .) defer?
 }

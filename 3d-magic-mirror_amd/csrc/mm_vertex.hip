@@ -12,15 +12,29 @@
 // mm_vertex_views.hip with MM_VERTEX_VIEWS defined -- the same kernels under the names *_views, in which image b reads the vertices of
 // SAMPLE b / views (multi-view calls, mm_render_views_*: `vertices` holds B / views rows).  A second compilation instead of a template
 // parameter: the first one then sees unchanged tokens, and its kernels keep their symbols and their machine code to the instruction
-// (tools/kernel_disasm_diff.py).
+// (tools/kernel_disasm_diff.py).  And a THIRD time through mm_vertex_indexed.hip with MM_VERTEX_INDEXED defined -- the names *_indexed, in which
+// image b reads the vertices of row vrow[b], the plan's sanitised table (indexed calls, mm_render_indexed_*); only that compilation's argument
+// structs carry the table's pointer, and its launchers take it in the place of the view count.
 #include "mm_device.h"
 
-#ifdef MM_VERTEX_VIEWS
+#if defined(MM_VERTEX_INDEXED)
+#define MM_VX(name) name##_indexed
+#define MM_VX_SAMPLE(b) (a.vrow[b])
+#define MM_VX_PARAM const int* vrow
+#define MM_VX_SET(a) do { (a).views = 1; (a).vrow = vrow; } while (0)
+#define MM_VX_ONE_VIEW true
+#elif defined(MM_VERTEX_VIEWS)
 #define MM_VX(name) name##_views
 #define MM_VX_SAMPLE(b) ((b) / a.views)
+#define MM_VX_PARAM int views
+#define MM_VX_SET(a) (a).views = views
+#define MM_VX_ONE_VIEW (views == 1)
 #else
 #define MM_VX(name) name
 #define MM_VX_SAMPLE(b) (b)
+#define MM_VX_PARAM int views
+#define MM_VX_SET(a) (a).views = views
+#define MM_VX_ONE_VIEW (views == 1)
 #endif
 
 namespace mm {
@@ -42,6 +56,9 @@ struct VertexFwdArgs {
     uint64_t* mask;          // (B,nbins,words) screen-bin candidate mask, written here (nullptr: not wanted)
     int* fflag;              // (B,F) "this face receives gradient from the pixels": cleared here, set by raster_fwd
     unsigned* ticket;        // (B) arrival counter of the vertex backward's workgroups: cleared here (and by its last workgroup after use)
+#ifdef MM_VERTEX_INDEXED
+    const int* vrow;         // (B) the row of `vertices` every image reads
+#endif
 };
 
 __device__ inline void block_camera(const float* azim, const float* elev, const float* dist, const float* bias, int b,
@@ -145,6 +162,9 @@ struct VertexBwdArgs {
     float* grad_lights;
     float* grad_vertices;
     float *grad_azim, *grad_elev, *grad_dist, *grad_bias;
+#ifdef MM_VERTEX_INDEXED
+    const int* vrow;        // (B) the row of `vertices` every image reads; the gradients stay per image
+#endif
 };
 
 #ifndef MM_VBWD_ROWS
@@ -553,12 +573,12 @@ __global__ __launch_bounds__(1024) void MM_VX(vertex_image_bwd_kernel)(VertexBwd
 int launch_vertex_fwd_views(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views);
 int launch_vertex_bwd_views(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views);
 
-int MM_VX(launch_vertex_fwd)(const MMRenderDesc* d, const Workspace& w, hipStream_t s, int views) {
-#ifndef MM_VERTEX_VIEWS
+int MM_VX(launch_vertex_fwd)(const MMRenderDesc* d, const Workspace& w, hipStream_t s, MM_VX_PARAM) {
+#if !defined(MM_VERTEX_VIEWS) && !defined(MM_VERTEX_INDEXED)
     if (views > 1) return launch_vertex_fwd_views(d, w, s, views);
 #endif
     VertexFwdArgs a;
-    a.views = views;
+    MM_VX_SET(a);
     a.B = d->B; a.V = d->V; a.F = d->F; a.H = d->H; a.W = d->W;
     a.proj0 = d->proj[0]; a.proj1 = d->proj[1]; a.proj2 = d->proj[2]; a.mult = d->multiplier; a.infl = d->boxlen * d->multiplier;
     a.faces = d->faces; a.vertices = d->vertices;
@@ -575,12 +595,12 @@ int MM_VX(launch_vertex_fwd)(const MMRenderDesc* d, const Workspace& w, hipStrea
     return launch_ok("vertex_fwd");
 }
 
-int MM_VX(launch_vertex_bwd)(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, int views) {
-#ifndef MM_VERTEX_VIEWS
+int MM_VX(launch_vertex_bwd)(const MMRenderDesc* d, const MMRenderGrads* g, const Workspace& w, hipStream_t s, MM_VX_PARAM) {
+#if !defined(MM_VERTEX_VIEWS) && !defined(MM_VERTEX_INDEXED)
     if (views > 1) return launch_vertex_bwd_views(d, g, w, s, views);
 #endif
     VertexBwdArgs a;
-    a.views = views;
+    MM_VX_SET(a);
     a.B = d->B; a.V = d->V; a.F = d->F;
     a.proj0 = d->proj[0]; a.proj1 = d->proj[1]; a.proj2 = d->proj[2];
     a.vc_table = (const int4*)d->vc_table; a.vc_stride = d->vc_stride; a.vertices = d->vertices;
@@ -589,7 +609,7 @@ int MM_VX(launch_vertex_bwd)(const MMRenderDesc* d, const MMRenderGrads* g, cons
     a.dTpart = w.dTpart; a.ticket = w.ticket;
     a.tcnt = w.tcnt; a.ntcnt = w.ntcnt;
     a.dl_part = w.dl_part; a.dl_tiles = 0; a.blocks_per_image = w.blocks_per_image; a.grad_lights = g->grad_lights;
-    if (views == 1 && !d->geometry_only && render_step_mode(d, w)) {
+    if (MM_VX_ONE_VIEW && !d->geometry_only && render_step_mode(d, w)) {
         // step mode: the light rows are the forward's, per tile; and what the forward left in the counters (the images' maxima, cursors and drop
         // counts) is READ by the backward, not consumed -- a second backward after the same forward finds it; the next forward clears it
         a.dl_part = w.dl_tile; a.dl_tiles = 1; a.ntcnt = 0;

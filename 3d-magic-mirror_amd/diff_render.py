@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's ``DiffRender`` (/root/reference/networks.py:164-491) over the gfx950 C ABI.
 
 Same constructor, attributes, method names, argument meaning and return values as the reference class, so a
-``trainer.py``-style loop can switch with ``from mm_amd import DiffRender``.  ``render``, ``render_views``, ``render_geometry``, ``render_recon``
+``trainer.py``-style loop can switch with ``from mm_amd import DiffRender``.  ``render``, ``render_views``, ``render_indexed``, ``render_geometry``, ``render_recon``
 and ``recon_data`` run the hand-written HIP kernels of ``lib/libmm_render.so`` through the C++ autograd nodes of
 ``lib/mm_torch_ext.so`` (csrc/mm_torch_ext.cpp); there is no CPU, eager-torch or Python-node fallback for them.  The mesh
 regularisers (``recon_flip``, ``calc_reg_*``) run as one HIP launch per direction (``mesh_reg.py``), and so
@@ -45,6 +45,54 @@ class _SplitBatchFn(torch.autograd.Function):
                 full.narrow(0, o, n).copy_(g)
             o += n
         return (full,) + (None,) * len(ctx.sizes)
+
+
+INDEXED = ('vertices', 'textures', 'lights', 'bg')             # the tensors a render_indexed image picks a row of, in the C ABI's order
+
+
+def grid_index(n_rows, n_cols):
+    """(row_of_image, col_of_image), two (n_rows * n_cols,) int64 CPU tensors, for the images of a row-major grid: image i sits in row
+    i // n_cols, column i % n_cols.  The rainbow sheet of show_rainbow2.py:376-399 (a row per texture, a column per shape) is
+    ``row, col = grid_index(n_textures, n_shapes)`` and ``index={"vertices": col, "lights": col, "textures": row}``."""
+    n_rows, n_cols = int(n_rows), int(n_cols)
+    if n_rows < 1 or n_cols < 1:
+        raise ValueError("grid_index needs at least one row and one column, got %d x %d" % (n_rows, n_cols))
+    i = torch.arange(n_rows * n_cols, dtype=torch.int64)
+    return torch.div(i, n_cols, rounding_mode="floor"), i % n_cols
+
+
+def check_render_index(index, rows, M):
+    """The `index` argument of render_indexed against the row counts `rows` ({name: R}, the call's tensors) and the image count M, on the
+    host: {name: None (the identity) | a device tensor as given (NOT validated: the plan kernel does that) | a validated (M,) int64 CPU tensor}.
+    ValueError for an unknown name, an identity over a tensor that does not hold M rows, a wrong length or an out-of-range host entry."""
+    index = dict(index or {})
+    for k in index:
+        if k not in INDEXED:
+            raise ValueError("render_indexed: index has no %r (the indexed tensors are %s)" % (k, ", ".join(INDEXED)))
+    out = {}
+    for k, R in rows.items():
+        v = index.get(k)
+        if v is None:
+            if R != M:
+                raise ValueError("render_indexed: %s holds %d rows for %d images and index[%r] is missing (a missing index is the identity)" % (k, R, M, k))
+            out[k] = None
+            continue
+        if torch.is_tensor(v) and v.device.type != "cpu":
+            if v.dim() != 1 or v.shape[0] != M or v.dtype not in (torch.int32, torch.int64):
+                raise ValueError("render_indexed: index[%r] must be an (%d,) int32 or int64 tensor, got %s %s" % (k, M, tuple(v.shape), v.dtype))
+            out[k] = v
+            continue
+        t = torch.as_tensor(np.asarray(v.detach().numpy() if torch.is_tensor(v) else v))
+        if t.dtype in (torch.float16, torch.float32, torch.float64, torch.bool) or t.is_complex():
+            raise ValueError("render_indexed: index[%r] must hold integers, got %s" % (k, t.dtype))
+        t = t.to(torch.int64)
+        if t.dim() != 1 or t.shape[0] != M:
+            raise ValueError("render_indexed: index[%r] must hold %d entries, one per image; got shape %s" % (k, M, tuple(t.shape)))
+        if M and (int(t.min()) < 0 or int(t.max()) >= R):
+            bad = int(((t < 0) | (t >= R)).nonzero()[0])
+            raise ValueError("render_indexed: index[%r][%d] = %d is outside the %d rows of %s" % (k, bad, int(t[bad]), R, k))
+        out[k] = t
+    return out
 
 
 class DiffRender(object):
@@ -145,8 +193,11 @@ class DiffRender(object):
     def _raise_if_records_were_dropped(self):
         n = self.poll_dropped_records()
         if n:
-            raise RuntimeError("an earlier mm_render_backward of this DiffRender dropped %d texture-gradient records (record pool overflow): the texture "
-                               "gradients of the affected images were NaN. Raise DiffRender.extra_texture_records_per_pixel." % n)
+            raise RuntimeError("an earlier call of this DiffRender added %d to its status word.  Two things count there and cannot be told apart "
+                               "afterwards: (1) a backward dropped that many texture-gradient records (record pool overflow; the texture gradients of the "
+                               "affected images were NaN: raise DiffRender.extra_texture_records_per_pixel), or (2) a render_indexed call found that many "
+                               "entries of a device index outside their tensor's rows (those images are NaN with face_idx -1 and take no part in "
+                               "any gradient: check the index tensors)." % n)
 
     def workspace_bytes(self, d):
         """Bytes of the render workspace for the shape in MMRenderDesc `d`: the library's minimum + the extra record pool asked for."""
@@ -293,6 +344,83 @@ class DiffRender(object):
             hit = int(N.lib().mm_render_views_query_workspace(ctypes.byref(vd))) - int(N.lib().mm_query_workspace(ctypes.byref(vd.render)))
             if hit < 0:
                 raise RuntimeError("mm_render_views_query_workspace refused the shape (%d images, %d views)" % (vd.render.B, views))
+            self._desc_cache[key] = hit
+        return hit
+
+    # ---- every image picks its rows (show_rainbow2.py:376-399 the rainbow sheets; networks.py:146-161 deep_copy(index=...) + render) ----
+    def render_indexed(self, no_mask=False, index=None, **attributes):
+        """``render`` of M images, each of which reads the row of ``vertices``, ``textures``, ``lights`` and ``bg`` that ``index`` names for it, as ONE
+        pass of the kernels -- nothing is gathered on the way in (csrc/mm_torch_ext.cpp: RenderIndexedNode; include/mm_render.h: MMRenderIndexedDesc).
+        The cameras are per image, (M,) / biases (M,2); the four indexed tensors carry row counts of their own.  ``index`` is a dict with any of
+        those four names; a missing name is the identity, and that tensor then needs M rows.  A value is a device tensor (int32 or int64:
+        converted on the device, NOT validated on the host -- an entry out of range makes its image NaN with face_idx -1, leaves it out of every
+        gradient sum, and raises on this object's next call) or a CPU tensor, list or numpy array (validated here with ValueError, then uploaded).
+        Returns (rgbs (M,4,H,W) -- the usual permuted view of NHWC memory --, attributes) with attributes['face_normals'] (M,F,3),
+        attributes['imnormal'] and self.last_face_idx (M,H,W).  Image i is bit-identical to image i of ``render`` on the tensors gathered with
+        index_select; the gradient of an indexed tensor has the tensor's own shape: row r's is the fp32 sum of the gradients of the images that
+        read it, in ascending image order (plain adds: bitwise reproducible), zeros for a row no image reads.
+        Not here: blending two rows inside the render (``mix_attributes``), the fused loss and step mode over indices."""
+        no_mask = bool(no_mask)
+        for k in ('vertices', 'textures', 'lights', 'azimuths', 'elevations', 'distances', 'biases'):
+            if not torch.is_tensor(attributes.get(k)):
+                raise TypeError("render_indexed needs attributes[%r] as a tensor" % k)
+        if no_mask and not torch.is_tensor(attributes.get('bg')):
+            raise TypeError("render_indexed(no_mask=True) needs attributes['bg'] (R,3,H,W)")
+        azimuths, elevations, distances, biases = (attributes[k] for k in ('azimuths', 'elevations', 'distances', 'biases'))
+        vertices, textures, lights = attributes['vertices'], attributes['textures'], attributes['lights']
+        bg = attributes['bg'] if no_mask else None
+        M = int(azimuths.numel())
+        if M < 1 or any(int(t.numel()) != M for t in (elevations, distances)) or int(biases.numel()) != 2 * M or biases.shape[-1] != 2:
+            raise ValueError("render_indexed: the cameras must hold one value per image (biases a pair): got azimuths %s, elevations %s, distances %s, "
+                             "biases %s" % tuple(tuple(t.shape) for t in (azimuths, elevations, distances, biases)))
+        if vertices.dim() != 3 or tuple(vertices.shape[1:]) != (self.num_vertices, 3) or vertices.shape[0] < 1:
+            raise ValueError("vertices must be (R,%d,3), got %s" % (self.num_vertices, tuple(vertices.shape)))
+        if textures.dim() != 4 or textures.shape[1] != 3 or textures.shape[0] < 1:
+            raise ValueError("textures must be (R,3,Ht,Wt), got %s" % (tuple(textures.shape),))
+        if lights.dim() != 2 or lights.shape[1] != 9 or lights.shape[0] < 1:
+            raise ValueError("lights must be (R,9), got %s" % (tuple(lights.shape),))
+        if bg is not None and (bg.dim() != 4 or tuple(bg.shape[1:]) != (3, self.render_height, self.image_size) or bg.shape[0] < 1):
+            raise ValueError("bg must be (R,3,%d,%d), got %s" % (self.render_height, self.image_size, tuple(bg.shape)))
+        rows = {'vertices': int(vertices.shape[0]), 'textures': int(textures.shape[0]), 'lights': int(lights.shape[0])}
+        if bg is not None:
+            rows['bg'] = int(bg.shape[0])
+        if M > 65535 or max(rows.values()) > 65535:
+            raise ValueError("render_indexed takes at most 65535 images and 65535 rows per tensor (got %d images, rows %s)" % (M, rows))
+        idx = check_render_index(index, rows, M)
+        self._raise_if_records_were_dropped()
+        N.require_device(azimuths, elevations, distances, biases, vertices, textures, lights, bg)
+        dev = azimuths.device
+        idx = {k: (None if v is None else v.to(device=dev, dtype=torch.int32).contiguous()) for k, v in idx.items()}
+        N.require_device(*[v for v in idx.values() if v is not None])
+        st = self._static(dev)
+        Ht, Wt = int(textures.shape[2]), int(textures.shape[3])
+        proto, nbytes = self._proto(st, M, no_mask, Ht, Wt)
+        backward = torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                                   for t in (vertices, textures, lights, bg, azimuths, elevations, distances, biases))
+        head = self._indexed_head_bytes(proto, tuple(rows.get(k, M) for k in INDEXED), backward)
+        self.last_indexed_workspace_bytes = nbytes + head         # (what the node allocates: the forward-only query when nothing requires grad)
+        rgba, fn, imn, face_idx = N.torch_ext().render_indexed(
+            N.fn_addr("mm_render_indexed_forward"), N.fn_addr("mm_render_indexed_backward"),
+            N.fn_addr("mm_render_status") if self.check_texture_records else 0, proto, nbytes + head, head, self._status_ptr(), bool(backward),
+            vertices, textures, lights, bg, azimuths, elevations, distances, biases, idx['vertices'], idx['textures'], idx['lights'], idx.get('bg'),
+            bool(self.emit_imnormal))
+        self._set_outputs(attributes, fn, imn, face_idx)
+        return rgba.permute(0, 3, 1, 2), attributes
+
+    def _indexed_head_bytes(self, proto, rows, backward):
+        """What an indexed workspace holds in front of the render workspace of its M images: the plan and, for a call with a backward, the
+        staging areas of the per-image gradients."""
+        key = ("indexed", proto, rows, bool(backward))
+        hit = self._desc_cache.get(key)
+        if hit is None:
+            vd = N.MMRenderIndexedDesc()
+            ctypes.memmove(ctypes.byref(vd), proto, len(proto))
+            for t in range(4):
+                vd.rows[t] = rows[t]
+            vd.backward = 1 if backward else 0
+            hit = int(N.lib().mm_render_indexed_query_workspace(ctypes.byref(vd))) - int(N.lib().mm_query_workspace(ctypes.byref(vd.render)))
+            if hit < 0:
+                raise RuntimeError("mm_render_indexed_query_workspace refused the shape (%d images, rows %s)" % (vd.render.B, rows))
             self._desc_cache[key] = hit
         return hit
 

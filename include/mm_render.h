@@ -238,6 +238,44 @@ int mm_render_views_forward(const MMRenderViewsDesc* desc, mm_stream_t stream);
 int mm_render_views_backward(const MMRenderViewsDesc* desc, const MMRenderGrads* grads, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Indexed render: M images in ONE pass of the render kernels, each of which picks its mesh, its texture, its lights and its background
+ * by a row index of its own.  The multi-view render above is the pattern "image i reads row i / N"; the reference renders a second one
+ * as often -- every texture on every shape (show_rainbow2.py:376-399), every deep_copy(Ae, index=...) followed by a render
+ * (networks.py:146-161, trainer.py:293-308), texture rows picked out of a pool with a row count of its own
+ * (generate_market_new_class9.py:331-336) -- and with mm_render_forward each costs a gathered copy of every tensor.
+ *   render   an MMRenderDesc of the M IMAGES (render.B = M): the four camera inputs and every output are per image, exactly as in
+ *            mm_render_forward; `vertices`, `textures`, `lights` and `bg` address tensors of rows[0..3] rows.  fused_gt, fused_totals and
+ *            geometry_only must be unset (MM_ERR_UNSUPPORTED); step_grads is ignored.
+ *   rows     {R_v, R_t, R_l, R_bg}, each >= 1 (R_bg is looked at under no_mask only).
+ *   index    per tensor (M) int32 in device memory: image i reads row index[t][i].  NULL: the identity, and rows[t] must equal M.
+ *   backward 0: a forward-only call -- the workspace holds no staging and mm_render_indexed_backward refuses it (MM_ERR_WORKSPACE).
+ *   status_flag  optional; device or pinned host memory.  The forward ADDS the number of index entries outside [0, rows[t]) to it.
+ * The forward's first launch turns the index tensors into a plan in the workspace's head (no host synchronisation, nothing read back):
+ * per tensor a sanitised table -- the only table a later kernel reads; an out-of-range entry becomes 0, is counted into the status
+ * word and marks its IMAGE bad -- and, for the backward, the rows' image lists (offsets, images in ascending image order, bad images left
+ * out).  A bad image gets rgba = NaN in all four channels and face_idx = -1; nothing is read through its raw index.
+ * Forward: a good image is bit-identical to image i of mm_render_forward on the tensors gathered with index_select.
+ * Backward: grad_rgba, grad_face_normals and the four camera gradients per IMAGE (bit-identical to mm_render_backward's; NaN for a bad
+ * image); grad_vertices, grad_textures, grad_lights, grad_bg shaped like the inputs, (rows[t],...): the kernels write the per-image
+ * gradients into staging areas of the workspace and one last launch adds up each row's list in ascending image order,
+ * ((g[i0] + g[i1]) + g[i2]) + ..., plain fp32 adds (no fma, no atomics): bitwise reproducible.  A row no image reads gets zeros.
+ * Workspace: the head -- the plan, and with `backward` the four staging areas of M rows each, as in the multi-view call -- then the render
+ * workspace of the M images with all the bytes that are left.  mm_render_status is asked with a copy of `render` whose workspace starts
+ * query - mm_query_workspace(&render) bytes in.  M <= 65535 and every rows[t] <= 65535 (MM_ERR_UNSUPPORTED; the query returns 0).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct MMRenderIndexedDesc {
+    MMRenderDesc render;
+    int32_t rows[4];
+    const int32_t* index[4];
+    int32_t backward;
+    int32_t* status_flag;
+} MMRenderIndexedDesc;
+
+size_t mm_render_indexed_query_workspace(const MMRenderIndexedDesc* desc);
+int mm_render_indexed_forward(const MMRenderIndexedDesc* desc, mm_stream_t stream);
+int mm_render_indexed_backward(const MMRenderIndexedDesc* desc, const MMRenderGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Reconstruction loss: replaces DiffRender.recon_data (networks.py:364-390) incl. kaolin mask_iou (:377) and the
  * optional contour term (:379-387):  loss = image_weight * mean|pred*gm+(1-gm) - (gt*gm+(1-gm))| + (1 - mean_b IoU_b)
  *                                           [+ contour * mean((c(pred_mask) - c(gt_mask))^2)].
@@ -874,7 +912,7 @@ const char* mm_last_error_detail(void);
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
- * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc (31 is unassigned). */
+ * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc (31 is unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -890,7 +928,8 @@ size_t mm_struct_size(int which);
  * existing field moves or changes meaning and NULL is the old behaviour; the struct grows by one pointer, which a binding built against the
  * shorter struct finds out from mm_struct_size(0), as every binding must check; still 9: MMBatchDesc and mm_assemble_batch, struct id 30, an
  * addition, detected by mm_struct_size(30) != 0; still 9: MMCompositeDesc and mm_composite_frames, struct id 32 -- id 31 stays unassigned and
- * returns 0 --, an addition, detected by mm_struct_size(32) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * returns 0 --, an addition, detected by mm_struct_size(32) != 0; still 9: MMRenderIndexedDesc and mm_render_indexed_*, struct id 33, an
+ * addition, detected by mm_struct_size(33) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
