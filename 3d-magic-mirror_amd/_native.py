@@ -205,6 +205,12 @@ class MMCompositeDesc(ctypes.Structure):
                 ("reserved", c_i), ("renders", c_p), ("backgrounds", c_p), ("params_host", c_p), ("params", c_p), ("out", c_p)]
 
 
+class MMPyramidDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("H", c_i), ("W", c_i), ("n_fg", c_i), ("n_bg", c_i), ("bg_C", c_i), ("fg_nhwc", c_i), ("k", c_i),
+                ("bg_pad", c_i * 4), ("rounding", c_i), ("as_float", c_i),
+                ("renders", c_p), ("backgrounds", c_p), ("params_host", c_p), ("params", c_p), ("out", c_p)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -228,7 +234,7 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
            "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward",
            "mm_render_indexed_query_workspace", "mm_render_indexed_forward", "mm_render_indexed_backward",
-           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_assemble_batch", "mm_composite_frames", "mm_struct_size",
+           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_assemble_batch", "mm_composite_frames", "mm_pyramid_frames", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -334,6 +340,7 @@ def lib():
     L.mm_export_grid.argtypes = [P(MMExportDesc), c_p]
     L.mm_assemble_batch.argtypes = [P(MMBatchDesc), c_p]
     L.mm_composite_frames.argtypes = [P(MMCompositeDesc), c_p]
+    L.mm_pyramid_frames.argtypes = [P(MMPyramidDesc), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -349,7 +356,7 @@ def lib():
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
                MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
                MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads, MMExportDesc, MMBatchDesc,
-               None, MMCompositeDesc, MMRenderIndexedDesc)        # (id 31 is unassigned)
+               None, MMCompositeDesc, MMRenderIndexedDesc, None, MMPyramidDesc)        # (ids 31 and 34 are unassigned)
     for i, cls in enumerate(mirrors):
         if cls is not None and L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

@@ -57,6 +57,9 @@ int launch_assemble_batch(const MMBatchDesc*, hipStream_t);
 struct CompArgs;
 long long composite_lds_bytes(const MMCompositeDesc*, CompArgs*);
 int launch_composite(const MMCompositeDesc*, hipStream_t);
+struct PyrArgs;
+long long pyramid_lds_bytes(const MMPyramidDesc*, PyrArgs*);
+int launch_pyramid(const MMPyramidDesc*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -790,6 +793,33 @@ int mm_composite_frames(const MMCompositeDesc* d, mm_stream_t stream) {
     return mm::launch_composite(d, (hipStream_t)stream);
 }
 
+int mm_pyramid_frames(const MMPyramidDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (!d->renders || !d->backgrounds || !d->params_host || !d->params || !d->out) return MM_ERR_NULL_POINTER;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->n_fg <= 0 || d->n_bg <= 0 || (d->bg_C != 3 && d->bg_C != 4)) return MM_ERR_BAD_SHAPE;
+    if (d->rounding != 0 && d->rounding != 1) return MM_ERR_BAD_SHAPE;
+    if (d->k < 1 || d->k > MM_PYRAMID_MAX_KERNEL || !(d->k & 1)) return MM_ERR_BAD_SHAPE;
+    const int32_t lim = 1 << 24;                                  // sums of sizes and pads stay far inside an int32
+    if (d->H > lim || d->W > lim || d->B > lim) return MM_ERR_BAD_SHAPE;
+    // a reflection reflects once: the pad is narrower than the image, and so is the blur radius, at every level
+    const int32_t* bp = d->bg_pad;
+    if (bp[0] < 0 || bp[1] < 0 || bp[2] < 0 || bp[3] < 0 || bp[0] >= d->W || bp[1] >= d->W || bp[2] >= d->H || bp[3] >= d->H) return MM_ERR_BAD_SHAPE;
+    if (d->k / 2 >= d->H || d->k / 2 >= d->W) return MM_ERR_BAD_SHAPE;
+    const int32_t* par = d->params_host;
+    for (int o = 0; o < d->B; ++o)
+        if (par[o] < 0 || par[o] >= d->n_fg || par[d->B + o] < 0 || par[d->B + o] >= d->n_bg) return MM_ERR_BAD_SHAPE;
+    const int32_t* row = par + 2 * (size_t)d->B + 9 * (size_t)d->B * d->k;
+    const int32_t n_out[2] = {d->H, d->W};
+    const int32_t n_in[2] = {d->H + bp[2] + bp[3], d->W + bp[0] + bp[1]};
+    for (int t = 0; t < 2; ++t)
+        for (int i = 0; i < n_out[t]; ++i, row += MM_PYRAMID_ROW_WORDS)
+            if (row[1] < 1 || row[1] > MM_PYRAMID_MAX_TAPS || row[0] < 0 || row[0] > n_in[t] - row[1]) return MM_ERR_BAD_SHAPE;
+    if (mm::pyramid_lds_bytes(d, nullptr) > 160 * 1024) return MM_ERR_UNSUPPORTED;
+    if ((long long)d->B * ((d->H + MM_PYRAMID_ROWS - 1) / MM_PYRAMID_ROWS) > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;
+    mm::clear_stale_error();
+    return mm::launch_pyramid(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -862,7 +892,7 @@ size_t mm_struct_size(int which) {
         case 24: return sizeof(MMInterpDesc);   case 25: return sizeof(MMInterpGrads);  case 26: return sizeof(MMRenderViewsDesc);
         case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);  case 29: return sizeof(MMExportDesc);
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
-        case 33: return sizeof(MMRenderIndexedDesc);
+        case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
         default: return 0;
     }
 }

@@ -889,6 +889,56 @@ typedef struct MMCompositeDesc {
 int mm_composite_frames(const MMCompositeDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Pyramid: renders blended into backgrounds through a three-level Laplacian pyramid as 8-bit frames, what the reference's
+ * tool/generate_market_test.py:326-369 does on the host per image after every render, in one launch: B frames (B,H,W,3) bytes -- or,
+ * with as_float, (B,3,H,W) fp32 planes fl(float(q) / 255) -- from `renders` and `backgrounds` as MMCompositeDesc takes them.  Per frame
+ * o there are three plane KINDS, 0 the mask, 1 the background, 2 the render, and every plane is blurred MM_PYRAMID_LEVELS = 3 times in a
+ * cascade, level l with the frame's own taps[o][kind][l - 1].  All in fp32, every operation rounded as written, every sum taken in
+ * ascending tap index starting from 0, no contraction:
+ *   level 0   m0 = channel 3 of render fg_index[o]; obj0_c = its channel c, untouched; bg0_c = plane c of background bg_index[o] behind
+ *             the reflection pad bg_pad = (left, right, top, bottom) -- a virtual image (H + top + bottom, W + left + right) that is index
+ *             arithmetic only -- resized to (H,W): sum_t fl(w[x][t] * v[C(start[x] + t)]) along x, then the same along y, C clamping to
+ *             the virtual image.  There is NO blur before the resize (the reference's order at this call site).
+ *   level l   v_l = vblur(hblur(v_{l-1})): sum_j fl(k[j] * v[R(x + j - r)]) along x, then the same along y, r = (k - 1) / 2, R reflecting
+ *             at the (H,W) image's own edge, at every level.
+ *   blend     t = fl(bg3 * fl(1 - m3)); t = fl(t + fl(obj3 * m3)); t = fl(t + fl(fl(bg1 - bg2) * fl(1 - m2)));
+ *             t = fl(t + fl(fl(obj1 - obj2) * m2)); t = fl(t + fl(fl(bg0 - bg1) * fl(1 - m1))); t = fl(t + fl(fl(obj0 - obj1) * m1)),
+ *             then the Export quantiser above, unchanged: rounding 0 trunc / 1 nearest, NaN -> 0, saturating (the sums leave [0, 1]).
+ * A one-tap kernel {1.0} makes a level the identity; resize rows {start i, 1 tap, 1.0} make level 0 of the background the image itself.
+ * params is ONE table of 32-bit words (floats by their bits) that the caller uploads; params_host is the host's copy of it, which is
+ * validated and sizes the kernel's LDS before anything is launched:
+ *   fg_index (B) | bg_index (B) | taps (B,3,3,k): [frame][kind][level] | resize rows: bg y (H), bg x (W)
+ * a resize row being MM_PYRAMID_ROW_WORDS words {start, n, w[0..8)}: output index i reads inputs [start, start + n) of the padded axis.
+ * MM_ERR_BAD_SHAPE: B, H, W, n_fg, n_bg < 1; bg_C not 3 or 4; k even, < 1 or > MM_PYRAMID_MAX_KERNEL; a pad that is negative or >= the
+ * dimension it reflects in; a radius >= min(H, W); an index outside [0, n_fg) / [0, n_bg); a resize row with n outside
+ * [1, MM_PYRAMID_MAX_TAPS] or taps outside the padded axis; rounding not 0 / 1.
+ * MM_ERR_UNSUPPORTED: more than the 160 KiB of LDS -- 8 * rows * W (rows: the most any band of MM_PYRAMID_ROWS stages, 8 + 3 (k - 1) of
+ * level 0 or the padded rows their vertical taps read) + 320 * W + 24 * W + 32 bytes, rounded up; kernel 7 behind a pad of 16 takes 39 KiB
+ * at 128 x 64, 77 KiB at 128 x 128 and 148 KiB at 256 x 256 --, or more than 2^31 - 1 workgroups.
+ * No workspace, no atomics, no host synchronisation; bitwise reproducible.  Not differentiable.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_PYRAMID_ROWS 8           /* output rows per workgroup */
+#define MM_PYRAMID_LEVELS 3
+#define MM_PYRAMID_MAX_KERNEL 15    /* LDS does not force less: kernel 15 at 128 x 128 behind a pad of 16 takes 107 KiB */
+#define MM_PYRAMID_MAX_TAPS 8       /* resize taps per output index */
+#define MM_PYRAMID_ROW_WORDS 10
+typedef struct MMPyramidDesc {
+    int32_t B, H, W;                /* the frames */
+    int32_t n_fg, n_bg, bg_C;       /* images in renders / backgrounds; channels of a background */
+    int32_t fg_nhwc;                /* layout flag of renders */
+    int32_t k;                      /* blur taps per frame, kind and level: odd, 1 = none (the tap is 1.0) */
+    int32_t bg_pad[4];              /* reflection pad of the background: left, right, top, bottom */
+    int32_t rounding;               /* 0 trunc, 1 nearest */
+    int32_t as_float;               /* fp32 planes (B,3,H,W) instead of bytes (B,H,W,3) */
+    const float* renders;
+    const float* backgrounds;
+    const int32_t* params_host;     /* host memory */
+    const int32_t* params;          /* device memory, the same words */
+    void* out;
+} MMPyramidDesc;
+int mm_pyramid_frames(const MMPyramidDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -912,7 +962,7 @@ const char* mm_last_error_detail(void);
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
- * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc (31 is unassigned). */
+ * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc (31 and 34 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -929,7 +979,8 @@ size_t mm_struct_size(int which);
  * shorter struct finds out from mm_struct_size(0), as every binding must check; still 9: MMBatchDesc and mm_assemble_batch, struct id 30, an
  * addition, detected by mm_struct_size(30) != 0; still 9: MMCompositeDesc and mm_composite_frames, struct id 32 -- id 31 stays unassigned and
  * returns 0 --, an addition, detected by mm_struct_size(32) != 0; still 9: MMRenderIndexedDesc and mm_render_indexed_*, struct id 33, an
- * addition, detected by mm_struct_size(33) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * addition, detected by mm_struct_size(33) != 0; still 9: MMPyramidDesc and mm_pyramid_frames, struct id 35 -- id 34 stays unassigned and
+ * returns 0 --, an addition, detected by mm_struct_size(35) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
