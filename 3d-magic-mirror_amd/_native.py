@@ -211,6 +211,11 @@ class MMPyramidDesc(ctypes.Structure):
                 ("renders", c_p), ("backgrounds", c_p), ("params_host", c_p), ("params", c_p), ("out", c_p)]
 
 
+class MMJpegDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("header_bytes", c_i), ("frames", c_p), ("params_host", c_p), ("params", c_p),
+                ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -234,7 +239,7 @@ EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_
            "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
            "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward",
            "mm_render_indexed_query_workspace", "mm_render_indexed_forward", "mm_render_indexed_backward",
-           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_assemble_batch", "mm_composite_frames", "mm_pyramid_frames", "mm_struct_size",
+           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_assemble_batch", "mm_composite_frames", "mm_pyramid_frames", "mm_jpeg_query_workspace", "mm_jpeg_files_offset", "mm_jpeg_encode", "mm_struct_size",
            "mm_abi_version")
 
 
@@ -341,6 +346,11 @@ def lib():
     L.mm_assemble_batch.argtypes = [P(MMBatchDesc), c_p]
     L.mm_composite_frames.argtypes = [P(MMCompositeDesc), c_p]
     L.mm_pyramid_frames.argtypes = [P(MMPyramidDesc), c_p]
+    L.mm_jpeg_query_workspace.restype = ctypes.c_size_t
+    L.mm_jpeg_query_workspace.argtypes = [P(MMJpegDesc)]
+    L.mm_jpeg_files_offset.restype = ctypes.c_size_t
+    L.mm_jpeg_files_offset.argtypes = [P(MMJpegDesc)]
+    L.mm_jpeg_encode.argtypes = [P(MMJpegDesc), c_p]
     L.mm_struct_size.restype = ctypes.c_size_t
     L.mm_struct_size.argtypes = [ctypes.c_int]
     L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
@@ -356,7 +366,7 @@ def lib():
                MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
                MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
                MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads, MMExportDesc, MMBatchDesc,
-               None, MMCompositeDesc, MMRenderIndexedDesc, None, MMPyramidDesc)        # (ids 31 and 34 are unassigned)
+               None, MMCompositeDesc, MMRenderIndexedDesc, None, MMPyramidDesc, None, MMJpegDesc)        # (ids 31, 34 and 36 are unassigned)
     for i, cls in enumerate(mirrors):
         if cls is not None and L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))

@@ -19,7 +19,7 @@ DESIGN.md has the order in full.  The blur is separable where torchvision convol
 separable where torch's two-tap bilinear is one 2x2 expression: the results differ from the functional composition by rounding only
 (within 1e-5; bytes differ by one only where ``x * 255`` lies within 2e-3 of an integer).
 
-Out of scope: reproducing the reference's random streams (the caller draws ``bg_index`` and the sigmas: ``draw_sigmas``); JPEG encoding; gradients.
+Out of scope: reproducing the reference's random streams (the caller draws ``bg_index`` and the sigmas: ``draw_sigmas``); gradients.  JPEG encoding: ``encode_jpeg`` (jpeg.py).
 tool/generate_market_test.py's three-level pyramid blend and its resize-before-blur order: ``pyramid_frames`` (pyramid.py).  Device tensors only."""
 import ctypes
 import functools

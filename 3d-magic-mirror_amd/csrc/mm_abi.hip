@@ -60,6 +60,9 @@ int launch_composite(const MMCompositeDesc*, hipStream_t);
 struct PyrArgs;
 long long pyramid_lds_bytes(const MMPyramidDesc*, PyrArgs*);
 int launch_pyramid(const MMPyramidDesc*, hipStream_t);
+size_t jpeg_workspace_bytes(const MMJpegDesc*);
+size_t jpeg_files_at(const MMJpegDesc*);
+int launch_jpeg(const MMJpegDesc*, hipStream_t);
 }  // namespace mm
 
 static int check_render(const MMRenderDesc* d, bool backward) {
@@ -820,6 +823,40 @@ int mm_pyramid_frames(const MMPyramidDesc* d, mm_stream_t stream) {
     return mm::launch_pyramid(d, (hipStream_t)stream);
 }
 
+// the sizes a JPEG call may have: MM_OK, or why not
+static int check_jpeg_shape(const MMJpegDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->n <= 0 || d->H <= 0 || d->W <= 0 || d->header_bytes < 2 || d->header_bytes > MM_JPEG_MAX_HEADER) return MM_ERR_BAD_SHAPE;
+    if (d->H > 65535 || d->W > 65535 || d->n > 65535) return MM_ERR_UNSUPPORTED;
+    const long long blocks = 6LL * ((d->H + 15) / 16) * ((d->W + 15) / 16);
+    if (blocks > MM_JPEG_MAX_BLOCKS || blocks * d->n > (1LL << 30)) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+size_t mm_jpeg_query_workspace(const MMJpegDesc* d) {
+    return check_jpeg_shape(d) == MM_OK ? mm::jpeg_workspace_bytes(d) : 0;
+}
+
+size_t mm_jpeg_files_offset(const MMJpegDesc* d) {
+    return check_jpeg_shape(d) == MM_OK ? mm::jpeg_files_at(d) : 0;
+}
+
+int mm_jpeg_encode(const MMJpegDesc* d, mm_stream_t stream) {
+    const int shape = check_jpeg_shape(d);
+    if (shape != MM_OK) return shape;
+    if (!d->frames || !d->params_host || !d->params || !d->workspace) return MM_ERR_NULL_POINTER;
+    if (d->workspace_bytes < mm::jpeg_workspace_bytes(d) || ((uintptr_t)d->workspace & 15)) return MM_ERR_WORKSPACE;
+    const int32_t* par = d->params_host;
+    for (int i = 0; i < 128; ++i)                                 // the divisors: 8 * q, q in 1..255 (baseline)
+        if (par[i] < 8 || par[i] > 8 * 255 || (par[i] & 7)) return MM_ERR_BAD_SHAPE;
+    for (int i = 0; i < 1024; ++i) {                              // the codes: at most 16 bits, no wider than their size, and with the symbol's
+        const uint32_t size = (uint32_t)par[128 + i] >> 16, code = (uint32_t)par[128 + i] & 0xFFFFu;      // category bits at most 26: a block's room
+        if (size > 16 || (code >> size) != 0 || (size != 0 && size + (i & 15) > 26)) return MM_ERR_BAD_SHAPE;
+    }
+    mm::clear_stale_error();
+    return mm::launch_jpeg(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -893,6 +930,7 @@ size_t mm_struct_size(int which) {
         case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);  case 29: return sizeof(MMExportDesc);
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
+        case 37: return sizeof(MMJpegDesc);                                                     // (36: unassigned)
         default: return 0;
     }
 }

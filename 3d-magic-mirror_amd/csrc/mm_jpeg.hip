@@ -1,0 +1,438 @@
+// mm_jpeg.hip -- 8-bit device frames (n,H,W,3) as baseline JPEG files, for gfx950: what the reference's scripts do on the host per image with
+// to_pil_image(X[i, :3].cpu()).save(name, 'JPEG', quality=100) (trainer.py:51, test.py:53, generate_market++.py:55,
+// tool/generate_market_test.py:57, ...).  Every file equals Pillow's (libjpeg-turbo's) byte for byte: baseline, 4:2:0, the standard
+// Huffman tables.  The host makes the tables and the header; everything after SOS is made here.  Integer arithmetic only (>> is
+// arithmetic), in libjpeg's order:
+//   colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+//             Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+//             Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+//   edges     an MCU is 16 x 16 pixels: four luma blocks Y00 Y01 Y10 Y11 and one block each of Cb and Cr.  Columns beyond W replicate the
+//             INPUT's last column; rows beyond H replicate the input's last row up to an even height; the chroma rows beyond ceil(H / 2)
+//             replicate the DOWNSAMPLED last row (this differs from replicating input rows when H is even and H mod 16 is in 1..8).
+//             A luma block wholly beyond ceil(W / 8) or ceil(H / 8) is a DUMMY: no AC, and the DC of the block before it in MCU order.
+//   chroma    c[y][x] = (C[2y][2x] + C[2y][2x+1] + C[2y+1][2x] + C[2y+1][2x+1] + bias) >> 2, bias 1 on even x and 2 on odd x
+//   DCT       jfdctint's islow transform of the samples minus 128: CONST_BITS 13, PASS1_BITS 2, rows first, then columns; scaled by 8
+//   quantise  q = sign(v) * ((|v| + (d >> 1)) / d), d = 8 * table[k]: half away from zero
+//   entropy   MCUs in raster order, blocks Y00 Y01 Y10 Y11 Cb Cr, one DC predictor per component; the DC difference and every non-zero AC
+//             as (code of run << 4 | category, then category bits of v, or of v - 1 below zero); sixteen zeros as ZRL (0xF0); EOB unless the
+//             last coefficient is non-zero; the last byte padded with 1-bits; a 0x00 after every 0xFF; EOI.
+//
+// Eight launches and one memset, all on the caller's stream, nothing synchronises:
+//   transform eight lanes per block.  Lane r loads row r of its block (luma: 8 pixels; chroma: 16 x 2 pixels, converted and downsampled),
+//             runs the row pass, the block is transposed through LDS, lane c runs the column pass and quantises, and the block leaves as
+//             int16 in zigzag order, 16 bytes per lane.  The edges are clamped indices: nothing is padded in memory.
+//   count     one lane per block walks its 64 coefficients and writes the block's exact bit count.  The DC difference needs the previous
+//             block of the same component only, which is in memory already: no lane waits for another.
+//   offsets   one workgroup per frame scans the counts in MCU order: every block's bit offset, the frame's bits.
+//   pack      one lane per block walks again and ORs its codes into the frame's zeroed stream, big-endian 32-bit words.  Only a block's
+//             first and last word are shared with its neighbours (atomic OR, integer: the result is the same in any order), the words
+//             between them are stored plainly.
+//   count FF  a workgroup per 1024-byte chunk of a stream counts its 0xFF bytes; the lane that holds the last byte pads it with 1-bits.
+//   place     one workgroup per frame scans its chunks' counts; the frame's length is header + bytes + stuffed + 2.
+//   files     one workgroup scans the lengths: offsets[0..n], the files lie back to back.
+//   write     a workgroup per chunk scans its lanes' counts and writes the stuffed bytes where they go; chunk 0 also writes the
+//             header, the lane with the last byte also EOI.
+// A stream is never assumed to fit LDS (256 x 256 noise at quality 100 is 130 KB): it lives in the workspace, MM_JPEG_BLOCK_BYTES = 208 per
+// block (a block codes to 20 + 63 * 26 bits at most), and a file's room is header + twice that + 2.  No floating point, no scratch; every
+// byte is a pure function of the frame (bitwise reproducible).
+#include <hip/hip_runtime.h>
+
+#include "mm_device.h"
+
+#define MM_JPG_BLOCK 256
+#define MM_JPG_BLOCK_WORDS (MM_JPEG_BLOCK_BYTES / 4)
+#define MM_JPG_CHUNK_WORDS (MM_JPEG_CHUNK_BYTES / 4)
+static_assert(MM_JPG_CHUNK_WORDS == MM_JPG_BLOCK, "a lane per word of a chunk");
+
+namespace mm {
+
+// where the tables lie in MMJpegDesc.params (32-bit words)
+enum { MM_JPG_DIV = 0, MM_JPG_HUFF = 128, MM_JPG_HEADER = 128 + 1024 };
+
+struct JpegLayout {
+    int my, mx, blocks, chunks;                               // MCU rows and columns, blocks and 1024-byte chunks of one frame
+    size_t file_cap;                                          // bytes kept for one file
+    size_t offsets, files, coef, bits, frame_bits, raw, chunk_ff, bytes;      // byte offsets into the workspace
+};
+__host__ inline size_t jpeg_up(size_t x) { return (x + 255) & ~(size_t)255; }
+__host__ JpegLayout jpeg_layout(const MMJpegDesc* d) {
+    JpegLayout l;
+    l.my = (d->H + 15) / 16; l.mx = (d->W + 15) / 16;
+    l.blocks = l.my * l.mx * 6;
+    l.chunks = (int)(((size_t)l.blocks * MM_JPEG_BLOCK_BYTES + MM_JPEG_CHUNK_BYTES - 1) / MM_JPEG_CHUNK_BYTES);
+    l.file_cap = (size_t)d->header_bytes + 2 * (size_t)l.chunks * MM_JPEG_CHUNK_BYTES + 2;
+    const size_t n = (size_t)d->n;
+    l.offsets = 0;
+    l.files = jpeg_up((n + 1) * 8);
+    l.coef = l.files + jpeg_up(n * l.file_cap);
+    l.bits = l.coef + jpeg_up(n * l.blocks * 128);
+    l.frame_bits = l.bits + jpeg_up(n * l.blocks * 4);
+    l.raw = l.frame_bits + jpeg_up(n * 4);
+    l.chunk_ff = l.raw + jpeg_up(n * l.chunks * MM_JPEG_CHUNK_BYTES);
+    l.bytes = l.chunk_ff + jpeg_up(n * l.chunks * 4);
+    return l;
+}
+size_t jpeg_workspace_bytes(const MMJpegDesc* d) { return jpeg_layout(d).bytes; }
+size_t jpeg_files_at(const MMJpegDesc* d) { return jpeg_layout(d).files; }
+
+struct JpegArgs {
+    const unsigned char* frames; const int* par;
+    long long* offsets; unsigned char* files; short* coef; unsigned* bits; unsigned* frame_bits; unsigned* raw; unsigned* chunk_ff;
+    int n, H, W, header_bytes;
+    int my, mx, blocks, chunks;
+    int bh, bw, ch;                                           // luma blocks down and across that hold pixels; chroma rows that do
+    long long total_blocks;
+};
+
+// ---- small pieces ------------------------------------------------------------------------------------------------------------------
+// exclusive prefix sum over the workgroup of 256 (total in every lane); every lane of the workgroup calls it.  sh: 4 ints.
+__device__ inline int block_prefix_excl(int v, int tid, int* sh, int& total) {
+    int wave_total;
+    const int e = wave_prefix_excl(v, tid & 63, wave_total);
+    __syncthreads();                                          // (sh may still be read from the call before)
+    if ((tid & 63) == 0) sh[tid >> 6] = wave_total;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < MM_JPG_BLOCK / 64; ++w) {
+        const int x = sh[w];
+        base += w < (tid >> 6) ? x : 0;
+        total += x;
+    }
+    return e + base;
+}
+
+// natural index -> position in zigzag order
+__device__ const unsigned char jpeg_zigzag_pos[64] = {
+    0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+    10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+// one pass of jfdctint over eight values; FIRST: the row pass (output scaled up by PASS1_BITS), else the column pass
+template <bool FIRST>
+__device__ inline void jpeg_fdct8(const int (&d)[8], int (&o)[8]) {
+    constexpr int CB = 13, PB = 2;
+    constexpr int N = FIRST ? CB - PB : CB + PB, R = 1 << (N - 1);
+    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    if (FIRST) { o[0] = (t10 + t11) * (1 << PB); o[4] = (t10 - t11) * (1 << PB); }
+    else       { o[0] = (t10 + t11 + (1 << (PB - 1))) >> PB; o[4] = (t10 - t11 + (1 << (PB - 1))) >> PB; }
+    int z1 = (t12 + t13) * 4433;
+    o[2] = (z1 + t13 * 6270 + R) >> N;
+    o[6] = (z1 + t12 * -15137 + R) >> N;
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+    z1 *= -7373; z2 *= -20995;
+    z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    o[7] = (a4 + z1 + z3 + R) >> N;
+    o[5] = (a5 + z2 + z4 + R) >> N;
+    o[3] = (a6 + z2 + z3 + R) >> N;
+    o[1] = (a7 + z1 + z4 + R) >> N;
+}
+
+// ---- transform: frames -> quantised coefficients, zigzag order, MCU order ---------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_transform_kernel(JpegArgs a) {
+    __shared__ int tile[MM_JPG_BLOCK / 8][65];                // a block's 64 values after the row pass (65: the blocks' rows on different banks)
+    __shared__ __attribute__((aligned(16))) short zz[MM_JPG_BLOCK / 8][64];
+    const int tid = threadIdx.x, lb = tid >> 3, r = tid & 7;
+    const long long g = (long long)blockIdx.x * (MM_JPG_BLOCK / 8) + lb;      // the block, over all frames
+    const bool live = g < a.total_blocks;
+    const long long gc = live ? g : 0;
+    const int img = (int)(gc / a.blocks), rem = (int)(gc % a.blocks);
+    const int mcu = rem / 6, j = rem % 6, my = mcu / a.mx, mx = mcu % a.mx;
+    const unsigned char* f = a.frames + (size_t)img * a.H * a.W * 3;
+    bool dummy = false;
+    int d[8], o[8];
+    if (j < 4) {
+        const int by = 2 * my + (j >> 1), bx = 2 * mx + (j & 1);
+        dummy = by >= a.bh || bx >= a.bw;
+        const int y = min(by * 8 + r, a.H - 1);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const unsigned char* p = f + ((size_t)y * a.W + min(bx * 8 + c, a.W - 1)) * 3;
+            d[c] = ((19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16) - 128;
+        }
+    } else {
+        const int cy = min(my * 8 + r, a.ch - 1);             // beyond the chroma rows: the downsampled last row
+        const size_t y0 = (size_t)min(2 * cy, a.H - 1) * a.W, y1 = (size_t)min(2 * cy + 1, a.H - 1) * a.W;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int x0 = min(2 * (mx * 8 + c), a.W - 1), x1 = min(2 * (mx * 8 + c) + 1, a.W - 1);
+            const unsigned char* q[4] = {f + (y0 + x0) * 3, f + (y0 + x1) * 3, f + (y1 + x0) * 3, f + (y1 + x1) * 3};
+            int sum = (c & 1) + 1;                            // the bias: 1 on even output columns, 2 on odd ones
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int R = q[i][0], G = q[i][1], B = q[i][2];
+                sum += j == 4 ? (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+                              : (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+            }
+            d[c] = (sum >> 2) - 128;
+        }
+    }
+    jpeg_fdct8<true>(d, o);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) tile[lb][r * 8 + c] = o[c];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = tile[lb][k * 8 + r];   // lane r now has column r
+    jpeg_fdct8<false>(d, o);
+    const int* div = a.par + MM_JPG_DIV + (j < 4 ? 0 : 64);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int nat = k * 8 + r;
+        const unsigned dv = (unsigned)div[nat];
+        const int v = o[k];
+        const unsigned m = ((unsigned)abs(v) + (dv >> 1)) / dv;
+        zz[lb][jpeg_zigzag_pos[nat]] = dummy ? (short)0 : (short)(v < 0 ? -(int)m : (int)m);
+    }
+    __syncthreads();
+    if (live) *(uint4*)(a.coef + (size_t)g * 64 + r * 8) = *(const uint4*)&zz[lb][r * 8];
+}
+
+// ---- the walk over a block, shared by the count and the pack ----------------------------------------------------------------------
+__device__ inline bool jpeg_is_dummy(const JpegArgs& a, int mcu, int j) {
+    return j < 4 && (2 * (mcu / a.mx) + (j >> 1) >= a.bh || 2 * (mcu % a.mx) + (j & 1) >= a.bw);
+}
+// the DC a block codes: its own, or for a dummy that of the block before it in MCU order (Y00 is never a dummy)
+__device__ inline int jpeg_dc(const JpegArgs& a, const short* frame_coef, int mcu, int j) {
+    while (jpeg_is_dummy(a, mcu, j)) --j;
+    return frame_coef[((size_t)mcu * 6 + j) * 64];
+}
+// the predictor: the DC coded by the previous block of the same component
+__device__ inline int jpeg_dc_pred(const JpegArgs& a, const short* frame_coef, int mcu, int j) {
+    if (j >= 1 && j < 4) return jpeg_dc(a, frame_coef, mcu, j - 1);
+    if (mcu == 0) return 0;
+    return jpeg_dc(a, frame_coef, mcu - 1, j == 0 ? 3 : j);
+}
+
+struct JpegCounter {
+    unsigned nbits = 0;
+    __device__ inline void put(unsigned, int len) { nbits += len; }
+    __device__ inline void finish() {}
+};
+// bits go out most significant first, into big-endian 32-bit words that were zeroed
+struct JpegWriter {
+    unsigned* word; unsigned* end;
+    unsigned long long acc = 0;
+    int nacc;                                                 // bits in acc, the first word's earlier bits (other blocks') as zeros
+    bool first = true;
+    __device__ inline JpegWriter(unsigned* w, unsigned* e, int used) : word(w), end(e), nacc(used) {}
+    __device__ inline void put(unsigned v, int len) {         // len <= 27
+        acc = (acc << len) | v;
+        nacc += len;
+        if (nacc >= 32) {
+            nacc -= 32;
+            const unsigned out = (unsigned)(acc >> nacc);
+            if (word < end) { if (first) atomicOr(word, out); else *word = out; }
+            first = false;
+            ++word;
+            acc &= (1ull << nacc) - 1;
+        }
+    }
+    __device__ inline void finish() { if (nacc > 0 && word < end) atomicOr(word, (unsigned)(acc << (32 - nacc))); }
+};
+
+__device__ inline void jpeg_symbol(unsigned entry, int v, int cat, unsigned& bits, int& len) {
+    const unsigned extra = (unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1);
+    bits = ((entry & 0xFFFFu) << cat) | extra;
+    len = (int)(entry >> 16) + cat;
+}
+
+// huff: the four tables in LDS (DC luma, AC luma, DC chroma, AC chroma), size << 16 | code per symbol
+template <class Sink>
+__device__ inline void jpeg_walk(const uint4* coef, int dc, int pred, const unsigned* dc_tab, const unsigned* ac_tab, Sink& sink) {
+    unsigned bits; int len;
+    {
+        const int diff = dc - pred, cat = 32 - __clz(abs(diff));
+        jpeg_symbol(dc_tab[cat], diff, cat, bits, len);
+        sink.put(bits, len);
+    }
+    int run = 0;
+    for (int g8 = 0; g8 < 8; ++g8) {
+        const uint4 q = coef[g8];
+        const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (g8 == 0 && i == 0) continue;                  // the DC
+            const int v = (int)(short)(w[i >> 1] >> (16 * (i & 1)));
+            if (v == 0) { ++run; continue; }
+            while (run > 15) { const unsigned z = ac_tab[0xF0]; sink.put(z & 0xFFFFu, (int)(z >> 16)); run -= 16; }
+            // |v| < 1024 for 8-bit samples (libjpeg refuses more), so cat <= 10.  A category 11 would read a table entry of size 0 and make a
+            // malformed stream, never an access outside the tables or the block's room (11 bits < 26).
+            const int cat = 32 - __clz(abs(v));
+            jpeg_symbol(ac_tab[((run << 4) | cat) & 0xFF], v, cat, bits, len);
+            sink.put(bits, len);
+            run = 0;
+        }
+    }
+    if (run > 0) { const unsigned z = ac_tab[0]; sink.put(z & 0xFFFFu, (int)(z >> 16)); }
+    sink.finish();
+}
+
+template <bool PACK>
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_code_kernel(JpegArgs a) {
+    __shared__ unsigned huff[1024];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 1024; i += MM_JPG_BLOCK) huff[i] = (unsigned)a.par[MM_JPG_HUFF + i];
+    __syncthreads();
+    const long long g = (long long)blockIdx.x * MM_JPG_BLOCK + tid;
+    if (g >= a.total_blocks) return;
+    const int img = (int)(g / a.blocks), rem = (int)(g % a.blocks), mcu = rem / 6, j = rem % 6;
+    const short* fc = a.coef + (size_t)img * a.blocks * 64;
+    const int dc = jpeg_dc(a, fc, mcu, j), pred = jpeg_dc_pred(a, fc, mcu, j);
+    const unsigned* dc_tab = huff + (j < 4 ? 0 : 512);
+    const uint4* coef = (const uint4*)(a.coef + (size_t)g * 64);
+    if (PACK) {
+        const unsigned at = a.bits[g];                        // the block's bit offset in its frame's stream
+        unsigned* raw = a.raw + (size_t)img * a.chunks * MM_JPG_CHUNK_WORDS;
+        JpegWriter w(raw + (at >> 5), raw + (size_t)a.chunks * MM_JPG_CHUNK_WORDS, (int)(at & 31));
+        jpeg_walk(coef, dc, pred, dc_tab, dc_tab + 256, w);
+    } else {
+        JpegCounter c;
+        jpeg_walk(coef, dc, pred, dc_tab, dc_tab + 256, c);
+        a.bits[g] = c.nbits;
+    }
+}
+
+// ---- offsets: per frame, the blocks' bit counts -> bit offsets, in place ------------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_bit_offsets_kernel(JpegArgs a) {
+    __shared__ int sh[4];
+    const int tid = threadIdx.x, img = blockIdx.x;
+    unsigned* bits = a.bits + (size_t)img * a.blocks;
+    unsigned carry = 0;
+    for (int base = 0; base < a.blocks; base += MM_JPG_BLOCK) {
+        const int i = base + tid;
+        int total;
+        const int e = block_prefix_excl(i < a.blocks ? (int)bits[i] : 0, tid, sh, total);
+        if (i < a.blocks) bits[i] = carry + (unsigned)e;
+        carry += (unsigned)total;
+    }
+    // (a block of valid tables codes to 64 * 26 bits at most, so the sum fits; the clamp keeps every later index inside the frame's room whatever the tables)
+    if (tid == 0) a.frame_bits[img] = min(carry, (unsigned)a.chunks * (MM_JPEG_CHUNK_BYTES * 8u));
+}
+
+// byte k of a stream lies in word k / 4 at shift 24 - 8 * (k % 4)
+__device__ inline int jpeg_count_ff(unsigned w, int nbytes) {  // among the first nbytes (0..4) bytes of the word
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c += (i < nbytes && ((w >> (24 - 8 * i)) & 0xFFu) == 0xFFu) ? 1 : 0;
+    return c;
+}
+
+// ---- count FF: per chunk of a stream; pads the last byte --------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_count_ff_kernel(JpegArgs a) {
+    __shared__ int sh[4];
+    const int tid = threadIdx.x, chunk = blockIdx.x, img = blockIdx.y;
+    const unsigned nbits = a.frame_bits[img];
+    const long long len = ((long long)nbits + 7) >> 3;        // the stream's bytes
+    const long long byte0 = (long long)chunk * MM_JPEG_CHUNK_BYTES + tid * 4;
+    int c = 0;
+    if (byte0 < len) {
+        unsigned* p = a.raw + ((size_t)img * a.chunks + chunk) * MM_JPG_CHUNK_WORDS + tid;
+        unsigned w = *p;
+        const int nb = (int)min(len - byte0, 4LL);
+        if (byte0 + nb == len && (nbits & 7)) {               // the last byte: its unused low bits become 1
+            w |= (0xFFu >> (nbits & 7)) << (24 - 8 * (nb - 1));
+            *p = w;
+        }
+        c = jpeg_count_ff(w, nb);
+    }
+    int total;
+    (void)block_prefix_excl(c, tid, sh, total);
+    if (tid == 0) a.chunk_ff[(size_t)img * a.chunks + chunk] = (unsigned)total;
+}
+
+// ---- place: per frame, the chunks' counts -> the stuffed bytes before each chunk, in place; the file's length -----------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_place_kernel(JpegArgs a) {
+    __shared__ int sh[4];
+    const int tid = threadIdx.x, img = blockIdx.x;
+    unsigned* ff = a.chunk_ff + (size_t)img * a.chunks;
+    unsigned carry = 0;
+    for (int base = 0; base < a.chunks; base += MM_JPG_BLOCK) {
+        const int i = base + tid;
+        int total;
+        const int e = block_prefix_excl(i < a.chunks ? (int)ff[i] : 0, tid, sh, total);
+        if (i < a.chunks) ff[i] = carry + (unsigned)e;
+        carry += (unsigned)total;
+    }
+    if (tid == 0) a.offsets[img + 1] = (long long)a.header_bytes + (((long long)a.frame_bits[img] + 7) >> 3) + carry + 2;
+}
+
+// ---- files: the lengths in offsets[1..n] -> offsets[0..n] -------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_file_offsets_kernel(JpegArgs a) {
+    __shared__ long long sh[MM_JPG_BLOCK];
+    const int tid = threadIdx.x;
+    long long carry = 0;
+    if (tid == 0) a.offsets[0] = 0;
+    for (int base = 0; base < a.n; base += MM_JPG_BLOCK) {
+        const int i = base + tid;
+        sh[tid] = i < a.n ? a.offsets[i + 1] : 0;
+        __syncthreads();
+        for (int o = 1; o < MM_JPG_BLOCK; o <<= 1) {
+            const long long t = tid >= o ? sh[tid - o] : 0;
+            __syncthreads();
+            sh[tid] += t;
+            __syncthreads();
+        }
+        if (i < a.n) a.offsets[i + 1] = carry + sh[tid];
+        carry += sh[MM_JPG_BLOCK - 1];
+        __syncthreads();
+    }
+}
+
+// ---- write: header, stuffed bytes, EOI ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_write_kernel(JpegArgs a) {
+    __shared__ int sh[4];
+    const int tid = threadIdx.x, chunk = blockIdx.x, img = blockIdx.y;
+    const unsigned nbits = a.frame_bits[img];
+    const long long len = ((long long)nbits + 7) >> 3;
+    if ((long long)chunk * MM_JPEG_CHUNK_BYTES >= len) return;                 // (the whole workgroup; a stream has a byte at least: chunk 0 stays)
+    unsigned char* dst = a.files + a.offsets[img];
+    if (chunk == 0) {
+        const unsigned char* h = (const unsigned char*)(a.par + MM_JPG_HEADER);
+        for (int i = tid; i < a.header_bytes; i += MM_JPG_BLOCK) dst[i] = h[i];
+    }
+    const long long byte0 = (long long)chunk * MM_JPEG_CHUNK_BYTES + tid * 4;
+    const int nb = byte0 < len ? (int)min(len - byte0, 4LL) : 0;
+    const unsigned w = nb ? a.raw[((size_t)img * a.chunks + chunk) * MM_JPG_CHUNK_WORDS + tid] : 0u;
+    int total;
+    const int before = block_prefix_excl(jpeg_count_ff(w, nb), tid, sh, total);
+    unsigned char* p = dst + a.header_bytes + byte0 + a.chunk_ff[(size_t)img * a.chunks + chunk] + before;
+    for (int i = 0; i < nb; ++i) {
+        const unsigned b = (w >> (24 - 8 * i)) & 0xFFu;
+        *p++ = (unsigned char)b;
+        if (b == 0xFFu) *p++ = 0;
+    }
+    if (nb && byte0 + nb == len) { p[0] = 0xFF; p[1] = 0xD9; }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+int launch_jpeg(const MMJpegDesc* d, hipStream_t s) {
+    const JpegLayout l = jpeg_layout(d);
+    unsigned char* ws = (unsigned char*)d->workspace;
+    JpegArgs a = {};
+    a.frames = d->frames; a.par = d->params;
+    a.offsets = (long long*)(ws + l.offsets); a.files = ws + l.files; a.coef = (short*)(ws + l.coef); a.bits = (unsigned*)(ws + l.bits);
+    a.frame_bits = (unsigned*)(ws + l.frame_bits); a.raw = (unsigned*)(ws + l.raw); a.chunk_ff = (unsigned*)(ws + l.chunk_ff);
+    a.n = d->n; a.H = d->H; a.W = d->W; a.header_bytes = d->header_bytes;
+    a.my = l.my; a.mx = l.mx; a.blocks = l.blocks; a.chunks = l.chunks;
+    a.bh = (d->H + 7) / 8; a.bw = (d->W + 7) / 8; a.ch = (d->H + 1) / 2;
+    a.total_blocks = (long long)d->n * l.blocks;
+    if (hipMemsetAsync(a.raw, 0, (size_t)d->n * l.chunks * MM_JPEG_CHUNK_BYTES, s) != hipSuccess) return launch_ok("jpeg_zero");
+    const dim3 wg(MM_JPG_BLOCK), per_frame((unsigned)d->n), per_chunk((unsigned)l.chunks, (unsigned)d->n);
+    const unsigned per_block = (unsigned)((a.total_blocks + MM_JPG_BLOCK - 1) / MM_JPG_BLOCK);
+    hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((a.total_blocks + MM_JPG_BLOCK / 8 - 1) / (MM_JPG_BLOCK / 8))), wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_code_kernel<false>, dim3(per_block), wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_bit_offsets_kernel, per_frame, wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_code_kernel<true>, dim3(per_block), wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_count_ff_kernel, per_chunk, wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_place_kernel, per_frame, wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_file_offsets_kernel, dim3(1), wg, 0, s, a);
+    hipLaunchKernelGGL(jpeg_write_kernel, per_chunk, wg, 0, s, a);
+    return launch_ok("jpeg");
+}
+
+}  // namespace mm

@@ -1,0 +1,227 @@
+"""Device frames as baseline JPEG files, Pillow's bytes: host side of ``mm_jpeg_encode`` (csrc/mm_jpeg.hip).
+
+The reference's dataset-generation, evaluation and visualisation scripts all end on ``to_pil_image(X[i, :3].cpu())`` followed by
+``output.save(name, 'JPEG', quality=100)`` (trainer.py:51, test.py:53, generate_market++.py:55, tool/generate_market_test.py:57, ...), one
+image and one process at a time.  ``encode_jpeg`` takes the (...,H,W,3) uint8 frames that ``export_images``, ``composite_frames`` and
+``pyramid_frames`` leave on the device and returns the complete files, back to back in one host buffer, after two device-to-host copies:
+the offsets, then exactly the bytes used.
+
+Every file equals, byte for byte, what ``PIL.Image.fromarray(frame).save(f, 'JPEG', quality=q)`` writes (Pillow 12 over libjpeg-turbo):
+baseline, 4:2:0, the standard Huffman tables, libjpeg's quality scaling.  libjpeg's baseline path is all integer and so is this one; the
+order is in DESIGN.md and in the kernel's header.  The host makes the tables and the header (``lower_jpeg``); everything after SOS is
+made on the device.
+
+Out of scope: 4:4:4 and 4:2:2 subsampling, greyscale, ``optimize=True``, progressive, restart markers, EXIF / ICC, decoding, writing to
+disk beyond ``JpegBatch.write``.  Device tensors only."""
+import ctypes
+import functools
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+BLOCK_BYTES = 208       # MM_JPEG_BLOCK_BYTES: a block codes to at most 20 + 63 * 26 bits, kept as 52 words
+CHUNK_BYTES = 1024      # MM_JPEG_CHUNK_BYTES: the piece of a stream one workgroup stuffs
+MAX_BLOCKS = 1 << 20    # MM_JPEG_MAX_BLOCKS: blocks of one frame (its stream's bit offsets stay inside 31 bits)
+MAX_FRAMES = 65535      # frames in a call
+
+# ITU-T T.81 Annex K: the two base quantisation tables (natural order) and the four Huffman tables (codes per length 1..16, symbols)
+_Q_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+           18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_Q_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+_AC_LUMA = ("01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+            "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6"
+            "c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_AC_CHROMA = ("000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445464748"
+              "494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3"
+              "c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+# (class << 4 | id, bits, symbols) in the order the four DHT segments are written: DC 0, AC 0, DC 1, AC 1
+HUFFMAN = ((0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),
+           (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125), bytes.fromhex(_AC_LUMA)),
+           (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),
+           (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119), bytes.fromhex(_AC_CHROMA)))
+
+
+def _zigzag():
+    """ZIGZAG[k]: the natural (row-major) index of the k-th coefficient in zigzag order"""
+    order = sorted(range(64), key=lambda i: (i // 8 + i % 8, i // 8 if (i // 8 + i % 8) % 2 else i % 8))
+    return np.array(order, dtype=np.int32)
+
+
+ZIGZAG = _zigzag()
+
+
+def quant_tables(quality):
+    """(2,64) int32, natural order: the luma and chroma tables by libjpeg's ``jpeg_set_quality(quality, force_baseline=TRUE)``"""
+    quality = int(quality)
+    if quality < 1 or quality > 100:
+        raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    base = np.array([_Q_LUMA, _Q_CHROMA], dtype=np.int64)
+    return np.clip((base * scale + 50) // 100, 1, 255).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def huffman_codes():
+    """(4,256) int32, ``size << 16 | code`` per symbol (0 where the table has none), tables in ``HUFFMAN``'s order: T.81 Annex C"""
+    out = np.zeros((4, 256), dtype=np.int32)
+    for t, (_, bits, vals) in enumerate(HUFFMAN):
+        code, k = 0, 0
+        for length in range(1, 17):
+            for _ in range(bits[length - 1]):
+                out[t, vals[k]] = length << 16 | code
+                code, k = code + 1, k + 1
+            code <<= 1
+    out.setflags(write=False)
+    return out
+
+
+def _segment(marker, body):
+    return bytes((0xFF, marker)) + (len(body) + 2).to_bytes(2, "big") + body
+
+
+def header_bytes(H, W, qtables):
+    """a file up to and including SOS, in Pillow's order: SOI, APP0 (JFIF 1.01, units 0, density 1 x 1), one DQT per table (zigzag order),
+    SOF0 (Y 2x2, Cb 1x1, Cr 1x1), four DHT segments, SOS"""
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\0\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t in range(2):
+        out += _segment(0xDB, bytes((t,)) + bytes(int(v) for v in np.asarray(qtables)[t][ZIGZAG]))
+    out += _segment(0xC0, b"\x08" + H.to_bytes(2, "big") + W.to_bytes(2, "big") + b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01")
+    for tc_th, bits, vals in HUFFMAN:
+        out += _segment(0xC4, bytes((tc_th,)) + bytes(bits) + vals)
+    return out + _segment(0xDA, b"\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00")
+
+
+@functools.lru_cache(maxsize=32)
+def lower_jpeg(H, W, quality=100):
+    """A frame size and quality as the tables the kernels read (host arithmetic only; nothing is launched): a dict of
+    qtables (2,64) int32, natural order; divisors (2,64) int32 = 8 * q, natural order (the islow transform leaves its output scaled by 8);
+    huffman (4,256) int32; header, the bytes up to and including SOS; mcu_rows, mcu_cols, blocks (six per MCU); stream_capacity, the bytes
+    kept for one frame's entropy-coded data before stuffing (208 per block, in whole 1024-byte chunks); file_capacity, the most one file
+    takes (header + twice that + EOI); ``params``, all of it packed as MMJpegDesc.params wants it (int32 words; the header's bytes in
+    file order, padded to a word); and ``workspace_bytes(n)`` / ``files_offset(n)``, what n frames need and where their files start in it:
+    mm_jpeg_query_workspace and mm_jpeg_files_offset in Python.
+    The dict is cached and shared between calls: read, not written.  ValueError for what the kernel refuses."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H > 65535 or W > 65535:
+        raise ValueError("a JPEG frame is 1..65535 pixels each way, got %d x %d" % (H, W))
+    q = quant_tables(quality)
+    my, mx = (H + 15) // 16, (W + 15) // 16
+    blocks = my * mx * 6
+    if blocks > MAX_BLOCKS:
+        raise ValueError("a frame of %d x %d has %d blocks, more than %d" % (H, W, blocks, MAX_BLOCKS))
+    chunks = (blocks * BLOCK_BYTES + CHUNK_BYTES - 1) // CHUNK_BYTES
+    header = header_bytes(H, W, q)
+    pad = -len(header) % 4
+    params = np.concatenate([(8 * q).reshape(-1), huffman_codes().reshape(-1),
+                             np.frombuffer(header + b"\0" * pad, dtype=np.uint8).view(np.int32)]).astype(np.int32)
+    low = dict(H=H, W=W, quality=int(quality), qtables=q, divisors=8 * q, huffman=huffman_codes(), header=header, mcu_rows=my, mcu_cols=mx,
+               blocks=blocks, chunks=chunks, stream_capacity=chunks * CHUNK_BYTES, file_capacity=len(header) + 2 * chunks * CHUNK_BYTES + 2,
+               params=torch.from_numpy(params))
+
+    def up(x):
+        return (x + 255) // 256 * 256
+
+    # offsets (n + 1) int64 | the files | coefficients (int16 x 64 per block) | bits per block | bits per frame | the unstuffed streams | 0xFF per chunk
+    low["files_offset"] = lambda n: up((n + 1) * 8)
+    low["workspace_bytes"] = lambda n: (up((n + 1) * 8) + up(n * low["file_capacity"]) + up(n * blocks * 128) + up(n * blocks * 4) + up(n * 4)
+                                        + up(n * chunks * CHUNK_BYTES) + up(n * chunks * 4))
+    return low
+
+
+class JpegBatch:
+    """n complete JPEG files back to back in one host uint8 buffer; file i is ``buffer[offsets[i]:offsets[i + 1]]``"""
+
+    def __init__(self, buffer, offsets, shape=None):
+        self.buffer, self.offsets = buffer, [int(o) for o in offsets]
+        self.shape = (len(self.offsets) - 1,) if shape is None else tuple(shape)       # the frames' leading dimensions
+        self._view = memoryview(buffer.numpy() if torch.is_tensor(buffer) else np.asarray(buffer))
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def __getitem__(self, i):
+        n = len(self)
+        if not isinstance(i, (int, np.integer)):
+            raise TypeError("a JpegBatch is indexed by an int, got %r" % (i,))
+        if i < -n or i >= n:
+            raise IndexError("file %d of %d" % (i, n))
+        i = int(i) % n
+        return bytes(self._view[self.offsets[i]:self.offsets[i + 1]])
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def write(self, paths):
+        """file i to paths[i]"""
+        paths = list(paths)
+        if len(paths) != len(self):
+            raise ValueError("%d paths for %d files" % (len(paths), len(self)))
+        for i, p in enumerate(paths):
+            with open(p, "wb") as f:
+                f.write(self._view[self.offsets[i]:self.offsets[i + 1]])
+
+
+def check_frames(frames, quality):
+    """the argument errors of ``encode_jpeg``, before anything touches a device: (n, H, W)"""
+    if not torch.is_tensor(frames):
+        raise ValueError("frames must be a uint8 tensor (...,H,W,3), got %s" % type(frames))
+    if frames.dtype != torch.uint8:
+        raise ValueError("frames must be uint8 (...,H,W,3), got %s: export_images makes 8-bit frames from float renders" % frames.dtype)
+    if frames.dim() < 3 or frames.shape[-1] != 3:
+        raise ValueError("frames must have shape (...,H,W,3), got %s" % (tuple(frames.shape),))
+    if min(frames.shape) < 1:
+        raise ValueError("an empty batch: frames of shape %s" % (tuple(frames.shape),))
+    if int(np.prod(frames.shape[:-3], dtype=np.int64)) > MAX_FRAMES:
+        raise ValueError("at most %d frames in a call, got shape %s" % (MAX_FRAMES, tuple(frames.shape)))
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or quality < 1 or quality > 100:
+        raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
+    H, W = frames.shape[-3:-1]
+    return int(np.prod(frames.shape[:-3], dtype=np.int64)), int(H), int(W)
+
+
+@functools.lru_cache(maxsize=16)
+def _resident_params(device, H, W, quality):
+    """``lower_jpeg``'s table in the device's memory, kept between calls (a run repeats one size and quality): uploaded once, by a copy
+    that has finished when this returns, and only read afterwards, so calls on any stream may share it"""
+    return lower_jpeg(H, W, quality)["params"].to(device)
+
+
+def encode_jpeg(frames, quality=100):
+    """Frames as baseline JPEG files, the bytes ``PIL.Image.fromarray(f).save(file, 'JPEG', quality=quality)`` writes: a ``JpegBatch``.
+
+    frames       device uint8 (...,H,W,3), what ``export_images``, ``composite_frames`` and ``pyramid_frames`` return; any byte alignment;
+                 other strides go through ``.contiguous()``.  Float input is refused: ``export_images`` makes the bytes.
+    quality      int in 1..100, libjpeg's scale (the scripts use 100)
+
+    ``batch[i]`` is file i as bytes, ``batch.write(paths)`` writes them, ``batch.shape`` keeps the leading dimensions (files are in
+    row-major order over them).  Two device-to-host copies: the n + 1 offsets, then exactly the bytes used.  ``batch.buffer`` is pinned host
+    memory and stays allocated for as long as the batch is held: take ``bytes`` or ``write`` and drop the batch rather than collecting batches.
+    The 5 KB table of a (device, H, W, quality) is uploaded on the first call and stays resident.  ValueError: another dtype or
+    channel count, an empty batch, a quality outside 1..100, a frame larger than 65535 or of more than 2^20 blocks.
+
+        batch = encode_jpeg(pyramid_frames(pred, Xa, idx, **preset("tool/generate_market_test", B)))
+        batch.write(names)                                                # was: per image to_pil_image(...).save(name, 'JPEG', quality=100)"""
+    n, H, W = check_frames(frames, quality)
+    low = lower_jpeg(H, W, int(quality))
+    N.require_device(frames)
+    x = frames.detach().contiguous()
+    dev = x.device
+    host, par = low["params"], _resident_params(dev, H, W, int(quality))
+    d = N.MMJpegDesc()
+    d.n, d.H, d.W, d.header_bytes = n, H, W, len(low["header"])
+    d.frames, d.params_host, d.params = N.ptr(x), ctypes.c_void_p(host.data_ptr()), N.ptr(par)
+    ws_bytes, files_at = N.lib().mm_jpeg_query_workspace(ctypes.byref(d)), N.lib().mm_jpeg_files_offset(ctypes.byref(d))
+    if (ws_bytes, files_at) != (low["workspace_bytes"](n), low["files_offset"](n)):
+        raise RuntimeError("mm_jpeg_query_workspace gives %d bytes with the files at %d, lower_jpeg %d and %d"
+                           % (ws_bytes, files_at, low["workspace_bytes"](n), low["files_offset"](n)))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    d.workspace, d.workspace_bytes = N.ptr(ws), ws_bytes
+    N.check(N.lib().mm_jpeg_encode(ctypes.byref(d), N.current_stream(dev)), "mm_jpeg_encode")
+    off_host = torch.empty((n + 1,), dtype=torch.int64, pin_memory=True)
+    off_host.copy_(ws[:8 * (n + 1)].view(torch.int64))                     # copy 1 (blocking): the offsets
+    off = off_host.tolist()
+    buf = torch.empty((off[-1],), dtype=torch.uint8, pin_memory=True)
+    buf.copy_(ws[files_at:files_at + off[-1]])                            # copy 2 (blocking): exactly the bytes used
+    return JpegBatch(buf, off, frames.shape[:-3])

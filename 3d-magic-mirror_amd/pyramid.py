@@ -18,8 +18,8 @@ The pyramid's sums leave [0, 1] (uniform inputs range over about -0.25 ... 1.25)
 undefined: this kernel saturates to 0 / 255 and sends NaN to 0, as ``export_images`` does.
 
 Out of scope: poisson_image_editing.py (imported by that script, never called); the texture mix with the mean-texture bank (:339);
-reproducing the reference's random streams (the caller draws ``bg_index`` and the sigmas: ``draw_sigmas``); JPEG encoding; gradients; other
-numbers of levels.  Device tensors only."""
+reproducing the reference's random streams (the caller draws ``bg_index`` and the sigmas: ``draw_sigmas``); gradients; other
+numbers of levels.  JPEG encoding: ``encode_jpeg`` (jpeg.py).  Device tensors only."""
 import ctypes
 import functools
 

@@ -939,6 +939,53 @@ typedef struct MMPyramidDesc {
 int mm_pyramid_frames(const MMPyramidDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * JPEG: n device frames (n,H,W,3) of bytes -- what mm_export_images, mm_composite_frames and mm_pyramid_frames write, at any byte
+ * alignment -- as n complete baseline JPEG files, byte for byte what libjpeg(-turbo) writes for 4:2:0 with the standard Huffman tables,
+ * the islow DCT and quantisation tables q (Pillow's Image.save(f, 'JPEG', quality=...)).  The caller writes the file's head, SOI up to and
+ * including SOS, and gives the tables; everything after SOS is made on the device.  Integer arithmetic only (>> arithmetic):
+ *   colour    Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;
+ *             Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   edges     an MCU is 16 x 16 pixels, blocks Y00 Y01 Y10 Y11 Cb Cr.  Columns beyond W replicate the input's last column, rows beyond H
+ *             its last row up to an even height; chroma rows beyond ceil(H / 2) replicate the DOWNSAMPLED last row.  A luma block wholly
+ *             beyond ceil(W / 8) or ceil(H / 8) is a dummy: no AC, the DC of the block before it in MCU order.
+ *   chroma    (a + b + c + d + bias) >> 2 over 2 x 2, bias 1 on even output columns and 2 on odd ones
+ *   DCT       jfdctint (islow) on the samples minus 128, CONST_BITS 13, PASS1_BITS 2, rows then columns; the output is scaled by 8
+ *   quantise  sign(v) * ((|v| + (d >> 1)) / d) with the divisor d = 8 * q: half away from zero
+ *   entropy   MCUs in raster order, a DC predictor per component, ZRL for sixteen zeros, EOB unless coefficient 63 is non-zero, the last
+ *             byte padded with 1-bits, 0x00 after every 0xFF, then EOI.
+ * params is ONE table of 32-bit words that the caller uploads; params_host is the host's copy of it, validated before anything is
+ * launched:   divisors (2,64): luma, chroma, NATURAL order, each 8 * q with q in 1..255
+ *           | codes (4,256): DC luma, AC luma, DC chroma, AC chroma, per symbol size << 16 | code (0: no such symbol)
+ *           | the file's head, header_bytes bytes in file order, padded to a word.
+ * The workspace is the caller's, mm_jpeg_query_workspace bytes, 16-byte aligned; the library allocates nothing.  After the call it holds
+ * the results: at byte 0 offsets[n + 1] as int64, and from byte mm_jpeg_files_offset on the files back to back, file i being bytes
+ * [offsets[i], offsets[i + 1]) of that region: a caller copies the offsets, then exactly offsets[n] bytes.  The rest is scratch:
+ * int16 coefficients (128 bytes per block, six blocks per MCU), a bit count per block, the unstuffed streams at MM_JPEG_BLOCK_BYTES per
+ * block (a block codes to 20 + 63 * 26 bits at most) in whole chunks of MM_JPEG_CHUNK_BYTES, and a count per chunk; a file has room for
+ * header_bytes + twice its stream + 2.  A stream is never held in LDS.
+ * MM_ERR_BAD_SHAPE: n, H, W < 1; header_bytes outside [2, MM_JPEG_MAX_HEADER]; a divisor that is not 8 * (1..255); a code wider than its
+ * size or than 16 bits, or whose size plus category bits (symbol & 15) exceeds 26.  MM_ERR_UNSUPPORTED: H, W or n > 65535; more than MM_JPEG_MAX_BLOCKS blocks in a frame or 2^30 in a call (the
+ * queries return 0).  MM_ERR_WORKSPACE: too small or misaligned.
+ * Nine stream operations (one memset, eight launches), no host synchronisation; bitwise reproducible.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_JPEG_BLOCK_BYTES 208
+#define MM_JPEG_CHUNK_BYTES 1024
+#define MM_JPEG_MAX_BLOCKS (1 << 20)
+#define MM_JPEG_MAX_HEADER 4096
+typedef struct MMJpegDesc {
+    int32_t n, H, W;                /* the frames */
+    int32_t header_bytes;           /* bytes of the file's head in params */
+    const uint8_t* frames;          /* (n,H,W,3), dense, any alignment */
+    const int32_t* params_host;     /* host memory */
+    const int32_t* params;          /* device memory, the same words */
+    void* workspace;
+    size_t workspace_bytes;
+} MMJpegDesc;
+size_t mm_jpeg_query_workspace(const MMJpegDesc* desc);     /* reads n, H, W, header_bytes */
+size_t mm_jpeg_files_offset(const MMJpegDesc* desc);        /* where the files start in the workspace */
+int mm_jpeg_encode(const MMJpegDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -962,7 +1009,7 @@ const char* mm_last_error_detail(void);
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
- * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc (31 and 34 are unassigned). */
+ * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -980,7 +1027,8 @@ size_t mm_struct_size(int which);
  * addition, detected by mm_struct_size(30) != 0; still 9: MMCompositeDesc and mm_composite_frames, struct id 32 -- id 31 stays unassigned and
  * returns 0 --, an addition, detected by mm_struct_size(32) != 0; still 9: MMRenderIndexedDesc and mm_render_indexed_*, struct id 33, an
  * addition, detected by mm_struct_size(33) != 0; still 9: MMPyramidDesc and mm_pyramid_frames, struct id 35 -- id 34 stays unassigned and
- * returns 0 --, an addition, detected by mm_struct_size(35) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * returns 0 --, an addition, detected by mm_struct_size(35) != 0; still 9: MMJpegDesc and mm_jpeg_*, struct id 37 -- id 36 stays
+ * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
