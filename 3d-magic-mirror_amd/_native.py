@@ -6,6 +6,7 @@ RuntimeError is raised.  torch is used here only for device memory and the curre
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -426,6 +427,15 @@ def as_f32(t, dev):
     if t.dtype is torch.float32 and t.device == dev and t.is_contiguous():
         return t.detach()
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def upload_int32(values, device):
+    """int32 ``values`` (a tensor, or an array that is cast) to ``device`` through pinned host memory, without waiting: (host, dev).  A
+    descriptor may name the pinned copy as its host table; it is read before the call returns."""
+    src = values if torch.is_tensor(values) else torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32))
+    host = torch.empty(src.shape, dtype=torch.int32, pin_memory=True)
+    host.copy_(src)
+    return host, host.to(device, non_blocking=True)
 
 
 def ptr(t):

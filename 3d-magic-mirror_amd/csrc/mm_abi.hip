@@ -94,6 +94,30 @@ static int check_render(const MMRenderDesc* d, bool backward) {
     return MM_OK;
 }
 
+// what mm_composite_frames and mm_pyramid_frames (MMCompositeDesc, MMPyramidDesc) refuse alike: pointers, sizes, the rounding, a reflection
+// pad that would reflect twice, and the host's copy of the two index tables in front of params
+template <class Desc>
+static int check_frames(const Desc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (!d->renders || !d->backgrounds || !d->params_host || !d->params || !d->out) return MM_ERR_NULL_POINTER;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->n_fg <= 0 || d->n_bg <= 0 || (d->bg_C != 3 && d->bg_C != 4)) return MM_ERR_BAD_SHAPE;
+    if (d->rounding != 0 && d->rounding != 1) return MM_ERR_BAD_SHAPE;
+    if (d->H > (1 << 24) || d->W > (1 << 24)) return MM_ERR_BAD_SHAPE;      // sums of sizes and pads stay far inside an int32
+    const int32_t* bp = d->bg_pad;                                // a reflection reflects once: the pad is narrower than the image
+    if (bp[0] < 0 || bp[1] < 0 || bp[2] < 0 || bp[3] < 0 || bp[0] >= d->W || bp[1] >= d->W || bp[2] >= d->H || bp[3] >= d->H) return MM_ERR_BAD_SHAPE;
+    const int32_t* par = d->params_host;
+    for (int o = 0; o < d->B; ++o)
+        if (par[o] < 0 || par[o] >= d->n_fg || par[d->B + o] < 0 || par[d->B + o] >= d->n_bg) return MM_ERR_BAD_SHAPE;
+    return MM_OK;
+}
+
+// the n_out resize rows at `row` (both kernels' rows are MM_COMPOSITE_ROW_WORDS: mm_frame.h), of an axis of n_in behind its pad; leaves `row` behind them
+static int check_resize_rows(const int32_t*& row, int32_t n_out, int32_t n_in) {
+    for (int i = 0; i < n_out; ++i, row += MM_COMPOSITE_ROW_WORDS)
+        if (row[1] < 1 || row[1] > MM_COMPOSITE_MAX_TAPS || row[0] < 0 || row[0] > n_in - row[1]) return MM_ERR_BAD_SHAPE;
+    return MM_OK;
+}
+
 extern "C" {
 
 size_t mm_query_workspace(const MMRenderDesc* d) {
@@ -767,29 +791,21 @@ int mm_assemble_batch(const MMBatchDesc* d, mm_stream_t stream) {
 }
 
 int mm_composite_frames(const MMCompositeDesc* d, mm_stream_t stream) {
-    if (!d) return MM_ERR_NULL_POINTER;
-    if (!d->renders || !d->backgrounds || !d->params_host || !d->params || !d->out) return MM_ERR_NULL_POINTER;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->n_fg <= 0 || d->n_bg <= 0 || (d->bg_C != 3 && d->bg_C != 4)) return MM_ERR_BAD_SHAPE;
-    if (d->rounding != 0 && d->rounding != 1) return MM_ERR_BAD_SHAPE;
+    const int st = check_frames(d);
+    if (st != MM_OK) return st;
     const int32_t ks[2] = {d->mask_k, d->bg_k};
     for (int i = 0; i < 2; ++i)
         if (ks[i] < 1 || ks[i] > MM_COMPOSITE_MAX_KERNEL || !(ks[i] & 1)) return MM_ERR_BAD_SHAPE;
-    const int32_t lim = 1 << 24;                                  // sums of sizes and pads stay far inside an int32
-    if (d->H > lim || d->W > lim || d->mask_pad < 0 || d->mask_pad > lim) return MM_ERR_BAD_SHAPE;
-    // a reflection reflects once: the pad is narrower than the image, the blur radius narrower than what it reflects in
+    if (d->mask_pad < 0 || d->mask_pad > (1 << 24)) return MM_ERR_BAD_SHAPE;
+    // ... and the blur radius narrower than what it reflects in
     const int32_t* bp = d->bg_pad;
-    if (bp[0] < 0 || bp[1] < 0 || bp[2] < 0 || bp[3] < 0 || bp[0] >= d->W || bp[1] >= d->W || bp[2] >= d->H || bp[3] >= d->H) return MM_ERR_BAD_SHAPE;
     const int32_t Hp = d->H + bp[2] + bp[3], Wp = d->W + bp[0] + bp[1];
     if (d->mask_k / 2 >= d->H || d->mask_k / 2 >= d->W || d->bg_k / 2 >= Hp || d->bg_k / 2 >= Wp) return MM_ERR_BAD_SHAPE;
-    const int32_t* par = d->params_host;
-    for (int o = 0; o < d->B; ++o)
-        if (par[o] < 0 || par[o] >= d->n_fg || par[d->B + o] < 0 || par[d->B + o] >= d->n_bg) return MM_ERR_BAD_SHAPE;
-    const int32_t* row = par + 2 * (size_t)d->B + (size_t)d->B * d->mask_k + (size_t)d->B * d->bg_k;
+    const int32_t* row = d->params_host + 2 * (size_t)d->B + (size_t)d->B * d->mask_k + (size_t)d->B * d->bg_k;
     const int32_t n_out[4] = {d->H, d->W, d->H, d->W};
     const int32_t n_in[4] = {d->H + 2 * d->mask_pad, d->W + 2 * d->mask_pad, Hp, Wp};
     for (int t = 0; t < 4; ++t)
-        for (int i = 0; i < n_out[t]; ++i, row += MM_COMPOSITE_ROW_WORDS)
-            if (row[1] < 1 || row[1] > MM_COMPOSITE_MAX_TAPS || row[0] < 0 || row[0] > n_in[t] - row[1]) return MM_ERR_BAD_SHAPE;
+        if (check_resize_rows(row, n_out[t], n_in[t]) != MM_OK) return MM_ERR_BAD_SHAPE;
     if (mm::composite_lds_bytes(d, nullptr) > 160 * 1024) return MM_ERR_UNSUPPORTED;
     if ((long long)d->B * ((d->H + MM_COMPOSITE_ROWS - 1) / MM_COMPOSITE_ROWS) > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;
     mm::clear_stale_error();
@@ -797,26 +813,13 @@ int mm_composite_frames(const MMCompositeDesc* d, mm_stream_t stream) {
 }
 
 int mm_pyramid_frames(const MMPyramidDesc* d, mm_stream_t stream) {
-    if (!d) return MM_ERR_NULL_POINTER;
-    if (!d->renders || !d->backgrounds || !d->params_host || !d->params || !d->out) return MM_ERR_NULL_POINTER;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->n_fg <= 0 || d->n_bg <= 0 || (d->bg_C != 3 && d->bg_C != 4)) return MM_ERR_BAD_SHAPE;
-    if (d->rounding != 0 && d->rounding != 1) return MM_ERR_BAD_SHAPE;
-    if (d->k < 1 || d->k > MM_PYRAMID_MAX_KERNEL || !(d->k & 1)) return MM_ERR_BAD_SHAPE;
-    const int32_t lim = 1 << 24;                                  // sums of sizes and pads stay far inside an int32
-    if (d->H > lim || d->W > lim || d->B > lim) return MM_ERR_BAD_SHAPE;
-    // a reflection reflects once: the pad is narrower than the image, and so is the blur radius, at every level
+    const int st = check_frames(d);
+    if (st != MM_OK) return st;
+    if (d->k < 1 || d->k > MM_PYRAMID_MAX_KERNEL || !(d->k & 1) || d->B > (1 << 24)) return MM_ERR_BAD_SHAPE;
+    if (d->k / 2 >= d->H || d->k / 2 >= d->W) return MM_ERR_BAD_SHAPE;     // ... and so is the blur radius, at every level
     const int32_t* bp = d->bg_pad;
-    if (bp[0] < 0 || bp[1] < 0 || bp[2] < 0 || bp[3] < 0 || bp[0] >= d->W || bp[1] >= d->W || bp[2] >= d->H || bp[3] >= d->H) return MM_ERR_BAD_SHAPE;
-    if (d->k / 2 >= d->H || d->k / 2 >= d->W) return MM_ERR_BAD_SHAPE;
-    const int32_t* par = d->params_host;
-    for (int o = 0; o < d->B; ++o)
-        if (par[o] < 0 || par[o] >= d->n_fg || par[d->B + o] < 0 || par[d->B + o] >= d->n_bg) return MM_ERR_BAD_SHAPE;
-    const int32_t* row = par + 2 * (size_t)d->B + 9 * (size_t)d->B * d->k;
-    const int32_t n_out[2] = {d->H, d->W};
-    const int32_t n_in[2] = {d->H + bp[2] + bp[3], d->W + bp[0] + bp[1]};
-    for (int t = 0; t < 2; ++t)
-        for (int i = 0; i < n_out[t]; ++i, row += MM_PYRAMID_ROW_WORDS)
-            if (row[1] < 1 || row[1] > MM_PYRAMID_MAX_TAPS || row[0] < 0 || row[0] > n_in[t] - row[1]) return MM_ERR_BAD_SHAPE;
+    const int32_t* row = d->params_host + 2 * (size_t)d->B + 9 * (size_t)d->B * d->k;
+    if (check_resize_rows(row, d->H, d->H + bp[2] + bp[3]) != MM_OK || check_resize_rows(row, d->W, d->W + bp[0] + bp[1]) != MM_OK) return MM_ERR_BAD_SHAPE;
     if (mm::pyramid_lds_bytes(d, nullptr) > 160 * 1024) return MM_ERR_UNSUPPORTED;
     if ((long long)d->B * ((d->H + MM_PYRAMID_ROWS - 1) / MM_PYRAMID_ROWS) > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;
     mm::clear_stale_error();

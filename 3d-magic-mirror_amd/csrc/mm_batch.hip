@@ -252,10 +252,7 @@ int launch_assemble_batch(const MMBatchDesc* d, hipStream_t s) {
     a.images = d->images; a.segs = d->segs; a.offsets = (const long long*)d->offsets; a.sizes = d->sizes; a.rec = d->records;
     a.out = d->out; a.H = d->H; a.W = d->W; a.bg = d->bg != 0; a.n_images = d->n_images;
     const long long lds = batch_lds_bytes(d, &a);
-    if (lds > 64 * 1024) {                                    // more dynamic LDS than a kernel gets by default
-        const hipError_t e = hipFuncSetAttribute((const void*)assemble_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MM_BATCH_LDS);
-        if (e != hipSuccess) { (void)hipGetLastError(); last_launch_error() = {e, "assemble_batch_lds"}; return MM_ERR_LAUNCH; }
-    }
+    if (allow_large_lds((const void*)assemble_batch_kernel, lds, MM_BATCH_LDS, "assemble_batch_lds") != MM_OK) return MM_ERR_LAUNCH;
     const dim3 grid((unsigned)((d->H + MM_BATCH_ROWS - 1) / MM_BATCH_ROWS), (unsigned)d->B);
     hipLaunchKernelGGL(assemble_batch_kernel, grid, dim3(MM_BATCH_BLOCK), (size_t)lds, s, a);
     return launch_ok("assemble_batch");

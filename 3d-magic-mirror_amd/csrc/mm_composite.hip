@@ -20,18 +20,15 @@
 // ping-pong between: the source rows the band needs (the rows its vertical resize taps read, widened by the blur radius, reflected on the
 // fly), hblur, vblur, hresize, then the vertical resize, whose result goes to an LDS plane (the mask) or straight into the blend (a
 // background plane, quantised to a byte in LDS).  Every pass has x along the lanes: a lane's column-wise taps step by whole rows, its
-// neighbours read the neighbouring words, so no pass has a bank conflict beyond the two-way one of a resize's stride.  A band's bytes are one
-// contiguous piece of the output; they are laid out in LDS at the output's own 16-byte phase and leave as 16-byte stores, the bytes before
-// and after the aligned chunks one by one.  Neighbouring bands recompute the halo rows.  Nothing intermediate goes to memory; no atomics, no
-// workspace, no scratch; every output byte is written by one lane (bitwise reproducible).
+// neighbours read the neighbouring words, so no pass has a bank conflict beyond the two-way one of a resize's stride.  Neighbouring bands
+// recompute the halo rows.  Nothing intermediate goes to memory; no atomics, no workspace, no scratch; every output byte is written by one
+// lane (bitwise reproducible).  The index maps, the resize rows and their sums, the render accessor and the band's bytes (their LDS layout
+// and their way out) are mm_frame.h's, shared with mm_pyramid.hip; here are the hole fill, run_plane's order of stages and the blend.
 #include <hip/hip_runtime.h>
 
-#include "mm_device.h"
-#include "mm_quant.h"
+#include "mm_frame.h"
 
-#define MM_COMPOSITE_BLOCK 256
-#define MM_COMPOSITE_LDS (160 * 1024)
-#define MM_CW MM_COMPOSITE_ROW_WORDS
+#define MM_CW MM_FRAME_ROW_WORDS
 
 namespace mm {
 
@@ -54,25 +51,6 @@ __host__ __device__ inline CompLayout composite_layout(int B, int H, int W, int 
     return l;
 }
 
-__host__ __device__ inline int clampi(int i, int lo, int hi) { return i < lo ? lo : (i > hi ? hi : i); }
-// a reflection pad narrower than the dimension (the entry point holds pads and radii to that) reflects once
-__host__ __device__ inline int reflecti(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return clampi(i, 0, n - 1);
-}
-
-// the blurred rows [c_lo, c_lo + n) that the vertical resize taps of output rows [y0, y1) read through a replicate pad of p
-__host__ __device__ inline void band_rows(const int* ty, int y0, int y1, int p, int Hv, int& c_lo, int& n) {
-    int lo = 0x7fffffff, hi = -0x7fffffff;
-    for (int y = y0; y < y1; ++y) {
-        const int s = ty[y * MM_CW], e = s + clampi(ty[y * MM_CW + 1], 1, MM_COMPOSITE_MAX_TAPS);
-        lo = s < lo ? s : lo; hi = e > hi ? e : hi;
-    }
-    c_lo = clampi(lo - p, 0, Hv - 1);
-    n = clampi(hi - 1 - p, 0, Hv - 1) - c_lo + 1;
-}
-
 struct Plane {
     int Hv, Wv;                                               // the virtual source: the image behind its reflection pad
     int pl, pt;                                               // the image's origin in it
@@ -85,18 +63,18 @@ struct Plane {
 template <class Src, class Sink>
 __device__ inline void run_plane(const CompArgs& a, const Plane& P, float* b0, float* b1, int y0, int y1, Src src, Sink sink) {
     MM_FP_EXACT
-    const int tid = threadIdx.x, r = P.k >> 1, Wv = P.Wv, W = a.W;
+    const int tid = threadIdx.x, r = P.k >> 1, Hv = P.Hv, Wv = P.Wv, W = a.W;
     int c_lo, nvb;
-    band_rows(P.ty, y0, y1, P.p, P.Hv, c_lo, nvb);
+    frame_src_rows(P.ty, y0, y1, P.p, Hv, c_lo, nvb);        // the blurred rows the band's vertical resize reads
     const int ns = nvb + 2 * r;
     if ((long long)ns * Wv > a.cap) return;                   // (uniform) a device table that is not the one the host sized the LDS from
-    for (int i = tid; i < ns * Wv; i += MM_COMPOSITE_BLOCK) { // source rows, reflected twice: at the virtual source's edge, then at the image's
+    for (int i = tid; i < ns * Wv; i += MM_FRAME_BLOCK) { // source rows, reflected twice: at the virtual source's edge, then at the image's
         const int row = i / Wv, x = i - row * Wv;
-        const int vy = reflecti(c_lo - r + row, P.Hv);
+        const int vy = reflecti(c_lo - r + row, Hv);
         b0[i] = src(reflecti(vy - P.pt, a.H), reflecti(x - P.pl, W));
     }
     __syncthreads();
-    for (int i = tid; i < ns * Wv; i += MM_COMPOSITE_BLOCK) { // horizontal blur
+    for (int i = tid; i < ns * Wv; i += MM_FRAME_BLOCK) { // horizontal blur
         const int row = i / Wv, x = i - row * Wv;
         const float* s = b0 + row * Wv;
         float acc = 0.0f;
@@ -104,35 +82,27 @@ __device__ inline void run_plane(const CompArgs& a, const Plane& P, float* b0, f
         b1[i] = acc;
     }
     __syncthreads();
-    for (int i = tid; i < nvb * Wv; i += MM_COMPOSITE_BLOCK) {   // vertical blur: blurred row c_lo + row reads staged rows row .. row + 2r
+    for (int i = tid; i < nvb * Wv; i += MM_FRAME_BLOCK) {   // vertical blur: blurred row c_lo + row reads staged rows row .. row + 2r
         const float* s = b1 + i;
         float acc = 0.0f;
         for (int j = 0; j < P.k; ++j) acc = acc + P.taps[j] * s[j * Wv];
         b0[i] = acc;
     }
     __syncthreads();
-    for (int i = tid; i < nvb * W; i += MM_COMPOSITE_BLOCK) { // horizontal resize through the replicate pad
+    for (int i = tid; i < nvb * W; i += MM_FRAME_BLOCK) { // horizontal resize through the replicate pad
         const int row = i / W, x = i - row * W;
-        const int* t = P.tx + x * MM_CW;
-        const int s0 = t[0] - P.p, n = clampi(t[1], 1, MM_COMPOSITE_MAX_TAPS);
         const float* s = b0 + row * Wv;
-        float acc = 0.0f;
-        for (int q = 0; q < n; ++q) acc = acc + __int_as_float(t[2 + q]) * s[clampi(s0 + q, 0, Wv - 1)];
-        b1[i] = acc;
+        b1[i] = frame_resize_sum(P.tx, x, P.p, [=](int j) { return s[clampi(j, 0, Wv - 1)]; });
     }
     __syncthreads();
-    for (int i = tid; i < (y1 - y0) * W; i += MM_COMPOSITE_BLOCK) {   // vertical resize
+    for (int i = tid; i < (y1 - y0) * W; i += MM_FRAME_BLOCK) {   // vertical resize
         const int yo = i / W, x = i - yo * W;
-        const int* t = P.ty + (y0 + yo) * MM_CW;
-        const int s0 = t[0] - P.p, n = clampi(t[1], 1, MM_COMPOSITE_MAX_TAPS);
-        float acc = 0.0f;
-        for (int q = 0; q < n; ++q) acc = acc + __int_as_float(t[2 + q]) * b1[(clampi(s0 + q, 0, P.Hv - 1) - c_lo) * W + x];
-        sink(yo, x, acc);
+        sink(yo, x, frame_resize_sum(P.ty, y0 + yo, P.p, [=](int j) { return b1[(clampi(j, 0, Hv - 1) - c_lo) * W + x]; }));
     }
     __syncthreads();
 }
 
-__global__ __launch_bounds__(MM_COMPOSITE_BLOCK) void composite_kernel(CompArgs a) {
+__global__ __launch_bounds__(MM_FRAME_BLOCK) void composite_kernel(CompArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int H = a.H, W = a.W;
     float* b0 = (float*)smem;
@@ -140,19 +110,12 @@ __global__ __launch_bounds__(MM_COMPOSITE_BLOCK) void composite_kernel(CompArgs 
     float* M = b1 + a.cap;                                    // [MM_COMPOSITE_ROWS][W] the band's finished mask
     unsigned char* bytes = (unsigned char*)(M + ((MM_COMPOSITE_ROWS * W + 3) & ~3));
 
-    const int tid = threadIdx.x;
     const int o = blockIdx.x / a.nbands, band = blockIdx.x - o * a.nbands;
     const int y0 = band * MM_COMPOSITE_ROWS, y1 = min(y0 + MM_COMPOSITE_ROWS, H);
     const CompLayout l = composite_layout(a.B, H, W, a.mk, a.bk);
-    // the entry point checked the host's copy of the indices; a device copy that differs reads another image, never a wild address
-    const long long fi = clampi(a.par[l.fg_index + o], 0, a.n_fg - 1), bi = clampi(a.par[l.bg_index + o], 0, a.n_bg - 1);
+    const long long fi = frame_index(a.par + l.fg_index, o, a.n_fg), bi = frame_index(a.par + l.bg_index, o, a.n_bg);
     const long long HW = (long long)H * W;
-    const float* fgp = a.fg + fi * 4 * HW;
-    const int nhwc = a.nhwc;
-    auto fg_at = [=](int c, int y, int x) -> float {
-        const long long p = (long long)y * W + x;
-        return nhwc ? fgp[p * 4 + c] : fgp[c * HW + p];
-    };
+    const FrameFg fg_at = {a.fg + fi * 4 * HW, HW, W, a.nhwc};
 
     Plane P;
     P.Hv = H; P.Wv = W; P.pl = 0; P.pt = 0; P.k = a.mk; P.taps = (const float*)(a.par + l.mask_taps) + (long long)o * a.mk;
@@ -189,20 +152,12 @@ __global__ __launch_bounds__(MM_COMPOSITE_BLOCK) void composite_kernel(CompArgs 
                       const int y = y0 + yo;
                       const float m = M[yo * W + x];
                       const float f = fg_at(c, y, x);
-                      const unsigned q = quant(f * m + v * (1.0f - m), nearest);
-                      if (as_float) outf[(((long long)o * 3 + c) * H + y) * W + x] = unquant(q);
-                      else bytes[al + (yo * W + x) * 3 + c] = (unsigned char)q;
+                      frame_store_pixel(f * m + v * (1.0f - m), nearest, as_float, outf, o, c, y, x, H, W, bytes, al, yo * W + x);
                   });
     }
     if (as_float) return;
     // (run_plane ended on a barrier: the band's bytes are all in LDS)
-    const int n = (y1 - y0) * W * 3;
-    int head = (16 - al) & 15;
-    if (head > n) head = n;
-    const int nch = (n - head) >> 4, done = head + nch * 16;
-    for (int j = tid; j < nch; j += MM_COMPOSITE_BLOCK) *(uint4*)(g + head + 16 * j) = *(const uint4*)(bytes + al + head + 16 * j);
-    if (tid < head) g[tid] = bytes[al + tid];
-    if (tid >= 16 && tid - 16 < n - done) g[done + tid - 16] = bytes[al + done + tid - 16];
+    frame_flush_bytes(g, bytes, al, (y1 - y0) * W * 3, threadIdx.x);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -215,9 +170,9 @@ long long composite_lds_bytes(const MMCompositeDesc* d, CompArgs* a) {
     for (int y0 = 0; y0 < d->H; y0 += MM_COMPOSITE_ROWS) {
         const int y1 = y0 + MM_COMPOSITE_ROWS < d->H ? y0 + MM_COMPOSITE_ROWS : d->H;
         int c_lo, n;
-        band_rows(d->params_host + l.mask_y, y0, y1, d->mask_pad, d->H, c_lo, n);
+        frame_src_rows(d->params_host + l.mask_y, y0, y1, d->mask_pad, d->H, c_lo, n);
         const long long m = (long long)(n + d->mask_k - 1) * d->W;
-        band_rows(d->params_host + l.bg_y, y0, y1, 0, Hp, c_lo, n);
+        frame_src_rows(d->params_host + l.bg_y, y0, y1, 0, Hp, c_lo, n);
         const long long b = (long long)(n + d->bg_k - 1) * Wp;
         cap = m > cap ? m : cap;
         cap = b > cap ? b : cap;
@@ -225,8 +180,7 @@ long long composite_lds_bytes(const MMCompositeDesc* d, CompArgs* a) {
     cap = (cap + 3) & ~3LL;
     if (a) a->cap = cap < 0x7fffffff ? (int)cap : 0x7fffffff;
     const long long mw = ((long long)MM_COMPOSITE_ROWS * d->W + 3) & ~3LL;
-    const long long nb = ((long long)MM_COMPOSITE_ROWS * d->W * 3 + 16 + 15) & ~15LL;
-    return 4 * (2 * cap + mw) + nb;
+    return 4 * (2 * cap + mw) + frame_band_bytes_lds(MM_COMPOSITE_ROWS, d->W);
 }
 
 int launch_composite(const MMCompositeDesc* d, hipStream_t s) {
@@ -238,11 +192,8 @@ int launch_composite(const MMCompositeDesc* d, hipStream_t s) {
     a.nearest = d->rounding; a.as_float = d->as_float != 0;
     a.nbands = (d->H + MM_COMPOSITE_ROWS - 1) / MM_COMPOSITE_ROWS;
     const long long lds = composite_lds_bytes(d, &a);
-    if (lds > 64 * 1024) {                                    // more dynamic LDS than a kernel gets by default
-        const hipError_t e = hipFuncSetAttribute((const void*)composite_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MM_COMPOSITE_LDS);
-        if (e != hipSuccess) { (void)hipGetLastError(); last_launch_error() = {e, "composite_lds"}; return MM_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)(d->B * a.nbands)), dim3(MM_COMPOSITE_BLOCK), (size_t)lds, s, a);
+    if (allow_large_lds((const void*)composite_kernel, lds, MM_FRAME_LDS, "composite_lds") != MM_OK) return MM_ERR_LAUNCH;
+    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)(d->B * a.nbands)), dim3(MM_FRAME_BLOCK), (size_t)lds, s, a);
     return launch_ok("composite");
 }
 

@@ -462,6 +462,15 @@ inline int launch_ok(const char* what) {
     last_launch_error() = {e, what};
     return MM_ERR_LAUNCH;
 }
+// more dynamic LDS than a kernel gets by default (64 KiB) has to be asked for, up to `limit`: MM_OK, or MM_ERR_LAUNCH with the error kept under `what`
+inline int allow_large_lds(const void* kernel, long long lds, int limit, const char* what) {
+    if (lds <= 64 * 1024) return MM_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    if (e == hipSuccess) return MM_OK;
+    (void)hipGetLastError();
+    last_launch_error() = {e, what};
+    return MM_ERR_LAUNCH;
+}
 // errors left behind by the caller's own earlier runtime calls (e.g. hipEventQuery -> hipErrorNotReady) are not ours
 inline void clear_stale_error() { (void)hipGetLastError(); }
 

@@ -28,21 +28,18 @@
 // band's own rows, into the plane's KEEP slot.  The mask goes first and keeps m1..m3; then, per colour channel, the background (hresize from
 // memory into T, vresize into A, which also keeps bg0) and the render cascades keep bg0..bg3 and obj1..obj3 (obj0 is read from memory again)
 // and the blend reads the ten planes in the stated order.  Every pass has x along the lanes: a lane's column-wise taps step by whole rows,
-// its neighbours read the neighbouring words, so no pass has a bank conflict.  A band's bytes are one contiguous piece of the output; they
-// are laid out in LDS at the output's own 16-byte phase and leave as 16-byte stores, the bytes before and after the aligned chunks one by
-// one.  Nothing intermediate goes to memory; no workspace, no atomics, no scratch; every output byte is written by one lane (bitwise
-// reproducible).  Dynamic LDS only: 4 * (2 * cap + 10 * bw) + bytes, cap = the most rows any band stages (level 0's, or the resize's
+// its neighbours read the neighbouring words, so no pass has a bank conflict.  The index maps, the resize rows and their sums, the render
+// accessor and the band's bytes (their LDS layout and their way out) are mm_frame.h's, shared with mm_composite.hip; here are the level
+// rows, the cascade, the keep slots and the blend.  Nothing intermediate goes to memory; no workspace, no atomics, no scratch; every
+// output byte is written by one lane (bitwise reproducible).  Dynamic LDS only: 4 * (2 * cap + 10 * bw) + bytes, cap = the most rows any band stages (level 0's, or the resize's
 // source rows) times W, bw = 8 * W, all rounded to 16 bytes.  MM_PYRAMID_MAX_KERNEL is 15: LDS does not force less -- kernel 15 at 128 x 128
 // behind a pad of 16 takes 107 KiB, kernel 7 at 256 x 256 148 KiB -- and a call that needs more than 160 KiB is refused.
 // The kernel has two instances: kernel size 7, the call site's, at compile time (its tap loops unroll), and the general one.
 #include <hip/hip_runtime.h>
 
-#include "mm_device.h"
-#include "mm_quant.h"
+#include "mm_frame.h"
 
-#define MM_PYR_BLOCK 256
-#define MM_PYR_LDS (160 * 1024)
-#define MM_PW MM_PYRAMID_ROW_WORDS
+#define MM_PW MM_FRAME_ROW_WORDS
 #define MM_PYR_KEEP 10                                        // m1 m2 m3 | bg0 bg1 bg2 bg3 | obj1 obj2 obj3
 
 namespace mm {
@@ -66,14 +63,6 @@ __host__ __device__ inline PyrLayout pyramid_layout(int B, int H, int W, int k) 
     return l;
 }
 
-__host__ __device__ inline int pyr_clamp(int i, int lo, int hi) { return i < lo ? lo : (i > hi ? hi : i); }
-// a pad or radius narrower than the dimension (the entry point holds them to that) reflects once
-__host__ __device__ inline int pyr_reflect(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return pyr_clamp(i, 0, n - 1);
-}
-
 // the rows [lo[l], hi[l]) of level l that the band [y0, y1) needs
 struct PyrRows { int lo[MM_PYRAMID_LEVELS + 1], hi[MM_PYRAMID_LEVELS + 1]; };
 __host__ __device__ inline PyrRows pyramid_rows(int y0, int y1, int r, int H) {
@@ -87,17 +76,6 @@ __host__ __device__ inline PyrRows pyramid_rows(int y0, int y1, int r, int H) {
     return R;
 }
 
-// the rows [c_lo, c_lo + n) of the virtual background that the vertical resize taps of rows [lo, hi) read
-__host__ __device__ inline void pyramid_src_rows(const int* ty, int lo, int hi, int Hp, int& c_lo, int& n) {
-    int a = 0x7fffffff, b = -0x7fffffff;
-    for (int y = lo; y < hi; ++y) {
-        const int s = ty[y * MM_PW], e = s + pyr_clamp(ty[y * MM_PW + 1], 1, MM_PYRAMID_MAX_TAPS);
-        a = s < a ? s : a; b = e > b ? e : b;
-    }
-    c_lo = pyr_clamp(a, 0, Hp - 1);
-    n = pyr_clamp(b - 1, 0, Hp - 1) - c_lo + 1;
-}
-
 // level 0 of a plane lies in A on rows [R.lo[0], R.hi[0]); leaves levels 1..3 of the band's rows in keep[0], keep[bw], keep[2 bw].
 // K: the kernel size at compile time (the tap loops unroll: the taps arrive in one scalar load and a lane's LDS reads are issued together,
 // where the run-time loop waits for every tap's read in turn), or 0 for the size in a.k.  The order of the sums is the same.
@@ -109,20 +87,20 @@ __device__ inline void pyramid_cascade(const PyrArgs& a, const PyrRows& R, const
     for (int l = 1; l <= MM_PYRAMID_LEVELS; ++l) {
         const float* tp = taps + (l - 1) * k;
         const int lo_in = R.lo[l - 1], n_in = R.hi[l - 1] - lo_in, lo = R.lo[l], n = R.hi[l] - lo;
-        for (int i = tid; i < n_in * W; i += MM_PYR_BLOCK) {  // horizontal blur of level l - 1
+        for (int i = tid; i < n_in * W; i += MM_FRAME_BLOCK) {  // horizontal blur of level l - 1
             const int row = i / W, x = i - row * W;
             const float* s = A + row * W;
             float acc = 0.0f;
 #pragma unroll
-            for (int j = 0; j < k; ++j) acc = acc + tp[j] * s[pyr_reflect(x + j - r, W)];
+            for (int j = 0; j < k; ++j) acc = acc + tp[j] * s[reflecti(x + j - r, W)];
             T[i] = acc;
         }
         __syncthreads();
-        for (int i = tid; i < n * W; i += MM_PYR_BLOCK) {     // vertical blur: row y of level l reads rows R(y - r .. y + r) of level l - 1
+        for (int i = tid; i < n * W; i += MM_FRAME_BLOCK) {     // vertical blur: row y of level l reads rows R(y - r .. y + r) of level l - 1
             const int row = i / W, x = i - row * W, y = lo + row;
             float acc = 0.0f;
 #pragma unroll
-            for (int j = 0; j < k; ++j) acc = acc + tp[j] * T[pyr_clamp(pyr_reflect(y + j - r, H) - lo_in, 0, n_in - 1) * W + x];
+            for (int j = 0; j < k; ++j) acc = acc + tp[j] * T[clampi(reflecti(y + j - r, H) - lo_in, 0, n_in - 1) * W + x];
             if (l < MM_PYRAMID_LEVELS) A[i] = acc;
             if (y >= y0 && y < y1) keep[(l - 1) * a.bw + (y - y0) * W + x] = acc;
         }
@@ -131,7 +109,7 @@ __device__ inline void pyramid_cascade(const PyrArgs& a, const PyrRows& R, const
 }
 
 template <int K>
-__global__ __launch_bounds__(MM_PYR_BLOCK) void pyramid_blend_kernel(PyrArgs a) {
+__global__ __launch_bounds__(MM_FRAME_BLOCK) void pyramid_blend_kernel(PyrArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int H = a.H, W = a.W, bw = a.bw;
     float* A = (float*)smem;
@@ -146,26 +124,20 @@ __global__ __launch_bounds__(MM_PYR_BLOCK) void pyramid_blend_kernel(PyrArgs a) 
     const int y0 = band * MM_PYRAMID_ROWS, y1 = min(y0 + MM_PYRAMID_ROWS, H);
     const int k = K > 0 ? K : a.k;
     const PyrLayout l = pyramid_layout(a.B, H, W, k);
-    // the entry point checked the host's copy of the indices; a device copy that differs reads another image, never a wild address
-    const long long fi = pyr_clamp(a.par[l.fg_index + o], 0, a.n_fg - 1), bi = pyr_clamp(a.par[l.bg_index + o], 0, a.n_bg - 1);
+    const long long fi = frame_index(a.par + l.fg_index, o, a.n_fg), bi = frame_index(a.par + l.bg_index, o, a.n_bg);
     const long long HW = (long long)H * W;
-    const float* fgp = a.fg + fi * 4 * HW;
-    const int nhwc = a.nhwc;
-    auto fg_at = [=](int c, int y, int x) -> float {
-        const long long p = (long long)y * W + x;
-        return nhwc ? fgp[p * 4 + c] : fgp[c * HW + p];
-    };
+    const FrameFg fg_at = {a.fg + fi * 4 * HW, HW, W, a.nhwc};
     const float* taps = (const float*)(a.par + l.taps) + (long long)o * 9 * k;       // [kind][level][k]
     const PyrRows R = pyramid_rows(y0, y1, k >> 1, H);
     const int lo0 = R.lo[0], n0 = R.hi[0] - lo0;
-    const int Hp = H + a.pt + a.pb, Wp = W + a.pl + a.pr;
+    const int Hp = H + a.pt + a.pb, Wp = W + a.pl + a.pr, pl = a.pl;
     const int* ty = a.par + l.bg_y;
     const int* tx = a.par + l.bg_x;
     int c_lo, nsrc;
-    pyramid_src_rows(ty, lo0, R.hi[0], Hp, c_lo, nsrc);
+    frame_src_rows(ty, lo0, R.hi[0], 0, Hp, c_lo, nsrc);      // the rows of the virtual background that level 0's vertical resize reads
     if ((long long)(nsrc > n0 ? nsrc : n0) * W > a.cap) return;   // (uniform) a device table that is not the one the host sized the LDS from
 
-    for (int i = tid; i < n0 * W; i += MM_PYR_BLOCK) {        // the mask
+    for (int i = tid; i < n0 * W; i += MM_FRAME_BLOCK) {        // the mask
         const int row = i / W, x = i - row * W;
         A[i] = fg_at(3, lo0 + row, x);
     }
@@ -177,36 +149,27 @@ __global__ __launch_bounds__(MM_PYR_BLOCK) void pyramid_blend_kernel(PyrArgs a) 
     float* outf = (float*)a.out;
     for (int c = 0; c < 3; ++c) {
         const float* bgp = a.bg + (bi * a.bgC + c) * HW;
-        for (int i = tid; i < nsrc * W; i += MM_PYR_BLOCK) {  // background: horizontal resize of the padded rows, straight from memory
-            MM_FP_EXACT
+        for (int i = tid; i < nsrc * W; i += MM_FRAME_BLOCK) {  // background: horizontal resize of the padded rows, straight from memory
             const int row = i / W, x = i - row * W;
-            const float* s = bgp + (long long)pyr_reflect(c_lo + row - a.pt, H) * W;
-            const int* t = tx + x * MM_PW;
-            const int s0 = t[0], n = pyr_clamp(t[1], 1, MM_PYRAMID_MAX_TAPS);
-            float acc = 0.0f;
-            for (int q = 0; q < n; ++q) acc = acc + __int_as_float(t[2 + q]) * s[pyr_reflect(pyr_clamp(s0 + q, 0, Wp - 1) - a.pl, W)];
-            T[i] = acc;
+            const float* s = bgp + (long long)reflecti(c_lo + row - a.pt, H) * W;
+            T[i] = frame_resize_sum(tx, x, 0, [=](int j) { return s[reflecti(clampi(j, 0, Wp - 1) - pl, W)]; });
         }
         __syncthreads();
-        for (int i = tid; i < n0 * W; i += MM_PYR_BLOCK) {    // vertical resize: level 0 of the background
-            MM_FP_EXACT
+        for (int i = tid; i < n0 * W; i += MM_FRAME_BLOCK) {    // vertical resize: level 0 of the background
             const int row = i / W, x = i - row * W, y = lo0 + row;
-            const int* t = ty + y * MM_PW;
-            const int s0 = t[0], n = pyr_clamp(t[1], 1, MM_PYRAMID_MAX_TAPS);
-            float acc = 0.0f;
-            for (int q = 0; q < n; ++q) acc = acc + __int_as_float(t[2 + q]) * T[pyr_clamp(pyr_clamp(s0 + q, 0, Hp - 1) - c_lo, 0, nsrc - 1) * W + x];
+            const float acc = frame_resize_sum(ty, y, 0, [=](int j) { return T[clampi(clampi(j, 0, Hp - 1) - c_lo, 0, nsrc - 1) * W + x]; });
             A[i] = acc;
             if (y >= y0 && y < y1) KB[(y - y0) * W + x] = acc;
         }
         __syncthreads();
         pyramid_cascade<K>(a, R, taps + 3 * k, A, T, KB + bw, y0, y1);
-        for (int i = tid; i < n0 * W; i += MM_PYR_BLOCK) {    // the render's plane
+        for (int i = tid; i < n0 * W; i += MM_FRAME_BLOCK) {    // the render's plane
             const int row = i / W, x = i - row * W;
             A[i] = fg_at(c, lo0 + row, x);
         }
         __syncthreads();
         pyramid_cascade<K>(a, R, taps + 6 * k, A, T, KO, y0, y1);
-        for (int i = tid; i < (y1 - y0) * W; i += MM_PYR_BLOCK) {
+        for (int i = tid; i < (y1 - y0) * W; i += MM_FRAME_BLOCK) {
             MM_FP_EXACT
             const int yo = i / W, x = i - yo * W, y = y0 + yo;
             const float m1 = KM[i], m2 = KM[bw + i], m3 = KM[2 * bw + i];
@@ -218,21 +181,13 @@ __global__ __launch_bounds__(MM_PYR_BLOCK) void pyramid_blend_kernel(PyrArgs a) 
             t = t + (obj1 - obj2) * m2;
             t = t + (bg0 - bg1) * (1.0f - m1);
             t = t + (obj0 - obj1) * m1;
-            const unsigned q = quant(t, a.nearest);
-            if (a.as_float) outf[(((long long)o * 3 + c) * H + y) * W + x] = unquant(q);
-            else bytes[al + i * 3 + c] = (unsigned char)q;
+            frame_store_pixel(t, a.nearest, a.as_float, outf, o, c, y, x, H, W, bytes, al, i);
         }
         // (the next channel's first write to a keep slot lies behind a barrier that every lane reaches after this loop)
     }
     if (a.as_float) return;
     __syncthreads();                                          // the band's bytes are all in LDS
-    const int n = (y1 - y0) * W * 3;
-    int head = (16 - al) & 15;
-    if (head > n) head = n;
-    const int nch = (n - head) >> 4, done = head + nch * 16;
-    for (int j = tid; j < nch; j += MM_PYR_BLOCK) *(uint4*)(g + head + 16 * j) = *(const uint4*)(bytes + al + head + 16 * j);
-    if (tid < head) g[tid] = bytes[al + tid];
-    if (tid >= 16 && tid - 16 < n - done) g[done + tid - 16] = bytes[al + done + tid - 16];
+    frame_flush_bytes(g, bytes, al, (y1 - y0) * W * 3, tid);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -246,7 +201,7 @@ long long pyramid_lds_bytes(const MMPyramidDesc* d, PyrArgs* a) {
         const int y1 = y0 + MM_PYRAMID_ROWS < d->H ? y0 + MM_PYRAMID_ROWS : d->H;
         const PyrRows R = pyramid_rows(y0, y1, d->k >> 1, d->H);
         int c_lo, n;
-        pyramid_src_rows(d->params_host + l.bg_y, R.lo[0], R.hi[0], Hp, c_lo, n);
+        frame_src_rows(d->params_host + l.bg_y, R.lo[0], R.hi[0], 0, Hp, c_lo, n);
         const int n0 = R.hi[0] - R.lo[0];
         rows = n > rows ? n : rows;
         rows = n0 > rows ? n0 : rows;
@@ -254,8 +209,7 @@ long long pyramid_lds_bytes(const MMPyramidDesc* d, PyrArgs* a) {
     const long long cap = (rows * d->W + 3) & ~3LL;
     const long long bw = ((long long)MM_PYRAMID_ROWS * d->W + 3) & ~3LL;
     if (a) { a->cap = cap < 0x7fffffff ? (int)cap : 0x7fffffff; a->bw = (int)bw; }
-    const long long nb = ((long long)MM_PYRAMID_ROWS * d->W * 3 + 16 + 15) & ~15LL;
-    return 4 * (2 * cap + MM_PYR_KEEP * bw) + nb;
+    return 4 * (2 * cap + MM_PYR_KEEP * bw) + frame_band_bytes_lds(MM_PYRAMID_ROWS, d->W);
 }
 
 int launch_pyramid(const MMPyramidDesc* d, hipStream_t s) {
@@ -268,11 +222,8 @@ int launch_pyramid(const MMPyramidDesc* d, hipStream_t s) {
     const long long lds = pyramid_lds_bytes(d, &a);
     // kernel 7 is the call site's (tool/generate_market_test.py:330) and has its own instance; every other size runs the general one
     void (*const kernel)(PyrArgs) = d->k == 7 ? pyramid_blend_kernel<7> : pyramid_blend_kernel<0>;
-    if (lds > 64 * 1024) {                                    // more dynamic LDS than a kernel gets by default
-        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MM_PYR_LDS);
-        if (e != hipSuccess) { (void)hipGetLastError(); last_launch_error() = {e, "pyramid_lds"}; return MM_ERR_LAUNCH; }
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(d->B * a.nbands)), dim3(MM_PYR_BLOCK), (size_t)lds, s, a);
+    if (allow_large_lds((const void*)kernel, lds, MM_FRAME_LDS, "pyramid_lds") != MM_OK) return MM_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(d->B * a.nbands)), dim3(MM_FRAME_BLOCK), (size_t)lds, s, a);
     return launch_ok("pyramid");
 }
 

@@ -210,9 +210,7 @@ def assemble_records(pool, records, out_hw, bg=False):
     N.require_device(pool.buffer)
     H, W = (int(v) for v in out_hw)
     B = records.shape[0]
-    host = torch.empty((B, REC_INTS), dtype=torch.int32, pin_memory=True)
-    host.numpy()[...] = records
-    dev = host.to(pool.device, non_blocking=True)
+    host, dev = N.upload_int32(records, pool.device)
     out = torch.empty((B, 4, H, W), dtype=torch.float32, device=pool.device)
     d = N.MMBatchDesc()
     d.B, d.H, d.W, d.n_images, d.bg = B, H, W, len(pool), int(bool(bg))

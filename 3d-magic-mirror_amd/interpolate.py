@@ -40,7 +40,7 @@ def _indices(idx, B, dev, name):
         raise ValueError("%s must hold %d integers, got shape %s dtype %s" % (name, B, a.shape, a.dtype))
     if a.min() < 0 or a.max() >= B:
         raise ValueError("%s holds indices outside [0, %d): min %d, max %d" % (name, B, int(a.min()), int(a.max())))
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).pin_memory().to(dev, non_blocking=True)
+    return N.upload_int32(a, dev)[1]
 
 
 def _alpha(a, B, dev, name):

@@ -7,7 +7,7 @@ cascaded on the mask, three on a random background, three on the render, four di
 ``bg3*(1-mask3) + obj3*mask3 + lbg2*(1-mask2) + lobj2*mask2 + lbg1*(1-mask1) + lobj1*mask1`` and ``np.uint8(x * 255)`` behind a
 blocking ``.cpu()`` -- as ONE launch for all the frames of a batch, and one byte-sized copy to the host.
 
-The host lowers a call to small tables (``lower_pyramid``) with composite.py's ``gaussian_taps`` and ``resize_taps``; no transcendental
+The host lowers a call to small tables (``lower_pyramid``) with frames.py's ``gaussian_taps`` and ``resize_taps``; no transcendental
 runs on the device.  The device then runs, per frame and in fp32 with every operation rounded as written and every sum in ascending tap
 order from 0: the reflection pad (index arithmetic) and separable resize (x, then y) of the background -- no blur before it, this call
 site's order --; for each of the seven planes (mask, three background, three render) a cascade of three separable blurs (x, then y), each
@@ -20,21 +20,18 @@ undefined: this kernel saturates to 0 / 255 and sends NaN to 0, as ``export_imag
 Out of scope: poisson_image_editing.py (imported by that script, never called); the texture mix with the mean-texture bank (:339);
 reproducing the reference's random streams (the caller draws ``bg_index`` and the sigmas: ``draw_sigmas``); gradients; other
 numbers of levels.  JPEG encoding: ``encode_jpeg`` (jpeg.py).  Device tensors only."""
-import ctypes
 import functools
 
 import numpy as np
 import torch
 
 from . import _native as N
-from .composite import LDS_BYTES, MAX_TAPS, ROW_WORDS, _index, _pad4, _rows, draw_sigmas, gaussian_taps, resize_taps
-from .export import _ROUNDING, _layout
+from .frames import LDS_BYTES, MAX_TAPS, ROW_WORDS, ROWS, _check_inputs, _launch, _lower_common, _rows, band_bytes_lds, draw_sigmas, gaussian_taps, resize_taps
 
-ROWS = 8                # MM_PYRAMID_ROWS
 LEVELS = 3              # MM_PYRAMID_LEVELS
 MAX_KERNEL = 15         # MM_PYRAMID_MAX_KERNEL
 KINDS = ("mask", "background", "render")      # the plane kinds, in the order the reference draws their sigmas
-assert (MAX_TAPS, ROW_WORDS) == (8, 10)       # MM_PYRAMID_MAX_TAPS, MM_PYRAMID_ROW_WORDS: resize rows as composite packs them
+assert (ROWS, MAX_TAPS, ROW_WORDS) == (8, 8, 10)   # MM_PYRAMID_ROWS, MM_PYRAMID_MAX_TAPS, MM_PYRAMID_ROW_WORDS: the band and resize rows of frames.py
 
 # the call site; a sigma of None is drawn per frame, plane kind and level (draw_sigmas), as GaussianBlur(7) without sigma draws it per call
 PRESETS = {"tool/generate_market_test": dict(blur=(7, None), bg_pad=16)}
@@ -90,7 +87,7 @@ def lds_bytes(low):
         c_lo = min(max(a, 0), H + t + b - 1)
         rows = max(rows, hi - lo, min(max(e - 1, 0), H + t + b - 1) - c_lo + 1)
     cap = (rows * W + 3) // 4 * 4
-    return 4 * (2 * cap + 10 * ((ROWS * W + 3) // 4 * 4)) + (ROWS * W * 3 + 16 + 15) // 16 * 16
+    return 4 * (2 * cap + 10 * ((ROWS * W + 3) // 4 * 4)) + band_bytes_lds(W)
 
 
 @functools.lru_cache(maxsize=32)
@@ -109,28 +106,15 @@ def lower_pyramid(H, W, n_fg, n_bg, bg_index, fg_index=None, *, blur, bg_pad=16,
     fg_index, bg_index (B,) int32; taps (B,3,3,k) float32, [frame][plane kind][level]; bg_y, bg_x, each ``resize_taps`` of the padded axis;
     the sizes; lds_bytes; and ``params``, all of it packed as MMPyramidDesc.params wants it (int32 words, floats by their bits).
     Raises ValueError for what the kernel refuses: see ``pyramid_frames``."""
-    H, W, n_fg, n_bg = int(H), int(W), int(n_fg), int(n_bg)
-    if H < 1 or W < 1 or n_fg < 1 or n_bg < 1:
-        raise ValueError("H, W and the numbers of renders and backgrounds must be positive, got %r" % ((H, W, n_fg, n_bg),))
-    bgi = _index(bg_index, n_bg, "bg_index").reshape(-1)
-    fgi = np.arange(n_fg, dtype=np.int32) if fg_index is None else _index(fg_index, n_fg, "fg_index").reshape(-1)
-    if fgi.shape != bgi.shape or bgi.size < 1:
-        raise ValueError("fg_index and bg_index must name the same, positive number of frames, got %d and %d" % (fgi.size, bgi.size))
-    B = bgi.size
-    taps = _taps(blur, B)
-    l, r, t, b = pad = _pad4(bg_pad)
-    if min(pad) < 0:
-        raise ValueError("pads must not be negative, got bg_pad %r" % (pad,))
-    if max(l, r) >= W or max(t, b) >= H:
-        raise ValueError("a reflection pad must be smaller than the dimension it reflects in: bg_pad %r on %d x %d" % (pad, H, W))
+    low, fgi, bgi, taps = _lower_common(H, W, n_fg, n_bg, bg_index, fg_index, bg_pad, taps=lambda B: _taps(blur, B))
+    H, W, pad = low["H"], low["W"], low["bg_pad"]
     k = taps.shape[-1]
     if k // 2 >= min(H, W):
         raise ValueError("a blur radius must be smaller than the dimension it reflects in: kernel %d on %d x %d" % (k, H, W))
     geo = _geometry(H, W, pad, k, bool(antialias))
     if geo["lds_bytes"] > LDS_BYTES:
         raise ValueError("the call takes %d bytes of LDS, more than %d: a smaller kernel, pad or image" % (geo["lds_bytes"], LDS_BYTES))
-    low = dict(B=B, H=H, W=W, n_fg=n_fg, n_bg=n_bg, bg_pad=pad, antialias=bool(antialias), fg_index=torch.from_numpy(fgi.copy()),
-               bg_index=torch.from_numpy(bgi.copy()), taps=taps, bg_y=geo["bg_y"], bg_x=geo["bg_x"], lds_bytes=geo["lds_bytes"])
+    low.update(antialias=bool(antialias), taps=taps, bg_y=geo["bg_y"], bg_x=geo["bg_x"], lds_bytes=geo["lds_bytes"])
     low["params"] = torch.from_numpy(np.concatenate([fgi, bgi, taps.numpy().view(np.int32).reshape(-1), geo["rows"]]))
     return low
 
@@ -158,36 +142,8 @@ def pyramid_frames(renders, backgrounds, bg_index, *, fg_index=None, blur, bg_pa
 
         frames = pyramid_frames(pred, Xa, torch.randint(0, B, (B,)), **preset("tool/generate_market_test", B))
         for f in frames.cpu().numpy(): PIL.Image.fromarray(f).save(...)                 # ONE device-to-host copy"""
-    for x, what, ok in ((renders, "renders", lambda s: len(s) >= 3 and s[-3] == 4), (backgrounds, "backgrounds", lambda s: len(s) == 4 and s[1] in (3, 4))):
-        if not torch.is_tensor(x) or not x.dtype.is_floating_point:
-            raise ValueError("%s must be a float tensor, got %s" % (what, x.dtype if torch.is_tensor(x) else type(x)))
-        if not ok(tuple(x.shape)) or min(x.shape) < 1:
-            raise ValueError("%s must have shape %s, got %s" % (what, "(...,4,H,W)" if what == "renders" else "(n_bg,3|4,H,W)", tuple(x.shape)))
-    if tuple(backgrounds.shape[-2:]) != tuple(renders.shape[-2:]):
-        raise ValueError("renders and backgrounds must have the same H x W, got %s and %s" % (tuple(renders.shape), tuple(backgrounds.shape)))
-    if rounding not in _ROUNDING:
-        raise ValueError("rounding must be 'trunc' or 'nearest', got %r" % (rounding,))
-    lead, (H, W) = tuple(renders.shape[:-3]), renders.shape[-2:]
-    n_fg = int(np.prod(lead, dtype=np.int64))
-    shape = tuple(np.shape(bg_index if fg_index is None else fg_index))
-    if tuple(np.shape(bg_index)) != shape or (fg_index is None and shape != lead):
-        raise ValueError("bg_index must have the shape of %s, got %s" % ("fg_index, %s" % (shape,) if fg_index is not None else
-                                                                         "the renders' leading dimensions, %s" % (lead,), tuple(np.shape(bg_index))))
+    _, H, W, n_fg, shape = _check_inputs(renders, backgrounds, bg_index, fg_index, rounding)
     low = lower_pyramid(H, W, n_fg, backgrounds.shape[0], bg_index, fg_index, blur=blur, bg_pad=bg_pad, antialias=antialias)
-    N.require_device(renders, backgrounds)
-    fg = renders.detach()
-    fg, flag = _layout(fg if fg.dtype == torch.float32 else fg.float())
-    bg = backgrounds.detach()
-    bg = (bg if bg.dtype == torch.float32 else bg.float()).contiguous()
-    host = torch.empty(low["params"].shape, dtype=torch.int32, pin_memory=True)
-    host.copy_(low["params"])
-    dev = host.to(fg.device, non_blocking=True)
-    out = torch.empty(shape + ((3, H, W) if as_float else (H, W, 3)), dtype=torch.float32 if as_float else torch.uint8, device=fg.device)
     d = N.MMPyramidDesc()
-    d.B, d.H, d.W, d.n_fg, d.n_bg, d.bg_C = low["B"], H, W, n_fg, bg.shape[0], bg.shape[1]
-    d.fg_nhwc, d.k = flag, low["taps"].shape[-1]
-    d.bg_pad = (ctypes.c_int32 * 4)(*low["bg_pad"])
-    d.rounding, d.as_float = _ROUNDING[rounding], int(bool(as_float))
-    d.renders, d.backgrounds, d.params_host, d.params, d.out = N.ptr(fg), N.ptr(bg), ctypes.c_void_p(host.data_ptr()), N.ptr(dev), N.ptr(out)
-    N.check(N.lib().mm_pyramid_frames(ctypes.byref(d), N.current_stream(fg.device)), "mm_pyramid_frames")
-    return out
+    d.k = low["taps"].shape[-1]
+    return _launch(d, "mm_pyramid_frames", low, renders, backgrounds, shape, H, W, rounding, as_float)
