@@ -6,7 +6,10 @@ Shapes are test_jpeg_host's, the smallest that reach each path: 1 x 1 is one MCU
 edges; 24 x 40 and 40 x 24 have an even H with H mod 16 = 8, where chroma rows replicate the downsampled row; 33 x 9 and 50 x 70 have odd
 numbers of MCUs; 128 x 64 is the call site.  Each shape runs with every content of that file as one batch of six frames, whose streams have
 different lengths.  5 x 7 frames of 105 bytes start at every byte alignment; 50 frames of 16 x 16 span the per-frame kernels' grids; one
-256 x 256 noise frame at quality 100 has a stream larger than LDS, several workgroups of blocks per scan and some hundred chunks."""
+256 x 256 noise frame at quality 100 has a stream larger than LDS, several workgroups of blocks per scan and some hundred chunks.
+
+These inputs reach the entropy coder's discrete paths by chance.  tests/test_gpu_jpeg_edges.py runs the constructed cases of
+tests/test_jpeg_edges_host.py, one per path, and the sizes at which each scan starts another pass (257 frames, 258 blocks, 257 chunks that hold bytes)."""
 import functools
 import importlib
 import io

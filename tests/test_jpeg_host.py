@@ -7,7 +7,11 @@ tests/test_gpu_jpeg.py holds the device to it byte for byte.  Here the restateme
 that ``Image.fromarray(f).save(buf, 'JPEG', quality=q)`` writes, with no tolerance, because nothing on either side is rounded in floating
 point.  The restatement counts what it emits (ZRL codes, stuffed bytes, padding bits, dummy blocks), and the tests assert on those
 counters that the cases reach every path.  Only the tests that compare with Pillow need it: the restatement, its counters, the tables,
-the argument and ABI tests run without it, and so does tests/test_gpu_jpeg.py, which imports the restatement from here."""
+the argument and ABI tests run without it, and so does tests/test_gpu_jpeg.py, which imports the restatement from here.
+
+The inputs here (noise, ramps, flat frames, renders) reach the entropy coder's discrete paths by chance.  tests/test_jpeg_edges_host.py builds an
+input for each path and asserts it from the per-stream records that ``stream_restated`` keeps (``stream_counters``, ``writer_shapes``,
+``ff_runs``) and the ties that ``blocks_restated`` counts; tests/test_gpu_jpeg_edges.py runs those inputs on the device."""
 import importlib
 import io
 
@@ -71,8 +75,9 @@ def planes_restated(f):
     return out
 
 
-def blocks_restated(f, divisors):
-    """(mcus,6,64) quantised coefficients in zigzag order, MCU order, and (mcus,6) bool: which blocks are dummies"""
+def blocks_restated(f, divisors, counters=None):
+    """(mcus,6,64) quantised coefficients in zigzag order, MCU order, and (mcus,6) bool: which blocks are dummies.
+    counters, if given: ties_pos and ties_neg, [luma, chroma], the coefficients of real blocks that lie exactly half way (they round away from zero)"""
     H, W = f.shape[:2]
     my, mx = (H + 15) // 16, (W + 15) // 16
     y, cb, cr = planes_restated(f)
@@ -84,6 +89,12 @@ def blocks_restated(f, divisors):
     m = np.arange(my * mx)
     by, bx = 2 * (m // mx)[:, None] + np.array([0, 0, 1, 1]), 2 * (m % mx)[:, None] + np.array([0, 1, 0, 1])
     dummy = np.concatenate([(by >= (H + 7) // 8) | (bx >= (W + 7) // 8), np.zeros((my * mx, 2), dtype=bool)], axis=1)
+    if counters is not None:
+        tie = ((np.abs(coef) + (div >> 1)) % div == 0) & ~dummy[:, :, None]
+        for key, sign in (("ties_pos", coef > 0), ("ties_neg", coef < 0)):
+            counters.setdefault(key, [0, 0])
+            counters[key][0] += int((tie & sign)[:, :4].sum())
+            counters[key][1] += int((tie & sign)[:, 4:].sum())
     for j in range(1, 4):                                        # a dummy block: no AC, the DC of the block before it in MCU order
         q[dummy[:, j], j, :] = 0
         q[dummy[:, j], j, 0] = q[dummy[:, j], j - 1, 0]
@@ -91,8 +102,11 @@ def blocks_restated(f, divisors):
 
 
 def stream_restated(zz, counters):
-    """the entropy-coded bytes of (mcus,6,64) zigzag coefficients: interleaved Y00 Y01 Y10 Y11 Cb Cr, one DC predictor per component"""
+    """the entropy-coded bytes of (mcus,6,64) zigzag coefficients: interleaved Y00 Y01 Y10 Y11 Cb Cr, one DC predictor per component.
+    What it emitted goes into counters: the sums zrl and stuffed, pad_bits of this stream, and one dict per stream appended to
+    counters["streams"] (see ``stream_counters``).  The counters observe; nothing below reads them."""
     huff = J.huffman_codes()
+    seen = stream_counters()
     acc, nacc, raw = 0, 0, bytearray()                           # the bits not yet in raw: fewer than 8 between two symbols
 
     def put(table, symbol, extra=0, nextra=0):
@@ -115,27 +129,87 @@ def stream_restated(zz, counters):
         for j, blk in enumerate(mcu):
             comp = max(j - 3, 0)
             dc, ac = (0, 1) if comp == 0 else (2, 3)
-            n, bits = magnitude(int(blk[0]) - pred[comp])
+            seen["block_at"].append(8 * len(raw) + nacc)
+            diff = int(blk[0]) - pred[comp]
+            n, bits = magnitude(diff)
+            seen["dc_diffs"][min(comp, 1)].append(diff)
+            seen["dc_cats"][min(comp, 1)][n] += 1
+            if n == 11:
+                seen["dc11_pos" if diff > 0 else "dc11_neg"][min(comp, 1)] += 1
             pred[comp] = int(blk[0])
             put(dc, n, bits, n)
             last = 0
             for k in np.nonzero(blk[1:])[0] + 1:
                 run = int(k) - last - 1
+                zrls = 0
                 while run > 15:
                     put(ac, 0xF0)
                     counters["zrl"] += 1
+                    zrls += 1
                     run -= 16
                 n, bits = magnitude(int(blk[k]))
+                seen["zrl_max"], seen["ac_cat_max"] = max(seen["zrl_max"], zrls), max(seen["ac_cat_max"], n)
                 put(ac, run << 4 | n, bits, n)
                 last = int(k)
             if last < 63:
                 put(ac, 0)
+            seen["no_eob"] += last == 63
+            seen["eob_only"] += last == 0
+            seen["block_bits"].append(8 * len(raw) + nacc - seen["block_at"][-1])
     pad = -nacc % 8                                              # the last byte is filled with 1-bits
     counters["pad_bits"] = pad
     if pad:
         raw.append((acc << pad) | ((1 << pad) - 1))
     counters["stuffed"] += raw.count(b"\xff")
+    seen["pad_bits"], seen["raw_bytes"] = pad, len(raw)
+    seen["ff_at"] = [i for i, b in enumerate(raw) if b == 0xFF]
+    seen["last_ff"] = raw[-1] == 0xFF
+    seen["last_ff_by_padding"] = bool(pad) and raw[-1] == 0xFF     # the stuffed 0x00 then comes just before EOI
+    counters.setdefault("streams", []).append(seen)
     return bytes(raw).replace(b"\xff", b"\xff\x00")
+
+
+def stream_counters():
+    """what ``stream_restated`` records of one stream; [luma, chroma] where a figure is kept per component class"""
+    return dict(dc_cats=[[0] * 12, [0] * 12],                    # how many DC differences of each category 0..11
+                dc11_pos=[0, 0], dc11_neg=[0, 0],                # the signs of the differences of category 11
+                dc_diffs=[[], []],                               # every DC difference, in coding order
+                ac_cat_max=0,                                    # the largest AC category
+                zrl_max=0,                                       # the most ZRLs before one coefficient
+                no_eob=0, eob_only=0,                            # blocks whose coefficient 63 is non-zero; blocks with no AC at all
+                block_at=[], block_bits=[],                      # every block's bit offset in the stream and its bit length
+                pad_bits=0, raw_bytes=0,                         # the stream before stuffing, padding included
+                ff_at=[],                                        # the index of every 0xFF in it
+                last_ff=False, last_ff_by_padding=False)
+
+
+def writer_shapes(seen):
+    """how many blocks of one stream take each way through the device's JpegWriter, which ORs a block's bits into big-endian 32-bit
+    words: the first word it flushes and the word ``finish`` completes are shared with the neighbours (atomic OR), the words between
+    are stored plainly.  a: begins and ends inside one word (no flush); b: begins inside a word and ends exactly at its end (the flush
+    is the OR, ``finish`` has nothing left); c: begins at bit 0 of a word; d: touches three words or more (plain stores between the
+    ORs); e: ends exactly on a word boundary after a plain store.  A block can have several."""
+    out = dict(a=0, b=0, c=0, d=0, e=0)
+    for at, n in zip(seen["block_at"], seen["block_bits"]):
+        s = at % 32
+        out["a"] += s + n < 32
+        out["b"] += s > 0 and s + n == 32
+        out["c"] += s == 0
+        out["d"] += (at + n - 1) // 32 - at // 32 >= 2
+        out["e"] += s + n >= 64 and (s + n) % 32 == 0
+    return out
+
+
+def ff_runs(seen):
+    """the lengths of the runs of consecutive 0xFF in a stream before stuffing, in order"""
+    runs, prev = [], None
+    for i in seen["ff_at"]:
+        if prev is not None and i == prev + 1:
+            runs[-1] += 1
+        else:
+            runs.append(1)
+        prev = i
+    return runs
 
 
 def jpeg_restated(frames, quality=100, counters=None):
@@ -149,7 +223,7 @@ def jpeg_restated(frames, quality=100, counters=None):
         counters.setdefault(key, 0)
     files = []
     for one in f.reshape(-1, H, W, 3):
-        zz, dummy = blocks_restated(one, low["divisors"])
+        zz, dummy = blocks_restated(one, low["divisors"], counters)
         counters["dummy_right"] += int(dummy[:, 1].sum())
         counters["dummy_below"] += int(dummy[:, 2].sum())
         files.append(low["header"] + stream_restated(zz, counters) + b"\xff\xd9")
@@ -220,7 +294,8 @@ def test_cases_reach_every_path():
                 jpeg_restated(content(kind, H, W), q, c)
                 aligned += c["pad_bits"] == 0
                 for k, v in c.items():
-                    total[k] = total.get(k, 0) + v
+                    if isinstance(v, int):                       # (the sums; the per-stream records are tests/test_jpeg_edges_host.py's)
+                        total[k] = total.get(k, 0) + v
     assert total["zrl"] > 0                                      # runs of 16 zeros
     assert total["stuffed"] > 0                                  # a 0xFF in the stream
     assert aligned > 0                                           # a stream that ends on a byte boundary: no padding
