@@ -65,9 +65,17 @@ size_t jpeg_files_at(const MMJpegDesc*);
 int launch_jpeg(const MMJpegDesc*, hipStream_t);
 }  // namespace mm
 
+static bool sizes_positive(const MMRenderDesc* d) { return d->B > 0 && d->H > 0 && d->W > 0 && d->V > 0 && d->F > 0 && d->Ht > 0 && d->Wt > 0; }
+
+// the render workspace of `d` as the kernels see it; placed = false: its layout alone, at address 0 with the minimum's record pool
+static mm::Workspace carve(const MMRenderDesc* d, bool placed = true) {
+    const bool geo = d->geometry_only != 0, step = d->step_grads != nullptr;
+    return mm::carve_workspace(placed ? d->workspace : nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, placed ? d->workspace_bytes : 0, geo, step);
+}
+
 static int check_render(const MMRenderDesc* d, bool backward) {
     if (!d) return MM_ERR_NULL_POINTER;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->V <= 0 || d->F <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
+    if (!sizes_positive(d)) return MM_ERR_BAD_SHAPE;
     if (d->knum <= 0) return MM_ERR_UNSUPPORTED;
     if (d->H > 65535 || d->W > 65535) return MM_ERR_UNSUPPORTED;                 // pixel boxes are packed in 16 + 16 bits
     if (d->geometry_only) {                                                       // vertex stage only: what it reads and writes
@@ -121,14 +129,14 @@ static int check_resize_rows(const int32_t*& row, int32_t n_out, int32_t n_in) {
 extern "C" {
 
 size_t mm_query_workspace(const MMRenderDesc* d) {
-    if (!d || d->B <= 0 || d->V <= 0 || d->F <= 0 || d->H <= 0 || d->W <= 0 || d->Ht <= 0 || d->Wt <= 0) return 0;
-    return mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, 0, d->geometry_only != 0, d->step_grads != nullptr).bytes;
+    if (!d || !sizes_positive(d)) return 0;
+    return carve(d, false).bytes;
 }
 
 int mm_render_forward(const MMRenderDesc* d, mm_stream_t stream) {
     int st = check_render(d, false);
     if (st != MM_OK) return st;
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
+    const mm::Workspace w = carve(d);
     hipStream_t s = (hipStream_t)stream;
     mm::clear_stale_error();
     st = mm::launch_vertex_fwd(d, w, s);
@@ -140,7 +148,7 @@ int mm_render_fused_loss(const MMRenderDesc* d, mm_stream_t stream) {
     int st = check_render(d, false);
     if (st != MM_OK) return st;
     if (!d->fused_gt || !d->fused_loss) return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
+    const mm::Workspace w = carve(d);
     mm::clear_stale_error();
     return mm::launch_fused_loss(d, w, (hipStream_t)stream);
 }
@@ -156,8 +164,8 @@ int mm_debug_workspace_layout(const MMRenderDesc* d, size_t* out5) {
 }
 
 int mm_render_step_mode(const MMRenderDesc* d) {
-    if (!d || d->B <= 0 || d->V <= 0 || d->F <= 0 || d->H <= 0 || d->W <= 0 || d->Ht <= 0 || d->Wt <= 0) return 0;
-    const mm::Workspace w = mm::carve_workspace(nullptr, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, 0, d->geometry_only != 0, d->step_grads != nullptr);
+    if (!d || !sizes_positive(d)) return 0;
+    const mm::Workspace w = carve(d, false);
     return mm::render_step_mode(d, w) ? 1 : 0;
 }
 
@@ -171,10 +179,10 @@ int mm_debug_step_layout(const MMRenderDesc* d, size_t* out4) {
 
 int mm_render_status(const MMRenderDesc* d, mm_stream_t stream, int32_t* dropped_host) {
     if (!d) return MM_ERR_NULL_POINTER;                            // (only the shape and the workspace are looked at)
-    if (d->B <= 0 || d->V <= 0 || d->F <= 0 || d->H <= 0 || d->W <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
+    if (!sizes_positive(d)) return MM_ERR_BAD_SHAPE;
     if (!d->workspace) return MM_ERR_NULL_POINTER;
     if (d->workspace_bytes < mm_query_workspace(d) || ((uintptr_t)d->workspace & 255)) return MM_ERR_BAD_SHAPE;   // (MM_ERR_WORKSPACE is this call's "records were dropped")
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
+    const mm::Workspace w = carve(d);
     std::vector<int32_t> h((size_t)d->B);
     if (hipMemcpyAsync(h.data(), w.tstatus, (size_t)d->B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) return MM_ERR_LAUNCH;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return MM_ERR_LAUNCH;
@@ -187,7 +195,7 @@ int mm_render_backward(const MMRenderDesc* d, const MMRenderGrads* g, mm_stream_
     int st = check_render(d, true);
     if (st != MM_OK) return st;
     if (!g || !g->grad_vertices || !g->grad_azimuths || !g->grad_elevations || !g->grad_distances || !g->grad_biases) return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(d->workspace, d->B, d->V, d->F, d->H, d->W, d->Ht, d->Wt, d->workspace_bytes, d->geometry_only != 0, d->step_grads != nullptr);
+    const mm::Workspace w = carve(d);
     hipStream_t s = (hipStream_t)stream;
     if (d->geometry_only) {                                       // nothing was rasterised: the gradient arrives through face_normals alone
         if (!g->grad_face_normals) return MM_ERR_NULL_POINTER;
@@ -202,9 +210,11 @@ int mm_render_backward(const MMRenderDesc* d, const MMRenderGrads* g, mm_stream_
     return mm::launch_vertex_bwd(d, g, w, s);
 }
 
-// ---- multi-view render (include/mm_render.h: MMRenderViewsDesc) ------------------------------------------------------------------------
-// staging areas of the per-image gradients of the four per-sample inputs, (B*N, row) floats each, at the HEAD of a multi-view workspace: the
-// render workspace of the B*N images follows them with exactly the bytes that are left, as mm_render_forward would be given them
+// ---- multi-view and indexed renders (include/mm_render.h: MMRenderViewsDesc, MMRenderIndexedDesc) ------------------------------------------
+// Both render the images of a sub-descriptor `r`: the caller's MMRenderDesc with a HEAD stripped off its workspace (the images' render workspace
+// follows the head with exactly the bytes that are left, as mm_render_forward would be given them).  Both end their backward with a row sum
+// (mm_row_sum.h) of the per-image gradients of vertices, textures, lights and bg, which the kernels write into staging areas in the head,
+// (images, row) floats each:
 struct ViewsStaging { size_t off[4]; int len[4]; size_t bytes; };
 static ViewsStaging views_staging(const MMRenderDesc* d) {
     ViewsStaging st;
@@ -214,23 +224,45 @@ static ViewsStaging views_staging(const MMRenderDesc* d) {
     st.bytes = o;
     return st;
 }
+static bool row_lengths_fit(const MMRenderDesc* d) { return (size_t)3 * d->Ht * d->Wt <= 0x7fffffff && (size_t)3 * d->H * d->W <= 0x7fffffff; }
 
-// everything checked before any launch; *r = the descriptor of the B*N images as the render kernels take it (the workspace without the staging)
+// What both calls' checks end with, before any launch: the modes not built over views or indices, `own` (the caller's verdict on its own
+// fields), then *r = the descriptor of the images as the render kernels take it (the workspace without its `head` bytes).
+static int check_sub_render(const MMRenderDesc* d, bool backward, int own, size_t head, MMRenderDesc* r) {
+    if (d->fused_gt || d->fused_totals || d->geometry_only) return MM_ERR_UNSUPPORTED;    // fused / deferred losses and geometry-only: not built
+    if (own != MM_OK) return own;
+    *r = *d; r->step_grads = nullptr;                            // (step mode is a single-view, fused mode: the field is ignored here)
+    r->workspace = d->workspace ? (char*)d->workspace + head : nullptr;      // (the head is a multiple of 256: the alignment is the caller's)
+    r->workspace_bytes = d->workspace_bytes > head ? d->workspace_bytes - head : 0;
+    return check_render(r, backward);
+}
+
+// a backward whose per-image gradients are summed: every pointer of the nine (bg under no_mask) is needed
+static bool grads_complete(const MMRenderGrads* g, bool no_mask) {
+    return g && g->grad_vertices && g->grad_azimuths && g->grad_elevations && g->grad_distances && g->grad_biases && g->grad_rgba && g->grad_textures && g->grad_lights && (!no_mask || g->grad_bg);
+}
+
+// The per-image gradients `gi` the backward kernels write -- into the staging areas `st` lays out at `base`, or straight into the caller's
+// where base is NULL (one view: nothing to sum) -- and the four outputs `out` a row sum reduces `staging` (rows of st.len floats) to.
+struct StagedGrads {
+    MMRenderGrads gi;
+    ViewsStaging st;
+    float *staging[4] = {}, *out[4];
+    StagedGrads(const MMRenderGrads* g, const ViewsStaging& st, char* base, bool no_mask) : gi(*g), st(st), out{g->grad_vertices, g->grad_textures, g->grad_lights, no_mask ? g->grad_bg : nullptr} {
+        if (!base) return;
+        for (int t = 0; t < 4; ++t) staging[t] = (float*)(base + st.off[t]);
+        gi.grad_vertices = staging[0]; gi.grad_textures = staging[1]; gi.grad_lights = staging[2]; gi.grad_bg = no_mask ? staging[3] : nullptr;
+    }
+};
+
+// the head of a multi-view workspace: the staging areas (B*N rows each); one view has none
 static int check_render_views(const MMRenderViewsDesc* v, bool backward, MMRenderDesc* r) {
     if (!v) return MM_ERR_NULL_POINTER;
     const MMRenderDesc* d = &v->render;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->V <= 0 || d->F <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
-    if (v->views < 1 || d->B % v->views != 0) return MM_ERR_BAD_SHAPE;
-    if (d->fused_gt || d->fused_totals || d->geometry_only) return MM_ERR_UNSUPPORTED;    // fused / deferred losses and geometry-only over views: not built
-    if ((size_t)3 * d->Ht * d->Wt > 0x7fffffff || (size_t)3 * d->H * d->W > 0x7fffffff || d->B / v->views > 65535) return MM_ERR_UNSUPPORTED;
-    *r = *d;
-    r->step_grads = nullptr;                                     // (step mode is a single-view, fused mode: the field is ignored here)
-    if (v->views > 1) {
-        const size_t st = views_staging(d).bytes;
-        r->workspace = d->workspace ? (char*)d->workspace + st : nullptr;      // (st is a multiple of 256: the alignment is the caller's)
-        r->workspace_bytes = d->workspace_bytes > st ? d->workspace_bytes - st : 0;
-    }
-    return check_render(r, backward);
+    if (!sizes_positive(d) || v->views < 1 || d->B % v->views != 0) return MM_ERR_BAD_SHAPE;
+    // (the verdict is computed here and handed in: check_sub_render returns it AFTER its modes test, where this refusal has always stood)
+    const int own = !row_lengths_fit(d) || d->B / v->views > 65535 ? MM_ERR_UNSUPPORTED : MM_OK;
+    return check_sub_render(d, backward, own, v->views > 1 ? views_staging(d).bytes : 0, r);
 }
 
 static int check_recon(const MMReconDesc* d, bool backward) {
@@ -247,15 +279,14 @@ static int check_recon(const MMReconDesc* d, bool backward) {
 size_t mm_render_views_query_workspace(const MMRenderViewsDesc* v) {
     if (!v || v->views < 1 || v->render.B <= 0 || v->render.B % v->views != 0) return 0;
     const size_t base = mm_query_workspace(&v->render);
-    if (base == 0 || v->views == 1) return base;
-    return base + views_staging(&v->render).bytes;
+    return base == 0 || v->views == 1 ? base : base + views_staging(&v->render).bytes;
 }
 
 int mm_render_views_forward(const MMRenderViewsDesc* v, mm_stream_t stream) {
     MMRenderDesc r;
     int st = check_render_views(v, false, &r);
     if (st != MM_OK) return st;
-    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    const mm::Workspace w = carve(&r);
     hipStream_t s = (hipStream_t)stream;
     mm::clear_stale_error();
     st = mm::launch_vertex_fwd(&r, w, s, v->views);
@@ -267,35 +298,22 @@ int mm_render_views_backward(const MMRenderViewsDesc* v, const MMRenderGrads* g,
     MMRenderDesc r;
     int st = check_render_views(v, true, &r);
     if (st != MM_OK) return st;
-    if (!g || !g->grad_vertices || !g->grad_azimuths || !g->grad_elevations || !g->grad_distances || !g->grad_biases || !g->grad_rgba ||
-        !g->grad_textures || !g->grad_lights || (r.no_mask && !g->grad_bg))
-        return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    if (!grads_complete(g, r.no_mask)) return MM_ERR_NULL_POINTER;
+    const mm::Workspace w = carve(&r);
     hipStream_t s = (hipStream_t)stream;
-    MMRenderGrads gi = *g;                                        // the per-image gradients the kernels write
-    const ViewsStaging stg = views_staging(&r);
-    float* staging[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (v->views > 1) {
-        char* base = (char*)v->render.workspace;
-        for (int t = 0; t < 4; ++t) staging[t] = (float*)(base + stg.off[t]);
-        gi.grad_vertices = staging[0]; gi.grad_textures = staging[1]; gi.grad_lights = staging[2];
-        gi.grad_bg = r.no_mask ? staging[3] : nullptr;
-    }
+    const StagedGrads sg(g, views_staging(&r), v->views > 1 ? (char*)v->render.workspace : nullptr, r.no_mask != 0);
     mm::clear_stale_error();
-    st = mm::launch_raster_bwd(&r, &gi, w, s, v->views);
+    st = mm::launch_raster_bwd(&r, &sg.gi, w, s, v->views);
     if (st != MM_OK) return st;
-    st = mm::launch_vertex_bwd(&r, &gi, w, s, v->views);
+    st = mm::launch_vertex_bwd(&r, &sg.gi, w, s, v->views);
     if (st != MM_OK || v->views == 1) return st;
-    float* out[4] = {g->grad_vertices, g->grad_textures, g->grad_lights, r.no_mask ? g->grad_bg : nullptr};
-    return mm::launch_view_sum(r.B / v->views, v->views, staging, out, stg.len, s);
+    return mm::launch_view_sum(r.B / v->views, v->views, sg.staging, sg.out, sg.st.len, s);
 }
 
-// ---- indexed render (include/mm_render.h: MMRenderIndexedDesc) --------------------------------------------------------------------------
-// The HEAD of an indexed workspace: the plan (mm_indexed.hip) -- the table (5, M), then per tensor offsets (rows + 1), cursors (rows) and
-// images (M) -- and, for a call with a backward, the staging areas of the per-image gradients as views_staging lays them out (M rows each).
-// The render workspace of the M images follows with exactly the bytes that are left.  rows[]: the row counts the kernels go by (bg without
-// no_mask: M rows, the identity, never summed).
-struct IndexedHead { size_t table, offsets[4], cursor[4], images[4], staging[4], bytes; int rows[4], len[4]; };
+// The head of an indexed workspace: the plan (mm_indexed.hip) -- the table (5, M), then per tensor offsets (rows + 1), cursors (rows) and
+// images (M) -- and, for a call with a backward, the staging areas `st` (M rows each) at `staging`.  rows[]: the row counts the kernels go by
+// (bg without no_mask: M rows, the identity, never summed).
+struct IndexedHead { size_t table, offsets[4], cursor[4], images[4], staging, bytes; int rows[4]; ViewsStaging st; };
 static IndexedHead indexed_head(const MMRenderIndexedDesc* v) {
     IndexedHead h;
     const MMRenderDesc* d = &v->render;
@@ -309,10 +327,8 @@ static IndexedHead indexed_head(const MMRenderIndexedDesc* v) {
         h.cursor[t] = o; o += mm::align256(R * sizeof(int));
         h.images[t] = o; o += mm::align256(M * sizeof(int));
     }
-    const ViewsStaging st = views_staging(d);
-    for (int t = 0; t < 4; ++t) { h.staging[t] = o + st.off[t]; h.len[t] = st.len[t]; }
-    if (v->backward) o += st.bytes;
-    h.bytes = o;
+    h.st = views_staging(d); h.staging = o;
+    h.bytes = o + (v->backward ? h.st.bytes : 0);
     return h;
 }
 static mm::IndexPlan indexed_plan(const IndexedHead& h, void* workspace) {
@@ -326,47 +342,39 @@ static mm::IndexPlan indexed_plan(const IndexedHead& h, void* workspace) {
 static int indexed_shape(const MMRenderIndexedDesc* v) {
     if (!v) return MM_ERR_NULL_POINTER;
     const MMRenderDesc* d = &v->render;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->V <= 0 || d->F <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
+    if (!sizes_positive(d)) return MM_ERR_BAD_SHAPE;
     if (d->B > 65535) return MM_ERR_UNSUPPORTED;                  // (rows and images are 16-bit keys of the plan; rows are the sum's grid y)
     for (int t = 0; t < 4; ++t) {
         if (t == 3 && !d->no_mask) continue;                      // (no bg in this call: its row count is not looked at)
         if (v->rows[t] < 1) return MM_ERR_BAD_SHAPE;
         if (v->rows[t] > 65535) return MM_ERR_UNSUPPORTED;
     }
-    if ((size_t)3 * d->Ht * d->Wt > 0x7fffffff || (size_t)3 * d->H * d->W > 0x7fffffff) return MM_ERR_UNSUPPORTED;
-    return MM_OK;
+    return row_lengths_fit(d) ? MM_OK : MM_ERR_UNSUPPORTED;
 }
 
-// everything checked before any launch; *r = the descriptor of the M images as the render kernels take it (the workspace without the head)
 static int check_render_indexed(const MMRenderIndexedDesc* v, bool backward, MMRenderDesc* r, IndexedHead* h) {
-    int st = indexed_shape(v);
+    const int st = indexed_shape(v);
     if (st != MM_OK) return st;
     const MMRenderDesc* d = &v->render;
-    if (d->fused_gt || d->fused_totals || d->geometry_only) return MM_ERR_UNSUPPORTED;    // fused / deferred losses and geometry-only over indices: not built
+    // computed early, returned by check_sub_render after its modes test (the refusal order); BAD_SHAPE is assigned last because it outranks WORKSPACE
+    int own = backward && !v->backward ? MM_ERR_WORKSPACE : MM_OK;      // a forward-only call left no staging
     for (int t = 0; t < 4; ++t)
-        if (!(t == 3 && !d->no_mask) && !v->index[t] && v->rows[t] != d->B) return MM_ERR_BAD_SHAPE;   // the identity needs a row per image
-    if (backward && !v->backward) return MM_ERR_WORKSPACE;       // a forward-only call left no staging
+        if (!(t == 3 && !d->no_mask) && !v->index[t] && v->rows[t] != d->B) own = MM_ERR_BAD_SHAPE;   // the identity needs a row per image
     *h = indexed_head(v);
-    *r = *d;
-    r->step_grads = nullptr;                                     // (step mode is a fused mode: the field is ignored here)
-    r->workspace = d->workspace ? (char*)d->workspace + h->bytes : nullptr;      // (the head is a multiple of 256: the alignment is the caller's)
-    r->workspace_bytes = d->workspace_bytes > h->bytes ? d->workspace_bytes - h->bytes : 0;
-    return check_render(r, backward);
+    return check_sub_render(d, backward, own, h->bytes, r);
 }
 
 size_t mm_render_indexed_query_workspace(const MMRenderIndexedDesc* v) {
     if (indexed_shape(v) != MM_OK) return 0;
     const size_t base = mm_query_workspace(&v->render);
-    if (base == 0) return 0;
-    return base + indexed_head(v).bytes;
+    return base ? base + indexed_head(v).bytes : 0;
 }
 
 int mm_render_indexed_forward(const MMRenderIndexedDesc* v, mm_stream_t stream) {
-    MMRenderDesc r;
-    IndexedHead h;
+    MMRenderDesc r; IndexedHead h;
     int st = check_render_indexed(v, false, &r, &h);
     if (st != MM_OK) return st;
-    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    const mm::Workspace w = carve(&r);
     const mm::IndexPlan p = indexed_plan(h, v->render.workspace);
     hipStream_t s = (hipStream_t)stream;
     const int32_t* index[4] = {v->index[0], v->index[1], v->index[2], r.no_mask ? v->index[3] : nullptr};
@@ -379,28 +387,20 @@ int mm_render_indexed_forward(const MMRenderIndexedDesc* v, mm_stream_t stream) 
 }
 
 int mm_render_indexed_backward(const MMRenderIndexedDesc* v, const MMRenderGrads* g, mm_stream_t stream) {
-    MMRenderDesc r;
-    IndexedHead h;
+    MMRenderDesc r; IndexedHead h;
     int st = check_render_indexed(v, true, &r, &h);
     if (st != MM_OK) return st;
-    if (!g || !g->grad_vertices || !g->grad_azimuths || !g->grad_elevations || !g->grad_distances || !g->grad_biases || !g->grad_rgba ||
-        !g->grad_textures || !g->grad_lights || (r.no_mask && !g->grad_bg))
-        return MM_ERR_NULL_POINTER;
-    const mm::Workspace w = mm::carve_workspace(r.workspace, r.B, r.V, r.F, r.H, r.W, r.Ht, r.Wt, r.workspace_bytes, false);
+    if (!grads_complete(g, r.no_mask)) return MM_ERR_NULL_POINTER;
+    const mm::Workspace w = carve(&r);
     const mm::IndexPlan p = indexed_plan(h, v->render.workspace);
     hipStream_t s = (hipStream_t)stream;
-    MMRenderGrads gi = *g;                                        // the per-image gradients the kernels write
-    float* staging[4];
-    for (int t = 0; t < 4; ++t) staging[t] = (float*)((char*)v->render.workspace + h.staging[t]);
-    gi.grad_vertices = staging[0]; gi.grad_textures = staging[1]; gi.grad_lights = staging[2];
-    gi.grad_bg = r.no_mask ? staging[3] : nullptr;
+    const StagedGrads sg(g, h.st, (char*)v->render.workspace + h.staging, r.no_mask != 0);
     mm::clear_stale_error();
-    st = mm::launch_raster_bwd(&r, &gi, w, s, 1, p.table);
+    st = mm::launch_raster_bwd(&r, &sg.gi, w, s, 1, p.table);
     if (st != MM_OK) return st;
-    st = mm::launch_vertex_bwd_indexed(&r, &gi, w, s, p.table);
+    st = mm::launch_vertex_bwd_indexed(&r, &sg.gi, w, s, p.table);
     if (st != MM_OK) return st;
-    float* out[4] = {g->grad_vertices, g->grad_textures, g->grad_lights, r.no_mask ? g->grad_bg : nullptr};
-    return mm::launch_index_sum(r.B, h.rows, staging, out, h.len, p, g, s);
+    return mm::launch_index_sum(r.B, h.rows, sg.staging, sg.out, sg.st.len, p, g, s);
 }
 
 size_t mm_recon_query_workspace(const MMReconDesc* d) {

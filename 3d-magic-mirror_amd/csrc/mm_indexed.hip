@@ -14,14 +14,10 @@
 //                       barriers, index loads and the 256-key rank scan per chunk, not profiled further.  No host synchronisation,
 //                       nothing read back.
 //   index_sum_kernel    last launch of the backward.  The backward kernels write PER-IMAGE gradients; those of the four indexed inputs land
-//                       in staging areas (M, row) of the workspace, and this launch reduces all four to (rows, row):
-//                           out[r][j] = ((g[i0][j] + g[i1][j]) + g[i2][j]) + ...        over row r's list, in the list's order
-//                       plain fp32 adds (no fma -- the file is compiled without contraction --, no float atomics: bitwise reproducible, the
-//                       bits of the adds written out in torch); an empty list writes zeros.  The unit scheme of mm_views.hip: a workgroup
-//                       takes 4 x 256 consecutive 16-byte units of one row (4-byte units where the row length or a pointer does not allow
-//                       16: vertices of most templates, lights), two staged rows loaded per trip.  The grid's last workgroups write NaN
-//                       into the four camera gradients of bad images.
-#include "mm_device.h"
+//                       in staging areas (M, row) of the workspace, and this launch reduces all four to (rows, row) with the row sum of
+//                       mm_row_sum.h: a row's staged rows are those of its list's images, in the list's order; an empty list writes
+//                       zeros.  The grid's last workgroups write NaN into the four camera gradients of bad images.
+#include "mm_row_sum.h"
 
 namespace mm {
 
@@ -180,13 +176,8 @@ int launch_index_plan(int M, const int32_t* const* index, const int* rows, const
 }
 
 // ---- the index sum -------------------------------------------------------------------------------------------------------------------
-#define MM_ISUM_UNITS 4            // units per lane (256 apart: coalesced per instruction)
-
 struct IndexSumArgs {
-    const float* src[4];           // (M, len) staging
-    float* dst[4];                 // (rows, len)
-    int len[4];                    // floats per row; 0: tensor not present
-    int vec[4];                    // 1: len % 4 == 0 and both pointers 16-byte aligned -> float4 units
+    RowSumArgs t;                  // src (M, len), dst (rows, len)
     int cpr[4];                    // workgroups (chunks of 1024 units) per row
     int xb[5];                     // tensor t owns blocks [xb[t], xb[t+1]) of the grid, rows[t] x cpr[t] of them; the blocks from xb[4] on poison the bad images' camera gradients
     const int* offsets[4];
@@ -195,55 +186,6 @@ struct IndexSumArgs {
     int M;
     float *grad_azim, *grad_elev, *grad_dist, *grad_bias;
 };
-
-template <typename T>
-__device__ inline T is_add(const T& a, const T& b);
-template <>
-__device__ inline float is_add<float>(const float& a, const float& b) { return a + b; }
-template <>
-__device__ inline float4 is_add<float4>(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-template <typename T>
-__device__ inline T is_zero();
-template <>
-__device__ inline float is_zero<float>() { return 0.f; }
-template <>
-__device__ inline float4 is_zero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-// one workgroup's chunk of one row: units [chunk * 1024, chunk * 1024 + 1024) of `n` units; image m's staged row starts at src + m * n
-template <typename T>
-__device__ inline void index_sum_chunk(const T* __restrict__ src, T* __restrict__ dst, int n, const int* __restrict__ list, int cnt, int chunk) {
-    int u[MM_ISUM_UNITS];
-    bool ok[MM_ISUM_UNITS];
-    T acc[MM_ISUM_UNITS];
-    const int first = cnt > 0 ? list[0] : 0;                     // (workgroup-uniform, like everything read from the list)
-#pragma unroll
-    for (int k = 0; k < MM_ISUM_UNITS; ++k) {
-        u[k] = chunk * (256 * MM_ISUM_UNITS) + k * 256 + (int)threadIdx.x;
-        ok[k] = u[k] < n;
-        u[k] = ok[k] ? u[k] : 0;                                 // (a valid address in every lane; nothing is stored for it)
-        acc[k] = cnt > 0 ? src[(size_t)first * n + u[k]] : is_zero<T>();      // the list's first image starts the sum: g0, not 0 + g0; no image: zeros
-    }
-    int m0 = cnt > 1 ? list[1] : 0, m1 = cnt > 2 ? list[2] : m0;
-    for (int v = 1; v < cnt; v += 2) {
-        const bool two = v + 1 < cnt;
-        T r0[MM_ISUM_UNITS], r1[MM_ISUM_UNITS];
-#pragma unroll
-        for (int k = 0; k < MM_ISUM_UNITS; ++k) {
-            r0[k] = src[(size_t)m0 * n + u[k]];
-            r1[k] = src[(size_t)m1 * n + u[k]];
-        }
-        m0 = v + 2 < cnt ? list[v + 2] : 0;                      // (the next trip's images: asked for before this trip's rows are waited for)
-        m1 = v + 3 < cnt ? list[v + 3] : m0;
-#pragma unroll
-        for (int k = 0; k < MM_ISUM_UNITS; ++k) {
-            acc[k] = is_add(acc[k], r0[k]);
-            if (two) acc[k] = is_add(acc[k], r1[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < MM_ISUM_UNITS; ++k)
-        if (ok[k]) dst[u[k]] = acc[k];
-}
 
 // grid: per tensor rows x chunks-per-row workgroups, row-major -- every tensor has its own row extent, no workgroup is launched for a row a
 // tensor does not have --, then the bad images' blocks
@@ -256,13 +198,13 @@ __global__ __launch_bounds__(256) void index_sum_kernel(IndexSumArgs a) {
         a.grad_azim[i] = nan; a.grad_elev[i] = nan; a.grad_dist[i] = nan; a.grad_bias[2 * i] = nan; a.grad_bias[2 * i + 1] = nan;
         return;
     }
-    const int t = x < a.xb[1] ? 0 : (x < a.xb[2] ? 1 : (x < a.xb[3] ? 2 : 3));
-    const int len = a.len[t], r = (x - a.xb[t]) / a.cpr[t], chunk = (x - a.xb[t]) % a.cpr[t];
+    const int t = x < a.xb[1] ? 0 : (x < a.xb[2] ? 1 : (x < a.xb[3] ? 2 : 3));   // (workgroup-uniform)
+    const int len = a.t.len[t], r = (x - a.xb[t]) / a.cpr[t], chunk = (x - a.xb[t]) % a.cpr[t];
     const int beg = a.offsets[t][r], cnt = a.offsets[t][r + 1] - beg;
     const int* list = a.images[t] + beg;
-    float* dst = a.dst[t] + (size_t)r * len;
-    if (a.vec[t]) index_sum_chunk<float4>((const float4*)a.src[t], (float4*)dst, len >> 2, list, cnt, chunk);
-    else index_sum_chunk<float>(a.src[t], dst, len, list, cnt, chunk);
+    float* dst = a.t.dst[t] + (size_t)r * len;
+    if (a.t.vec[t]) row_sum_chunk<float4, true>((const float4*)a.t.src[t], (float4*)dst, len >> 2, list, cnt, chunk);
+    else row_sum_chunk<float, true>(a.t.src[t], dst, len, list, cnt, chunk);
 }
 
 // staging[t] (M, len[t]) -> out[t] (rows[t], len[t]) for the tensors with len[t] > 0, and NaN into the camera gradients of bad images: one launch.
@@ -273,12 +215,11 @@ int launch_index_sum(int M, const int* rows, const float* const* staging, float*
     a.grad_azim = g->grad_azimuths; a.grad_elev = g->grad_elevations; a.grad_dist = g->grad_distances; a.grad_bias = g->grad_biases;
     long long x = 0;
     for (int t = 0; t < 4; ++t) {
-        const bool on = len[t] > 0 && staging[t] && out[t];
-        a.src[t] = staging[t]; a.dst[t] = out[t]; a.len[t] = on ? len[t] : 0; a.cpr[t] = 1;
         a.offsets[t] = p.offsets[t]; a.images[t] = p.images[t];
-        a.vec[t] = on && (len[t] & 3) == 0 && (((uintptr_t)staging[t] | (uintptr_t)out[t]) & 15) == 0;
         a.xb[t] = (int)x;
-        if (on) { const int n = a.vec[t] ? len[t] >> 2 : len[t]; a.cpr[t] = (n + 256 * MM_ISUM_UNITS - 1) / (256 * MM_ISUM_UNITS); x += (long long)rows[t] * a.cpr[t]; }
+        const int cpr = row_sum_pack(a.t, t, staging[t], out[t], len[t]);
+        a.cpr[t] = cpr ? cpr : 1;
+        x += (long long)rows[t] * cpr;
         if (x > 0x7fff0000LL) return MM_ERR_UNSUPPORTED;          // (65535 rows of a 16-megapixel background: not a render)
     }
     a.xb[4] = (int)x;

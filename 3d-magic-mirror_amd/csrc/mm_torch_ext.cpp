@@ -98,7 +98,7 @@ MMRenderDesc proto_desc(const std::string& proto) {
 
 template <class Desc> void bind_workspace(Desc& d, const at::Tensor& ws) { d.workspace = ws.data_ptr(); d.workspace_bytes = (size_t)ws.numel(); }
 
-// ---- what RenderNode, GeometryNode and RenderViewsNode share: inputs, descriptor, gradients, record check, camera shapes ------------------
+// ---- what the render nodes share: inputs, outputs, descriptors, gradients, record check, camera shapes -----------------------------------------
 using torch::autograd::AutogradContext;
 using torch::autograd::tensor_list;
 
@@ -117,32 +117,39 @@ DenseInputs saved_inputs(const tensor_list& sv) {
     return {sv[S_VERTICES], sv[S_TEXTURES], sv[S_LIGHTS], sv[S_BG], sv[S_AZIMUTHS], sv[S_ELEVATIONS], sv[S_DISTANCES], sv[S_BIASES]};
 }
 
-// The caller's tensors as DenseInputs, every shape checked against the prototype `d` of `images` images of `samples` samples (images = samples x
-// views; render and render_geometry have one view).  per_view: the render_views call, whose cameras arrive as (B,N) / (B,N,2) and whose
-// messages name the sample count.
-DenseInputs dense_inputs(const c10::Device& dev, const MMRenderDesc& d, int64_t samples, int64_t images, bool per_view, const at::Tensor& vertices,
+// The caller's tensors as DenseInputs, every shape checked against the prototype `d` of `images` images.  The per-sample tensors carry their own
+// row counts: `samples` each in RENDER (and render_geometry: images = samples) and VIEWS (images = samples x views), any count >= 1 in INDEXED.
+// VIEWS and INDEXED take the cameras in any shape of `images` values (biases: pairs) and name the counts in their messages.
+enum Caller { RENDER, VIEWS, INDEXED };
+DenseInputs dense_inputs(const c10::Device& dev, const MMRenderDesc& d, Caller who, int64_t samples, int64_t images, const at::Tensor& vertices,
                          const at::Tensor& textures, const at::Tensor& lights, const c10::optional<at::Tensor>& bg, const at::Tensor& azimuths,
                          const at::Tensor& elevations, const at::Tensor& distances, const at::Tensor& biases) {
     const bool geometry = d.geometry_only == 1;                  // (no textures, lights or bg)
     DenseInputs in;
     in.vertices = dense_f32(vertices, dev, "vertices");
     if (!geometry) { in.textures = dense_f32(textures, dev, "textures"); in.lights = dense_f32(lights, dev, "lights"); }
+    // (which error comes first when two inputs are bad: INDEXED has always converted bg before the cameras, the other callers after them)
+    auto dense_bg = [&] { if (bg.has_value() && bg->defined()) in.bg = dense_f32(*bg, dev, "bg"); };
+    if (who == INDEXED) dense_bg();
     in.azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); in.elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
     in.distances = dense_f32(distances, dev, "distances").reshape({-1}); in.biases = dense_f32(biases, dev, "biases");
-    if (per_view) in.biases = in.biases.reshape({-1, 2});
-    if (bg.has_value() && bg->defined()) in.bg = dense_f32(*bg, dev, "bg");
+    if (who != RENDER) in.biases = in.biases.reshape({-1, 2});
+    if (who != INDEXED) dense_bg();
     const at::Tensor &v = in.vertices, &t = in.textures, &l = in.lights, &b = in.biases;
-    const bool vertices_ok = v.dim() == 3 && v.size(0) == samples && v.size(1) == d.V && v.size(2) == 3;
-    const bool textures_ok = geometry || (t.dim() == 4 && t.size(0) == samples && t.size(1) == 3 && t.size(2) == d.Ht && t.size(3) == d.Wt);
-    const bool lights_ok = geometry || (l.dim() == 2 && l.size(0) == samples && l.size(1) == 9);
-    const bool bg_ok = !d.no_mask || (in.bg.defined() && in.bg.dim() == 4 && in.bg.size(0) == samples && in.bg.size(1) == 3 && in.bg.size(2) == d.H && in.bg.size(3) == d.W);
+    auto rows_ok = [&](const at::Tensor& x) { return who == INDEXED ? x.size(0) >= 1 : x.size(0) == samples; };
+    const bool vertices_ok = v.dim() == 3 && rows_ok(v) && v.size(1) == d.V && v.size(2) == 3;
+    const bool textures_ok = geometry || (t.dim() == 4 && rows_ok(t) && t.size(1) == 3 && t.size(2) == d.Ht && t.size(3) == d.Wt);
+    const bool lights_ok = geometry || (l.dim() == 2 && rows_ok(l) && l.size(1) == 9);
+    const bool bg_ok = !d.no_mask || (in.bg.defined() && in.bg.dim() == 4 && rows_ok(in.bg) && in.bg.size(1) == 3 && in.bg.size(2) == d.H && in.bg.size(3) == d.W);
     const bool cameras_ok = in.elevations.size(0) == images && in.distances.size(0) == images && b.dim() == 2 && b.size(0) == images && b.size(1) == 2;
-    if (per_view) {
-        TORCH_CHECK(in.azimuths.size(0) == images && cameras_ok, "render_views: the cameras must hold B*N = ", images, " values each (biases B*N pairs)");
-        TORCH_CHECK(vertices_ok, "vertices must be (", samples, ",", d.V, ",3), got ", v.sizes());
-        TORCH_CHECK(textures_ok, "textures must be (", samples, ",3,", d.Ht, ",", d.Wt, "), got ", t.sizes());
-        TORCH_CHECK(lights_ok, "lights must be (", samples, ",9), got ", l.sizes());
-        TORCH_CHECK(bg_ok, "bg must be (", samples, ",3,", d.H, ",", d.W, ")");
+    if (who != RENDER) {
+        const std::string n = who == INDEXED ? "R" : std::to_string(samples);      // how the messages name a tensor's rows
+        TORCH_CHECK(in.azimuths.size(0) == images && cameras_ok, who == INDEXED ? "render_indexed: the cameras must hold M = " : "render_views: the cameras must hold B*N = ",
+                    images, " values each (biases ", who == INDEXED ? "M" : "B*N", " pairs)");
+        TORCH_CHECK(vertices_ok, "vertices must be (", n, ",", d.V, ",3), got ", v.sizes());
+        TORCH_CHECK(textures_ok, "textures must be (", n, ",3,", d.Ht, ",", d.Wt, "), got ", t.sizes());
+        TORCH_CHECK(lights_ok, "lights must be (", n, ",9), got ", l.sizes());
+        TORCH_CHECK(bg_ok, "bg must be (", n, ",3,", d.H, ",", d.W, ")");
     } else {
         TORCH_CHECK(in.azimuths.size(0) == images, "batch size ", in.azimuths.size(0), " does not match the descriptor (", d.B, ")");
         TORCH_CHECK(vertices_ok, "vertices must be (B,", d.V, ",3), got ", v.sizes());
@@ -174,6 +181,53 @@ struct RenderGrads {
         abi.grad_azimuths = mptr(azimuths); abi.grad_elevations = mptr(elevations); abi.grad_distances = mptr(distances); abi.grad_biases = mptr(biases);
     }
 };
+
+// The four outputs of an image-producing node for the leading shape `lead` ({B}, {B,N} or {M}), bound into the forward's descriptor.
+struct Outputs {
+    at::Tensor rgba, fn, face_idx, imn;
+    Outputs(MMRenderDesc& d, std::vector<int64_t> lead, const at::TensorOptions& opts, bool want_imnormal) {
+        auto shape = [&lead](std::initializer_list<int64_t> tail) { std::vector<int64_t> s = lead; s.insert(s.end(), tail); return s; };
+        rgba = at::empty(shape({d.H, d.W, 4}), opts); fn = at::empty(shape({d.F, 3}), opts);
+        face_idx = at::empty(shape({d.H, d.W}), opts.dtype(at::kInt));
+        imn = want_imnormal ? at::empty(shape({d.H, d.W, 3}), opts) : at::empty({0}, opts);
+        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
+    }
+    // saves enum Saved up to the workspace, then `more`; an output nobody used arrives as an undefined gradient, not as a zero-filled tensor (three
+    // allocations + fill launches per step when only the image feeds the loss)
+    tensor_list save(AutogradContext* ctx, const DenseInputs& in, const at::Tensor& ws, const tensor_list& more = {}) const {
+        tensor_list saved = in.list();
+        saved.insert(saved.end(), {face_idx, fn, ws});
+        saved.insert(saved.end(), more.begin(), more.end());
+        ctx->save_for_backward(saved);
+        ctx->mark_non_differentiable({face_idx, imn});
+        ctx->set_materialize_grads(false);
+        return {rgba, fn, imn, face_idx};
+    }
+};
+
+// A backward's descriptor, rebuilt from the context's prototype and the saved list (the image is not read back, nor saved: the backward re-forms the
+// prediction per pixel), and its two upstream gradients, dense: the normals' may be absent (NULL); the image's is zeros where nothing reached
+// the image and `zero_image` asks for them.
+struct Backward {
+    MMRenderDesc d;
+    at::Tensor grgba, gfn;
+    Backward(AutogradContext* ctx, const tensor_list& sv, const DenseInputs& in, const tensor_list& g, bool zero_image) : d(proto_desc(ctx->saved_data["proto"].toStringRef())) {
+        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
+        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
+        d.rgba = nullptr; d.imnormal = nullptr;
+        if (g[0].defined()) grgba = g[0].to(at::kFloat).contiguous();
+        else if (zero_image) { auto shape = sv[S_FACE_IDX].sizes().vec(); shape.push_back(4); grgba = at::zeros(shape, in.vertices.options()); }
+        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
+    }
+};
+
+// a backward's return value, one entry per forward argument: `lead` non-tensors, the gradients of the eight inputs, `trail` more non-tensors
+tensor_list input_grads(size_t lead, const RenderGrads& gr, size_t trail) {
+    tensor_list out(lead, at::Tensor());
+    out.insert(out.end(), {gr.vertices, gr.textures, gr.lights, gr.bg, gr.azimuths, gr.elevations, gr.distances, gr.biases});
+    out.resize(out.size() + trail);
+    return out;
+}
 
 // DiffRender.check_texture_records (f_status: mm_render_status, or 0): a diagnostic after a backward -- it synchronises the stream.  `d` is the
 // backward's descriptor of `images` images; their render workspace starts `offset` bytes into the node's (render_views: behind the staging head).
@@ -256,14 +310,11 @@ class RenderNode : public torch::autograd::Function<RenderNode> {
         at::Tensor ws = at::empty({ws_bytes}, azimuths.options().dtype(at::kByte));   // (the caching allocator is the workspace pool)
         MMRenderDesc d = proto_desc(proto);
         const int64_t B = d.B, H = d.H, W = d.W;
-        const DenseInputs in = dense_inputs(dev, d, B, B, false, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
+        const DenseInputs in = dense_inputs(dev, d, RENDER, B, B, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
         auto opts = in.vertices.options();
-        at::Tensor rgba = at::empty({B, H, W, 4}, opts), fn = at::empty({B, (int64_t)d.F, 3}, opts);
-        at::Tensor face_idx = at::empty({B, H, W}, opts.dtype(at::kInt));
-        at::Tensor imn = want_imnormal ? at::empty({B, H, W, 3}, opts) : at::empty({0}, opts);
+        const Outputs out(d, {B}, opts, want_imnormal);
         at::Tensor loss, gtt;
         bind_inputs(d, in); bind_workspace(d, ws);
-        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
         const bool fused = gt.has_value() && gt->defined();
         if (fused) {
             gtt = dense_f32(*gt, dev, "gt_data");
@@ -276,20 +327,14 @@ class RenderNode : public torch::autograd::Function<RenderNode> {
         if (fused) check(((render_fwd_t)f_loss)(&d, stream), "mm_render_fused_loss");
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto;
         ctx->saved_data["image_weight"] = image_weight;
-        tensor_list saved = in.list();
-        saved.insert(saved.end(), {face_idx, fn, ws, gtt});      // (enum Saved)
-        ctx->save_for_backward(saved);
-        ctx->mark_non_differentiable({face_idx, imn});
-        ctx->set_materialize_grads(false);                       // an output nobody used arrives as an undefined gradient, not as a zero-filled tensor (three
-                                                                 // allocations + fill launches per step when only the image feeds the loss)
-        if (fused) ctx->mark_non_differentiable({rgba});
-        tensor_list ret = {rgba, fn, imn, face_idx};
+        tensor_list ret = out.save(ctx, in, ws, {gtt});          // (enum Saved)
+        if (fused) ctx->mark_non_differentiable({out.rgba});
         if (fused) ret.push_back(loss);
         else if (defer) {
             // deferred fusion: a fifth output whose only job is to carry dL/dloss of a later recon_data(image, gt) back into THIS node (never read, never
             // written: no launch), and the mailbox that recon_data finds through the image's address
             auto mb = std::make_shared<Mailbox>();
-            mb->rgba_ptr = rgba.data_ptr(); mb->B = B; mb->H = H; mb->W = W;
+            mb->rgba_ptr = out.rgba.data_ptr(); mb->B = B; mb->H = H; mb->W = W;
             mb->has_token = true;
             ctx->saved_data["mb"] = mailbox_holder(mb);
             { std::lock_guard<std::mutex> lock(g_mail_mutex);
@@ -315,32 +360,23 @@ class RenderNode : public torch::autograd::Function<RenderNode> {
         const at::Tensor& gt = deferred ? mb->gt : sv[S_GT];
         const double image_weight = deferred ? mb->image_weight : ctx->saved_data["image_weight"].toDouble();
         const bool fused = gt.defined();
-        MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
-        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
-        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
-        d.rgba = nullptr; d.imnormal = nullptr;                  // the backward re-forms the prediction per pixel: the image is not read back (nor saved)
-        at::Tensor grgba, gfn, gloss;
-        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
+        Backward b(ctx, sv, in, g, !fused);
+        MMRenderDesc& d = b.d;
+        at::Tensor gloss;
         if (fused) {
             // An undefined gradient of the loss output means the loss took no part in what is being differentiated (materialize_grads is off):
             // its gradient is ZERO, never one -- e.g. reg.backward() through attributes['face_normals'] only.
             gloss = token_grad ? g[4].to(at::kFloat).reshape({}).contiguous() : at::zeros({}, in.vertices.options().dtype(at::kFloat));
             d.fused_gt = fptr(gt); d.fused_image_weight = (float)image_weight; d.fused_grad_loss = fptr(gloss);
-            if (deferred) {
-                d.fused_totals = mb->totals; d.fused_contour = 0.f;
-                if (g[0].defined()) grgba = g[0].to(at::kFloat).contiguous();   // the image's other consumers: added by the kernel
-            }
-        } else {
-            grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({d.B, d.H, d.W, 4}, in.vertices.options());
+            if (deferred) { d.fused_totals = mb->totals; d.fused_contour = 0.f; }    // (b.grgba: the image's other consumers, added by the kernel)
+            else b.grgba = at::Tensor();                         // the fused loss alone drives the image
         }
-        RenderGrads gr(in, d.no_mask, grgba, gfn);
+        RenderGrads gr(in, d.no_mask, b.grgba, b.gfn);
         void* stream = current_stream(dev);
         check(((render_bwd_t)ctx->saved_data["f_bwd"].toInt())(&d, &gr.abi, stream), "mm_render_backward");
         check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, d.B, 0, "mm_render_backward", "images");
         restore_camera_shapes(ctx, gr);
-        // one entry per forward argument: six non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, then four more
-        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr.vertices, gr.textures, gr.lights, gr.bg,
-                gr.azimuths, gr.elevations, gr.distances, gr.biases, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        return input_grads(6, gr, 4);
     }
 };
 
@@ -407,7 +443,7 @@ class GeometryNode : public torch::autograd::Function<GeometryNode> {
         MMRenderDesc d = proto_desc(proto);
         TORCH_CHECK(d.geometry_only == 1, "GeometryNode needs a geometry-only descriptor prototype");
         save_camera_shapes(ctx, azimuths, elevations, distances, biases);
-        const DenseInputs in = dense_inputs(dev, d, d.B, d.B, false, vertices, at::Tensor(), at::Tensor(), c10::nullopt, azimuths, elevations, distances, biases);
+        const DenseInputs in = dense_inputs(dev, d, RENDER, d.B, d.B, vertices, at::Tensor(), at::Tensor(), c10::nullopt, azimuths, elevations, distances, biases);
         at::Tensor ws = at::empty({ws_bytes}, azimuths.options().dtype(at::kByte));
         at::Tensor fn = at::empty({(int64_t)d.B, (int64_t)d.F, 3}, in.vertices.options());
         bind_inputs(d, in); bind_workspace(d, ws);
@@ -451,28 +487,20 @@ class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
         const c10::Device dev = azimuths.device();
         const DeviceGuard guard(dev);
         MMRenderDesc d = proto_desc(proto);                          // (of the B*N images)
-        const int64_t N = views, BN = d.B, H = d.H, W = d.W;
+        const int64_t N = views, BN = d.B;
         TORCH_CHECK(N >= 1 && BN % N == 0, "render_views: ", BN, " images are not a multiple of ", N, " views");
         const int64_t B = BN / N;
         save_camera_shapes(ctx, azimuths, elevations, distances, biases);
-        const DenseInputs in = dense_inputs(dev, d, B, BN, true, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
+        const DenseInputs in = dense_inputs(dev, d, VIEWS, B, BN, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
         auto opts = in.vertices.options();
-        at::Tensor rgba = at::empty({B, N, H, W, 4}, opts), fn = at::empty({B, N, (int64_t)d.F, 3}, opts);
-        at::Tensor face_idx = at::empty({B, N, H, W}, opts.dtype(at::kInt));
-        at::Tensor imn = want_imnormal ? at::empty({B, N, H, W, 3}, opts) : at::empty({0}, opts);
+        const Outputs out(d, {B, N}, opts, want_imnormal);
         at::Tensor ws = at::empty({ws_bytes}, opts.dtype(at::kByte));
         bind_inputs(d, in); bind_workspace(d, ws);
-        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
         const MMRenderViewsDesc vd{d, (int32_t)views};
         check(((views_fwd_t)f_fwd)(&vd, current_stream(dev)), "mm_render_views_forward");
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto; ctx->saved_data["views"] = views;
         ctx->saved_data["staging_bytes"] = staging_bytes;            // the head of the workspace (the per-image gradients' staging): mm_render_status skips it
-        tensor_list saved = in.list();                               // (the UN-replicated inputs)
-        saved.insert(saved.end(), {face_idx, fn, ws});               // (enum Saved)
-        ctx->save_for_backward(saved);
-        ctx->mark_non_differentiable({face_idx, imn});
-        ctx->set_materialize_grads(false);
-        return {rgba, fn, imn, face_idx};
+        return out.save(ctx, in, ws);                                // (enum Saved: the UN-replicated inputs)
     }
 
     static tensor_list backward(AutogradContext* ctx, tensor_list g) {
@@ -480,25 +508,17 @@ class RenderViewsNode : public torch::autograd::Function<RenderViewsNode> {
         const DenseInputs in = saved_inputs(sv);
         const c10::Device dev = in.azimuths.device();
         const DeviceGuard guard(dev);
-        MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
-        const int64_t N = ctx->saved_data["views"].toInt(), BN = d.B, B = BN / N;
-        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
-        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
-        d.rgba = nullptr; d.imnormal = nullptr;
-        at::Tensor grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({B, N, (int64_t)d.H, (int64_t)d.W, 4}, in.vertices.options());
-        at::Tensor gfn;
-        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
-        RenderGrads gr(in, d.no_mask, grgba, gfn);
+        const Backward b(ctx, sv, in, g, true);
+        const MMRenderDesc& d = b.d;
+        RenderGrads gr(in, d.no_mask, b.grgba, b.gfn);
         void* stream = current_stream(dev);
-        const MMRenderViewsDesc vd{d, (int32_t)N};
+        const MMRenderViewsDesc vd{d, (int32_t)ctx->saved_data["views"].toInt()};
         check(((views_bwd_t)ctx->saved_data["f_bwd"].toInt())(&vd, &gr.abi, stream), "mm_render_views_backward");
         // per IMAGE, as in render: the render workspace of the B*N images lies behind the staging head of the multi-view workspace
-        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, BN, (size_t)ctx->saved_data["staging_bytes"].toInt(),
+        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, d.B, (size_t)ctx->saved_data["staging_bytes"].toInt(),
                               "mm_render_views_backward", "samples");
         restore_camera_shapes(ctx, gr);
-        // one entry per forward argument: seven non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, want_imnormal
-        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr.vertices, gr.textures, gr.lights, gr.bg,
-                gr.azimuths, gr.elevations, gr.distances, gr.biases, at::Tensor()};
+        return input_grads(7, gr, 1);
     }
 };
 
@@ -528,21 +548,9 @@ class RenderIndexedNode : public torch::autograd::Function<RenderIndexedNode> {
         const c10::Device dev = azimuths.device();
         const DeviceGuard guard(dev);
         MMRenderDesc d = proto_desc(proto);                          // (of the M images)
-        const int64_t M = d.B, H = d.H, W = d.W;
+        const int64_t M = d.B;
         save_camera_shapes(ctx, azimuths, elevations, distances, biases);
-        DenseInputs in;
-        in.vertices = dense_f32(vertices, dev, "vertices"); in.textures = dense_f32(textures, dev, "textures"); in.lights = dense_f32(lights, dev, "lights");
-        if (bg.has_value() && bg->defined()) in.bg = dense_f32(*bg, dev, "bg");
-        in.azimuths = dense_f32(azimuths, dev, "azimuths").reshape({-1}); in.elevations = dense_f32(elevations, dev, "elevations").reshape({-1});
-        in.distances = dense_f32(distances, dev, "distances").reshape({-1}); in.biases = dense_f32(biases, dev, "biases").reshape({-1, 2});
-        TORCH_CHECK(in.azimuths.size(0) == M && in.elevations.size(0) == M && in.distances.size(0) == M && in.biases.size(0) == M,
-                    "render_indexed: the cameras must hold M = ", M, " values each (biases M pairs)");
-        TORCH_CHECK(in.vertices.dim() == 3 && in.vertices.size(0) >= 1 && in.vertices.size(1) == d.V && in.vertices.size(2) == 3, "vertices must be (R,", d.V, ",3), got ", in.vertices.sizes());
-        TORCH_CHECK(in.textures.dim() == 4 && in.textures.size(0) >= 1 && in.textures.size(1) == 3 && in.textures.size(2) == d.Ht && in.textures.size(3) == d.Wt,
-                    "textures must be (R,3,", d.Ht, ",", d.Wt, "), got ", in.textures.sizes());
-        TORCH_CHECK(in.lights.dim() == 2 && in.lights.size(0) >= 1 && in.lights.size(1) == 9, "lights must be (R,9), got ", in.lights.sizes());
-        TORCH_CHECK(!d.no_mask || (in.bg.defined() && in.bg.dim() == 4 && in.bg.size(0) >= 1 && in.bg.size(1) == 3 && in.bg.size(2) == H && in.bg.size(3) == W),
-                    "bg must be (R,3,", H, ",", W, ")");
+        const DenseInputs in = dense_inputs(dev, d, INDEXED, 0, M, vertices, textures, lights, bg, azimuths, elevations, distances, biases);
         IndexTensors ix;
         const c10::optional<at::Tensor>* given[4] = {&idx_vertices, &idx_textures, &idx_lights, &idx_bg};
         for (int k = 0; k < 4; ++k) {
@@ -553,23 +561,15 @@ class RenderIndexedNode : public torch::autograd::Function<RenderIndexedNode> {
             ix.t[k] = t;
         }
         auto opts = in.vertices.options();
-        at::Tensor rgba = at::empty({M, H, W, 4}, opts), fn = at::empty({M, (int64_t)d.F, 3}, opts);
-        at::Tensor face_idx = at::empty({M, H, W}, opts.dtype(at::kInt));
-        at::Tensor imn = want_imnormal ? at::empty({M, H, W, 3}, opts) : at::empty({0}, opts);
+        const Outputs out(d, {M}, opts, want_imnormal);
         at::Tensor ws = at::empty({ws_bytes}, opts.dtype(at::kByte));
         bind_inputs(d, in); bind_workspace(d, ws);
-        d.rgba = mptr(rgba); d.face_idx = face_idx.data_ptr<int32_t>(); d.face_normals = mptr(fn); d.imnormal = want_imnormal ? mptr(imn) : nullptr;
         MMRenderIndexedDesc vd{};
         bind_indexed(vd, d, in, ix, backward, status_word);
         check(((indexed_fwd_t)f_fwd)(&vd, current_stream(dev)), "mm_render_indexed_forward");
         ctx->saved_data["f_bwd"] = f_bwd; ctx->saved_data["f_status"] = f_status; ctx->saved_data["proto"] = proto;
         ctx->saved_data["head_bytes"] = head_bytes; ctx->saved_data["status_word"] = status_word; ctx->saved_data["backward"] = backward;
-        tensor_list saved = in.list();                               // (the UN-gathered inputs)
-        saved.insert(saved.end(), {face_idx, fn, ws, at::Tensor(), ix.t[0], ix.t[1], ix.t[2], ix.t[3]});     // (enum Saved, then the four indices)
-        ctx->save_for_backward(saved);
-        ctx->mark_non_differentiable({face_idx, imn});
-        ctx->set_materialize_grads(false);
-        return {rgba, fn, imn, face_idx};
+        return out.save(ctx, in, ws, {at::Tensor(), ix.t[0], ix.t[1], ix.t[2], ix.t[3]});     // (enum Saved: the UN-gathered inputs; then the four indices)
     }
 
     static tensor_list backward(AutogradContext* ctx, tensor_list g) {
@@ -578,15 +578,9 @@ class RenderIndexedNode : public torch::autograd::Function<RenderIndexedNode> {
         const c10::Device dev = in.azimuths.device();
         const DeviceGuard guard(dev);
         TORCH_CHECK(ctx->saved_data["backward"].toBool(), "render_indexed: the forward ran without an input that requires grad and kept no staging");
-        MMRenderDesc d = proto_desc(ctx->saved_data["proto"].toStringRef());
-        const int64_t M = d.B;
-        bind_inputs(d, in); bind_workspace(d, sv[S_WORKSPACE]);
-        d.face_idx = sv[S_FACE_IDX].data_ptr<int32_t>(); d.face_normals = mptr(sv[S_FACE_NORMALS]);
-        d.rgba = nullptr; d.imnormal = nullptr;
-        at::Tensor grgba = g[0].defined() ? g[0].to(at::kFloat).contiguous() : at::zeros({M, (int64_t)d.H, (int64_t)d.W, 4}, in.vertices.options());
-        at::Tensor gfn;
-        if (g[1].defined()) gfn = g[1].to(at::kFloat).contiguous();
-        RenderGrads gr(in, d.no_mask, grgba, gfn);                   // (the indexed inputs' gradients in the inputs' own shapes)
+        const Backward b(ctx, sv, in, g, true);
+        const MMRenderDesc& d = b.d;
+        RenderGrads gr(in, d.no_mask, b.grgba, b.gfn);               // (the indexed inputs' gradients in the inputs' own shapes)
         void* stream = current_stream(dev);
         IndexTensors ix;
         for (int k = 0; k < 4; ++k) ix.t[k] = sv[S_GT + 1 + k];
@@ -594,12 +588,10 @@ class RenderIndexedNode : public torch::autograd::Function<RenderIndexedNode> {
         bind_indexed(vd, d, in, ix, true, ctx->saved_data["status_word"].toInt());
         check(((indexed_bwd_t)ctx->saved_data["f_bwd"].toInt())(&vd, &gr.abi, stream), "mm_render_indexed_backward");
         // per IMAGE, as in render: the render workspace of the M images lies behind the head of the indexed workspace
-        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, M, (size_t)ctx->saved_data["head_bytes"].toInt(),
+        check_texture_records(ctx->saved_data["f_status"].toInt(), d, stream, d.B, (size_t)ctx->saved_data["head_bytes"].toInt(),
                               "mm_render_indexed_backward", "images");
         restore_camera_shapes(ctx, gr);
-        // one entry per forward argument: eight non-tensors, then vertices, textures, lights, bg, azimuths, elevations, distances, biases, four indices, want_imnormal
-        return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gr.vertices, gr.textures, gr.lights,
-                gr.bg, gr.azimuths, gr.elevations, gr.distances, gr.biases, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        return input_grads(8, gr, 5);
     }
 };
 

@@ -95,6 +95,22 @@ def check_render_index(index, rows, M):
     return out
 
 
+def require_tensors(who, attributes):
+    """TypeError unless the seven attributes every render reads are tensors (`who`: the calling method, for the message)."""
+    for k in ('vertices', 'textures', 'lights', 'azimuths', 'elevations', 'distances', 'biases'):
+        if not torch.is_tensor(attributes.get(k)):
+            raise TypeError("%s needs attributes[%r] as a tensor" % (who, k))
+
+
+def sub_desc(cls, proto, **fields):
+    """A multi-view or indexed descriptor: the render prototype's bytes, then the fields of its own."""
+    vd = cls()
+    ctypes.memmove(ctypes.byref(vd), proto, len(proto))
+    for k, v in fields.items():
+        setattr(vd, k, v)
+    return vd
+
+
 class DiffRender(object):
     """Drop-in for ``networks.DiffRender`` (networks.py:164)."""
 
@@ -269,9 +285,7 @@ class DiffRender(object):
     def _view_cameras(self, attributes):
         """(B, N, the four camera attributes as (B,N) / (B,N,2)) of a render_views call, every shape checked: B from `vertices`; a camera
         attribute is (B,N) (biases (B,N,2)) or, broadcast over the views, (B,) (biases (B,2)); at least one carries N and all that do agree."""
-        for k in ('vertices', 'textures', 'lights', 'azimuths', 'elevations', 'distances', 'biases'):
-            if not torch.is_tensor(attributes.get(k)):
-                raise TypeError("render_views needs attributes[%r] as a tensor" % k)
+        require_tensors("render_views", attributes)
         vertices, textures, lights = attributes['vertices'], attributes['textures'], attributes['lights']
         if vertices.dim() != 3 or tuple(vertices.shape[1:]) != (self.num_vertices, 3):
             raise ValueError("vertices must be (B,%d,3), got %s" % (self.num_vertices, tuple(vertices.shape)))
@@ -325,7 +339,9 @@ class DiffRender(object):
         st = self._static(azimuths.device)
         Ht, Wt = int(textures.shape[2]), int(textures.shape[3])
         proto, nbytes = self._proto(st, B * n, no_mask, Ht, Wt)
-        staging = self._views_staging_bytes(proto, n)            # the workspace's head; the B*N images' render workspace (render's own size) follows
+        # the workspace's head; the B*N images' render workspace (render's own size) follows
+        staging = self._head_bytes(("views", proto, n), lambda: sub_desc(N.MMRenderViewsDesc, proto, views=n),
+                                   "mm_render_views_query_workspace", lambda: "%d views" % n)
         rgba, fn, imn, face_idx = N.torch_ext().render_views(
             N.fn_addr("mm_render_views_forward"), N.fn_addr("mm_render_views_backward"),
             N.fn_addr("mm_render_status") if self.check_texture_records else 0, proto, n, nbytes + staging, staging,
@@ -333,17 +349,16 @@ class DiffRender(object):
         self._set_outputs(attributes, fn, imn, face_idx)
         return rgba.permute(0, 1, 4, 2, 3), attributes
 
-    def _views_staging_bytes(self, proto, views):
-        """What a multi-view workspace holds beyond the render workspace of its B*N images: the staging areas of the per-image gradients."""
-        key = ("views", proto, views)
+    def _head_bytes(self, key, make_desc, query, shape):
+        """What a multi-view or indexed workspace holds in front of the render workspace of its images (render_views: the staging areas of the
+        per-image gradients; render_indexed: the plan and, for a call with a backward, the staging areas), cached under `key`: the library's
+        `query` (its name) of the sub-descriptor make_desc() minus mm_query_workspace of its render.  shape(): the refusal's words for the shape."""
         hit = self._desc_cache.get(key)
         if hit is None:
-            vd = N.MMRenderViewsDesc()
-            ctypes.memmove(ctypes.byref(vd), proto, len(proto))
-            vd.views = views
-            hit = int(N.lib().mm_render_views_query_workspace(ctypes.byref(vd))) - int(N.lib().mm_query_workspace(ctypes.byref(vd.render)))
+            vd = make_desc()
+            hit = int(getattr(N.lib(), query)(ctypes.byref(vd))) - int(N.lib().mm_query_workspace(ctypes.byref(vd.render)))
             if hit < 0:
-                raise RuntimeError("mm_render_views_query_workspace refused the shape (%d images, %d views)" % (vd.render.B, views))
+                raise RuntimeError("%s refused the shape (%d images, %s)" % (query, vd.render.B, shape()))
             self._desc_cache[key] = hit
         return hit
 
@@ -361,9 +376,7 @@ class DiffRender(object):
         read it, in ascending image order (plain adds: bitwise reproducible), zeros for a row no image reads.
         Not here: blending two rows inside the render (``mix_attributes``), the fused loss and step mode over indices."""
         no_mask = bool(no_mask)
-        for k in ('vertices', 'textures', 'lights', 'azimuths', 'elevations', 'distances', 'biases'):
-            if not torch.is_tensor(attributes.get(k)):
-                raise TypeError("render_indexed needs attributes[%r] as a tensor" % k)
+        require_tensors("render_indexed", attributes)
         if no_mask and not torch.is_tensor(attributes.get('bg')):
             raise TypeError("render_indexed(no_mask=True) needs attributes['bg'] (R,3,H,W)")
         azimuths, elevations, distances, biases = (attributes[k] for k in ('azimuths', 'elevations', 'distances', 'biases'))
@@ -397,7 +410,10 @@ class DiffRender(object):
         proto, nbytes = self._proto(st, M, no_mask, Ht, Wt)
         backward = torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                    for t in (vertices, textures, lights, bg, azimuths, elevations, distances, biases))
-        head = self._indexed_head_bytes(proto, tuple(rows.get(k, M) for k in INDEXED), backward)
+        nrows = tuple(rows.get(k, M) for k in INDEXED)
+        head = self._head_bytes(("indexed", proto, nrows, bool(backward)),
+                                lambda: sub_desc(N.MMRenderIndexedDesc, proto, rows=nrows, backward=1 if backward else 0),
+                                "mm_render_indexed_query_workspace", lambda: "rows %s" % (nrows,))
         self.last_indexed_workspace_bytes = nbytes + head         # (what the node allocates: the forward-only query when nothing requires grad)
         rgba, fn, imn, face_idx = N.torch_ext().render_indexed(
             N.fn_addr("mm_render_indexed_forward"), N.fn_addr("mm_render_indexed_backward"),
@@ -406,23 +422,6 @@ class DiffRender(object):
             bool(self.emit_imnormal))
         self._set_outputs(attributes, fn, imn, face_idx)
         return rgba.permute(0, 3, 1, 2), attributes
-
-    def _indexed_head_bytes(self, proto, rows, backward):
-        """What an indexed workspace holds in front of the render workspace of its M images: the plan and, for a call with a backward, the
-        staging areas of the per-image gradients."""
-        key = ("indexed", proto, rows, bool(backward))
-        hit = self._desc_cache.get(key)
-        if hit is None:
-            vd = N.MMRenderIndexedDesc()
-            ctypes.memmove(ctypes.byref(vd), proto, len(proto))
-            for t in range(4):
-                vd.rows[t] = rows[t]
-            vd.backward = 1 if backward else 0
-            hit = int(N.lib().mm_render_indexed_query_workspace(ctypes.byref(vd))) - int(N.lib().mm_query_workspace(ctypes.byref(vd.render)))
-            if hit < 0:
-                raise RuntimeError("mm_render_indexed_query_workspace refused the shape (%d images, rows %s)" % (vd.render.B, rows))
-            self._desc_cache[key] = hit
-        return hit
 
     def render_many(self, attribute_sets, no_mask=False):
         """Several INDEPENDENT ``render`` calls as one: the attribute sets (same shapes) are concatenated along the batch and rendered by ONE pass
