@@ -226,25 +226,98 @@ OPT_WALK_QUEUE, OPT_WALK_BATCH = 1 << 10, 1 << 11
 OPT_MANY_IN_FLIGHT = 1 << 12          # hint: several independent calls in flight (identical results; include/mm_render.h)
 PROF_RECON = ("recon_partial", "recon_final", "recon_bwd", "recon_contour")
 
-EXPORTS = ("mm_query_workspace", "mm_render_forward", "mm_render_backward", "mm_render_status", "mm_render_fused_loss", "mm_render_step_mode", "mm_debug_step_layout", "mm_debug_workspace_layout", "mm_recon_query_workspace",
-           "mm_recon_data_forward", "mm_recon_data_backward", "mm_recon_data_totals", "mm_build_vertex_corner_csr", "mm_build_vertex_corner_csr_device", "mm_build_vertex_corner_table", "mm_nearest_neighbour", "mm_chamfer_nearest", "mm_chamfer_backward", "mm_status_string", "mm_last_error_detail",
-           "mm_mesh_reg_query_workspace", "mm_mesh_reg_forward", "mm_mesh_reg_backward", "mm_texture_flow_forward",
-           "mm_texture_flow_backward", "mm_attribute_loss_query_workspace", "mm_attribute_loss_forward",
-           "mm_attribute_loss_backward",
-           "mm_prepare_vertices_query_workspace", "mm_prepare_vertices_forward", "mm_prepare_vertices_backward",
-           "mm_face_normals_forward", "mm_face_normals_backward", "mm_dibr_query_workspace", "mm_dibr_rasterization_forward",
-           "mm_dibr_rasterization_backward", "mm_texture_mapping_forward", "mm_texture_mapping_backward", "mm_texture_mapping_backward_query_workspace", "mm_sh_lighting_forward",
-           "mm_sh_lighting_backward", "mm_mask_iou_forward", "mm_mask_iou_backward", "mm_ssim_query_workspace", "mm_ssim_forward",
-           "mm_ssim_backward", "mm_shape_features_query_workspace", "mm_shape_features_forward", "mm_shape_features_backward",
-           "mm_camera_features_query_workspace", "mm_camera_features_forward", "mm_camera_features_backward",
-           "mm_interp_query_workspace", "mm_collapse_resample", "mm_attribute_mix_forward", "mm_attribute_mix_backward",
-           "mm_render_views_query_workspace", "mm_render_views_forward", "mm_render_views_backward",
-           "mm_render_indexed_query_workspace", "mm_render_indexed_forward", "mm_render_indexed_backward",
-           "mm_critic_inputs_forward", "mm_critic_inputs_backward", "mm_export_images", "mm_export_grid", "mm_assemble_batch", "mm_composite_frames", "mm_pyramid_frames", "mm_jpeg_query_workspace", "mm_jpeg_files_offset", "mm_jpeg_encode", "mm_struct_size",
-           "mm_abi_version")
 
+P, c_z, c_int = ctypes.POINTER, ctypes.c_size_t, ctypes.c_int
 
-_STRUCT_IDS = None
+# The C ABI of include/mm_render.h, declared once: export name -> (restype, argtypes).  lib() applies it, EXPORTS is its keys, and
+# tests/test_abi_and_host.py holds every row against the header.  A stream (mm_stream_t) and a raw array are c_p.
+SIGNATURES = {
+    "mm_query_workspace": (c_z, [P(MMRenderDesc)]),
+    "mm_render_forward": (c_int, [P(MMRenderDesc), c_p]),
+    "mm_render_backward": (c_int, [P(MMRenderDesc), P(MMRenderGrads), c_p]),
+    "mm_render_status": (c_int, [P(MMRenderDesc), c_p, P(c_i)]),
+    "mm_render_fused_loss": (c_int, [P(MMRenderDesc), c_p]),
+    "mm_render_step_mode": (c_int, [P(MMRenderDesc)]),
+    "mm_debug_step_layout": (c_int, [P(MMRenderDesc), P(c_z)]),
+    "mm_debug_workspace_layout": (c_int, [P(MMRenderDesc), P(c_z)]),
+    "mm_render_views_query_workspace": (c_z, [P(MMRenderViewsDesc)]),
+    "mm_render_views_forward": (c_int, [P(MMRenderViewsDesc), c_p]),
+    "mm_render_views_backward": (c_int, [P(MMRenderViewsDesc), P(MMRenderGrads), c_p]),
+    "mm_render_indexed_query_workspace": (c_z, [P(MMRenderIndexedDesc)]),
+    "mm_render_indexed_forward": (c_int, [P(MMRenderIndexedDesc), c_p]),
+    "mm_render_indexed_backward": (c_int, [P(MMRenderIndexedDesc), P(MMRenderGrads), c_p]),
+    "mm_recon_query_workspace": (c_z, [P(MMReconDesc)]),
+    "mm_recon_data_forward": (c_int, [P(MMReconDesc), c_p]),
+    "mm_recon_data_backward": (c_int, [P(MMReconDesc), c_p]),
+    "mm_recon_data_totals": (c_p, [P(MMReconDesc)]),
+    "mm_nearest_neighbour": (c_int, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "mm_chamfer_nearest": (c_int, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "mm_chamfer_backward": (c_int, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "mm_mesh_reg_query_workspace": (c_z, [P(MMMeshRegDesc)]),
+    "mm_mesh_reg_forward": (c_int, [P(MMMeshRegDesc), c_p]),
+    "mm_mesh_reg_backward": (c_int, [P(MMMeshRegDesc), P(MMMeshRegGrads), c_p]),
+    "mm_attribute_loss_query_workspace": (c_z, [P(MMAttLossDesc)]),
+    "mm_attribute_loss_forward": (c_int, [P(MMAttLossDesc), c_p]),
+    "mm_attribute_loss_backward": (c_int, [P(MMAttLossDesc), P(MMAttLossGrads), c_p]),
+    "mm_texture_flow_forward": (c_int, [P(MMTexFlowDesc), c_p]),
+    "mm_texture_flow_backward": (c_int, [P(MMTexFlowDesc), P(MMTexFlowGrads), c_p]),
+    "mm_prepare_vertices_query_workspace": (c_z, [P(MMPrepareDesc)]),
+    "mm_prepare_vertices_forward": (c_int, [P(MMPrepareDesc), c_p]),
+    "mm_prepare_vertices_backward": (c_int, [P(MMPrepareDesc), P(MMPrepareGrads), c_p]),
+    "mm_face_normals_forward": (c_int, [ctypes.c_int64, c_i, c_p, c_p, c_p]),
+    "mm_face_normals_backward": (c_int, [ctypes.c_int64, c_i, c_p, c_p, c_p, c_p]),
+    "mm_dibr_query_workspace": (c_z, [P(MMDibrDesc)]),
+    "mm_dibr_rasterization_forward": (c_int, [P(MMDibrDesc), c_p]),
+    "mm_dibr_rasterization_backward": (c_int, [P(MMDibrDesc), P(MMDibrGrads), c_p]),
+    "mm_texture_mapping_backward_query_workspace": (c_z, [P(MMTexMapDesc)]),
+    "mm_texture_mapping_forward": (c_int, [P(MMTexMapDesc), c_p]),
+    "mm_texture_mapping_backward": (c_int, [P(MMTexMapDesc), P(MMTexMapGrads), c_p]),
+    "mm_sh_lighting_forward": (c_int, [P(MMShDesc), c_p]),
+    "mm_sh_lighting_backward": (c_int, [P(MMShDesc), P(MMShGrads), c_p]),
+    "mm_mask_iou_forward": (c_int, [P(MMMaskIouDesc), c_p]),
+    "mm_mask_iou_backward": (c_int, [P(MMMaskIouDesc), c_p, c_p, c_p, c_p]),
+    "mm_ssim_query_workspace": (c_z, [P(MMSsimDesc)]),
+    "mm_ssim_forward": (c_int, [P(MMSsimDesc), c_p]),
+    "mm_ssim_backward": (c_int, [P(MMSsimDesc), P(MMSsimGrads), c_p]),
+    "mm_shape_features_query_workspace": (c_z, [P(MMShapeFeatDesc)]),
+    "mm_shape_features_forward": (c_int, [P(MMShapeFeatDesc), c_p]),
+    "mm_shape_features_backward": (c_int, [P(MMShapeFeatDesc), P(MMShapeFeatGrads), c_p]),
+    "mm_camera_features_query_workspace": (c_z, [P(MMCameraFeatDesc)]),
+    "mm_camera_features_forward": (c_int, [P(MMCameraFeatDesc), c_p]),
+    "mm_camera_features_backward": (c_int, [P(MMCameraFeatDesc), P(MMCameraFeatGrads), c_p]),
+    "mm_interp_query_workspace": (c_z, [P(MMInterpDesc)]),
+    "mm_collapse_resample": (c_int, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p]),
+    "mm_attribute_mix_forward": (c_int, [P(MMInterpDesc), c_p]),
+    "mm_attribute_mix_backward": (c_int, [P(MMInterpDesc), P(MMInterpGrads), c_p]),
+    "mm_critic_inputs_forward": (c_int, [P(MMCriticDesc), c_p]),
+    "mm_critic_inputs_backward": (c_int, [P(MMCriticDesc), P(MMCriticGrads), c_p]),
+    "mm_export_images": (c_int, [P(MMExportDesc), c_p]),
+    "mm_export_grid": (c_int, [P(MMExportDesc), c_p]),
+    "mm_assemble_batch": (c_int, [P(MMBatchDesc), c_p]),
+    "mm_composite_frames": (c_int, [P(MMCompositeDesc), c_p]),
+    "mm_pyramid_frames": (c_int, [P(MMPyramidDesc), c_p]),
+    "mm_jpeg_query_workspace": (c_z, [P(MMJpegDesc)]),
+    "mm_jpeg_files_offset": (c_z, [P(MMJpegDesc)]),
+    "mm_jpeg_encode": (c_int, [P(MMJpegDesc), c_p]),
+    "mm_build_vertex_corner_csr": (c_int, [c_i, c_i, c_p, c_p, c_p]),
+    "mm_build_vertex_corner_csr_device": (c_int, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "mm_build_vertex_corner_table": (c_int, [c_i, c_i, c_p, c_i, c_p]),
+    "mm_status_string": (ctypes.c_char_p, [c_int]),
+    "mm_last_error_detail": (ctypes.c_char_p, []),
+    "mm_struct_size": (c_z, [c_int]),
+    "mm_abi_version": (c_int, []),
+}
+EXPORTS = tuple(SIGNATURES)
+
+# mm_struct_size's ids (include/mm_render.h, "Ids:"); 31, 34 and 36 are unassigned
+STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDesc, 4: MMMeshRegGrads, 5: MMAttLossDesc, 6: MMAttLossGrads,
+              7: MMTexFlowDesc, 8: MMTexFlowGrads, 9: MMPrepareDesc, 10: MMPrepareGrads, 11: MMDibrDesc, 12: MMDibrGrads, 13: MMTexMapDesc,
+              14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
+              21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
+              27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
+              35: MMPyramidDesc, 37: MMJpegDesc}
+
+_FN = {}          # export name -> bound function, filled by lib()
 
 
 def lib():
@@ -266,111 +339,19 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("libmm_render.so not found at %s (run __graft_entry__.build())" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    fns = {}
+    for name, (restype, argtypes) in SIGNATURES.items():
         if not hasattr(L, name):
             raise RuntimeError("libmm_render.so does not export %s" % name)
-    L.mm_query_workspace.restype = ctypes.c_size_t
-    L.mm_query_workspace.argtypes = [ctypes.POINTER(MMRenderDesc)]
-    L.mm_render_forward.argtypes = [ctypes.POINTER(MMRenderDesc), c_p]
-    L.mm_render_backward.argtypes = [ctypes.POINTER(MMRenderDesc), ctypes.POINTER(MMRenderGrads), c_p]
-    L.mm_render_fused_loss.argtypes = [ctypes.POINTER(MMRenderDesc), c_p]
-    L.mm_render_step_mode.argtypes = [ctypes.POINTER(MMRenderDesc)]
-    L.mm_debug_step_layout.argtypes = [ctypes.POINTER(MMRenderDesc), ctypes.POINTER(ctypes.c_size_t)]
-    L.mm_render_status.argtypes = [ctypes.POINTER(MMRenderDesc), c_p, ctypes.POINTER(ctypes.c_int32)]
-    L.mm_recon_query_workspace.restype = ctypes.c_size_t
-    L.mm_recon_query_workspace.argtypes = [ctypes.POINTER(MMReconDesc)]
-    L.mm_recon_data_forward.argtypes = [ctypes.POINTER(MMReconDesc), c_p]
-    L.mm_recon_data_backward.argtypes = [ctypes.POINTER(MMReconDesc), c_p]
-    L.mm_recon_data_totals.restype = c_p
-    L.mm_recon_data_totals.argtypes = [ctypes.POINTER(MMReconDesc)]
-    L.mm_nearest_neighbour.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
-    L.mm_chamfer_nearest.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
-    L.mm_chamfer_backward.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
-    L.mm_mesh_reg_query_workspace.restype = ctypes.c_size_t
-    L.mm_mesh_reg_query_workspace.argtypes = [ctypes.POINTER(MMMeshRegDesc)]
-    L.mm_mesh_reg_forward.argtypes = [ctypes.POINTER(MMMeshRegDesc), c_p]
-    L.mm_mesh_reg_backward.argtypes = [ctypes.POINTER(MMMeshRegDesc), ctypes.POINTER(MMMeshRegGrads), c_p]
-    L.mm_attribute_loss_query_workspace.restype = ctypes.c_size_t
-    L.mm_attribute_loss_query_workspace.argtypes = [ctypes.POINTER(MMAttLossDesc)]
-    L.mm_attribute_loss_forward.argtypes = [ctypes.POINTER(MMAttLossDesc), c_p]
-    L.mm_attribute_loss_backward.argtypes = [ctypes.POINTER(MMAttLossDesc), ctypes.POINTER(MMAttLossGrads), c_p]
-    L.mm_texture_flow_forward.argtypes = [ctypes.POINTER(MMTexFlowDesc), c_p]
-    L.mm_texture_flow_backward.argtypes = [ctypes.POINTER(MMTexFlowDesc), ctypes.POINTER(MMTexFlowGrads), c_p]
-    P = ctypes.POINTER
-    L.mm_prepare_vertices_query_workspace.restype = ctypes.c_size_t
-    L.mm_prepare_vertices_query_workspace.argtypes = [P(MMPrepareDesc)]
-    L.mm_prepare_vertices_forward.argtypes = [P(MMPrepareDesc), c_p]
-    L.mm_prepare_vertices_backward.argtypes = [P(MMPrepareDesc), P(MMPrepareGrads), c_p]
-    L.mm_face_normals_forward.argtypes = [ctypes.c_int64, c_i, c_p, c_p, c_p]
-    L.mm_face_normals_backward.argtypes = [ctypes.c_int64, c_i, c_p, c_p, c_p, c_p]
-    L.mm_dibr_query_workspace.restype = ctypes.c_size_t
-    L.mm_dibr_query_workspace.argtypes = [P(MMDibrDesc)]
-    L.mm_dibr_rasterization_forward.argtypes = [P(MMDibrDesc), c_p]
-    L.mm_dibr_rasterization_backward.argtypes = [P(MMDibrDesc), P(MMDibrGrads), c_p]
-    L.mm_texture_mapping_forward.argtypes = [P(MMTexMapDesc), c_p]
-    L.mm_texture_mapping_backward.argtypes = [P(MMTexMapDesc), P(MMTexMapGrads), c_p]
-    L.mm_texture_mapping_backward_query_workspace.argtypes = [P(MMTexMapDesc)]
-    L.mm_texture_mapping_backward_query_workspace.restype = ctypes.c_size_t
-    L.mm_sh_lighting_forward.argtypes = [P(MMShDesc), c_p]
-    L.mm_sh_lighting_backward.argtypes = [P(MMShDesc), P(MMShGrads), c_p]
-    L.mm_mask_iou_forward.argtypes = [P(MMMaskIouDesc), c_p]
-    L.mm_mask_iou_backward.argtypes = [P(MMMaskIouDesc), c_p, c_p, c_p, c_p]
-    L.mm_ssim_query_workspace.restype = ctypes.c_size_t
-    L.mm_ssim_query_workspace.argtypes = [P(MMSsimDesc)]
-    L.mm_ssim_forward.argtypes = [P(MMSsimDesc), c_p]
-    L.mm_ssim_backward.argtypes = [P(MMSsimDesc), P(MMSsimGrads), c_p]
-    L.mm_shape_features_query_workspace.restype = ctypes.c_size_t
-    L.mm_shape_features_query_workspace.argtypes = [P(MMShapeFeatDesc)]
-    L.mm_shape_features_forward.argtypes = [P(MMShapeFeatDesc), c_p]
-    L.mm_shape_features_backward.argtypes = [P(MMShapeFeatDesc), P(MMShapeFeatGrads), c_p]
-    L.mm_camera_features_query_workspace.restype = ctypes.c_size_t
-    L.mm_camera_features_query_workspace.argtypes = [P(MMCameraFeatDesc)]
-    L.mm_camera_features_forward.argtypes = [P(MMCameraFeatDesc), c_p]
-    L.mm_camera_features_backward.argtypes = [P(MMCameraFeatDesc), P(MMCameraFeatGrads), c_p]
-    L.mm_interp_query_workspace.restype = ctypes.c_size_t
-    L.mm_interp_query_workspace.argtypes = [P(MMInterpDesc)]
-    L.mm_collapse_resample.argtypes = [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p]
-    L.mm_attribute_mix_forward.argtypes = [P(MMInterpDesc), c_p]
-    L.mm_attribute_mix_backward.argtypes = [P(MMInterpDesc), P(MMInterpGrads), c_p]
-    L.mm_render_views_query_workspace.restype = ctypes.c_size_t
-    L.mm_render_views_query_workspace.argtypes = [P(MMRenderViewsDesc)]
-    L.mm_render_views_forward.argtypes = [P(MMRenderViewsDesc), c_p]
-    L.mm_render_views_backward.argtypes = [P(MMRenderViewsDesc), P(MMRenderGrads), c_p]
-    L.mm_render_indexed_query_workspace.restype = ctypes.c_size_t
-    L.mm_render_indexed_query_workspace.argtypes = [P(MMRenderIndexedDesc)]
-    L.mm_render_indexed_forward.argtypes = [P(MMRenderIndexedDesc), c_p]
-    L.mm_render_indexed_backward.argtypes = [P(MMRenderIndexedDesc), P(MMRenderGrads), c_p]
-    L.mm_critic_inputs_forward.argtypes = [P(MMCriticDesc), c_p]
-    L.mm_critic_inputs_backward.argtypes = [P(MMCriticDesc), P(MMCriticGrads), c_p]
-    L.mm_export_images.argtypes = [P(MMExportDesc), c_p]
-    L.mm_export_grid.argtypes = [P(MMExportDesc), c_p]
-    L.mm_assemble_batch.argtypes = [P(MMBatchDesc), c_p]
-    L.mm_composite_frames.argtypes = [P(MMCompositeDesc), c_p]
-    L.mm_pyramid_frames.argtypes = [P(MMPyramidDesc), c_p]
-    L.mm_jpeg_query_workspace.restype = ctypes.c_size_t
-    L.mm_jpeg_query_workspace.argtypes = [P(MMJpegDesc)]
-    L.mm_jpeg_files_offset.restype = ctypes.c_size_t
-    L.mm_jpeg_files_offset.argtypes = [P(MMJpegDesc)]
-    L.mm_jpeg_encode.argtypes = [P(MMJpegDesc), c_p]
-    L.mm_struct_size.restype = ctypes.c_size_t
-    L.mm_struct_size.argtypes = [ctypes.c_int]
-    L.mm_build_vertex_corner_csr.argtypes = [c_i, c_i, c_p, c_p, c_p]
-    L.mm_build_vertex_corner_csr_device.argtypes = [c_i, c_i, c_p, c_p, c_p, c_p, c_p]
-    L.mm_status_string.restype = ctypes.c_char_p
-    L.mm_status_string.argtypes = [ctypes.c_int]
-    L.mm_last_error_detail.restype = ctypes.c_char_p
-    L.mm_last_error_detail.argtypes = []
-    L.mm_abi_version.restype = ctypes.c_int
+        f = fns[name] = getattr(L, name)
+        f.restype = restype
+        f.argtypes = argtypes
     if L.mm_abi_version() != ABI_VERSION:
         raise RuntimeError("libmm_render.so has ABI version %d, this binding mirrors version %d" % (L.mm_abi_version(), ABI_VERSION))
-    mirrors = (MMRenderDesc, MMRenderGrads, MMReconDesc, MMMeshRegDesc, MMMeshRegGrads, MMAttLossDesc, MMAttLossGrads, MMTexFlowDesc,
-               MMTexFlowGrads, MMPrepareDesc, MMPrepareGrads, MMDibrDesc, MMDibrGrads, MMTexMapDesc, MMTexMapGrads, MMShDesc, MMShGrads,
-               MMMaskIouDesc, MMSsimDesc, MMSsimGrads, MMShapeFeatDesc, MMShapeFeatGrads, MMCameraFeatDesc, MMCameraFeatGrads,
-               MMInterpDesc, MMInterpGrads, MMRenderViewsDesc, MMCriticDesc, MMCriticGrads, MMExportDesc, MMBatchDesc,
-               None, MMCompositeDesc, MMRenderIndexedDesc, None, MMPyramidDesc, None, MMJpegDesc)        # (ids 31, 34 and 36 are unassigned)
-    for i, cls in enumerate(mirrors):
-        if cls is not None and L.mm_struct_size(i) != ctypes.sizeof(cls):
+    for i, cls in STRUCT_IDS.items():
+        if L.mm_struct_size(i) != ctypes.sizeof(cls):
             raise RuntimeError("struct layout mismatch for %s: library %d bytes, binding %d" % (cls.__name__, L.mm_struct_size(i), ctypes.sizeof(cls)))
+    _FN.update(fns)
     _LIB = L
     return L
 
@@ -450,6 +431,39 @@ def current_stream(device):
     if _raw_stream is not None and device.index is not None:
         return ctypes.c_void_p(_raw_stream(device.index))
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def fn(name):
+    """export ``name`` as lib() bound it (restype and argtypes from SIGNATURES); a name the table lacks raises before anything is called"""
+    f = _FN.get(name)
+    if f is None:
+        if name not in SIGNATURES:
+            raise RuntimeError("%s is not an export of libmm_render.so (see _native.SIGNATURES)" % name)
+        lib()
+        f = _FN[name]
+    return f
+
+
+def call(name, where, *args, what=None):
+    """Call export ``name`` with ``args`` followed by the stream and raise (check) on a non-zero status, labelled ``what or name``.  ``where`` is a
+    torch.device, whose current stream is taken, or a ready c_void_p stream.  A Structure goes in as itself: argtypes passes it by reference.
+
+    The one call path of every entry point that takes a stream and returns an MMStatus.  Deliberately not folded in: input_batches.py turns a
+    refusal of mm_assemble_batch into a ValueError of its own wording (it uses fn, not check); mm_render_status returns a verdict, not an
+    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
+    and diff_render.py hands fn_addr addresses to the C++ nodes."""
+    status = (_FN.get(name) or fn(name))(*args, where if type(where) is c_p else current_stream(where))
+    if status:
+        check(status, what or name)
+
+
+def workspace(query_name, desc, device, zero=False, at_least=0):
+    """A uint8 workspace of max(``query_name``(desc), at_least) bytes on ``device``, zero-filled if ``zero``; desc.workspace is set to it and
+    desc.workspace_bytes to the queried size.  The caller keeps the returned tensor alive for as long as the descriptor is used."""
+    nbytes = fn(query_name)(desc)
+    t = (torch.zeros if zero else torch.empty)(max(nbytes, at_least), device=device, dtype=torch.uint8)
+    desc.workspace, desc.workspace_bytes = t.data_ptr(), nbytes
+    return t
 
 
 def require_device(*tensors):

@@ -1,8 +1,6 @@
 """Host side of the attribute-reconstruction losses: autograd wrapper over
 ``mm_attribute_loss_forward / backward`` (csrc/mm_attloss.hip), the seven means of the reference's ``DiffRender.recon_att``
 (/root/reference/networks.py:326-362).  Device tensors only."""
-import ctypes
-
 import torch
 
 from . import _native as N
@@ -39,9 +37,8 @@ class AttLossFn(torch.autograd.Function):
         d.B, d.V, d.Ht, d.Wt, d.l1 = B, V, Ht, Wt, int(bool(l1))
         d.pred, d.target = _attributes(pred), _attributes(target)
         d.losses = N.ptr(losses)
-        ws = torch.zeros(N.lib().mm_attribute_loss_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)    # zero-filled: ABI contract
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        N.check(N.lib().mm_attribute_loss_forward(ctypes.byref(d), N.current_stream(dev)), "mm_attribute_loss_forward")
+        ws = N.workspace("mm_attribute_loss_query_workspace", d, dev, zero=True)    # zero-filled: ABI contract
+        N.call("mm_attribute_loss_forward", dev, d)
         ctx.cfg = (B, V, Ht, Wt, int(bool(l1)))
         ctx.save_for_backward(*ts, ws)
         return losses
@@ -62,7 +59,7 @@ class AttLossFn(torch.autograd.Function):
             return (None,) * 15
         w = g.detach().to(device=dev, dtype=torch.float32).contiguous()
         gr = N.MMAttLossGrads(N.ptr(w), _attributes(grads[:7]), _attributes(grads[7:]))
-        N.check(N.lib().mm_attribute_loss_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_attribute_loss_backward")
+        N.call("mm_attribute_loss_backward", dev, d, gr)
         return (None,) + tuple(grads)
 
 

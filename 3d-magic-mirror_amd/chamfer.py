@@ -21,8 +21,7 @@ def nearest_neighbour(x, y):
     m = yc.shape[1]
     dist = torch.empty((B, n), device=x.device, dtype=torch.float32)
     idx = torch.empty((B, n), device=x.device, dtype=torch.int32)
-    N.check(N.lib().mm_nearest_neighbour(B, n, m, N.ptr(xc), N.ptr(yc), N.ptr(dist), N.ptr(idx), N.current_stream(x.device)),
-            "mm_nearest_neighbour")
+    N.call("mm_nearest_neighbour", x.device, B, n, m, N.ptr(xc), N.ptr(yc), N.ptr(dist), N.ptr(idx))
     return dist, idx.long()
 
 
@@ -36,8 +35,7 @@ def _nearest_both_i32(x, y):
     idx = torch.empty((B * (n + m),), device=x.device, dtype=torch.int32)
     dx, dy = dist.view(-1)[:B * n], dist.view(-1)[B * n:]
     ix, iy = idx[:B * n], idx[B * n:]
-    N.check(N.lib().mm_chamfer_nearest(B, n, m, N.ptr(xc), N.ptr(yc), N.ptr(dx), N.ptr(ix), N.ptr(dy), N.ptr(iy), N.current_stream(x.device)),
-            "mm_chamfer_nearest")
+    N.call("mm_chamfer_nearest", x.device, B, n, m, N.ptr(xc), N.ptr(yc), N.ptr(dx), N.ptr(ix), N.ptr(dy), N.ptr(iy))
     return xc, yc, ix.view(B, n), iy.view(B, m)
 
 
@@ -65,8 +63,7 @@ class _ChamferFn(torch.autograd.Function):
         B, n, m = xc.shape[0], xc.shape[1], yc.shape[1]
         g = grad_loss.detach().reshape(1).to(device=xc.device, dtype=torch.float32).contiguous()    # (read by the kernel: no sync)
         gx, gy = torch.empty_like(xc), torch.empty_like(yc)
-        N.check(N.lib().mm_chamfer_backward(B, n, m, N.ptr(xc), N.ptr(yc), N.ptr(ix), N.ptr(iy), N.ptr(g), N.ptr(gx), N.ptr(gy),
-                                            N.current_stream(xc.device)), "mm_chamfer_backward")
+        N.call("mm_chamfer_backward", xc.device, B, n, m, N.ptr(xc), N.ptr(yc), N.ptr(ix), N.ptr(iy), N.ptr(g), N.ptr(gx), N.ptr(gy))
         return (gx.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
                 gy.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None)
 

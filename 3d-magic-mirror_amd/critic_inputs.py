@@ -13,7 +13,6 @@ With ``M`` the channel map of the ``unmask`` mode (``m = X[:, 3:4]``)
 
 every forward value is torch's eager fp32 result bit for bit.  Device tensors only."""
 import collections
-import ctypes
 
 import torch
 
@@ -62,7 +61,7 @@ class _CriticFn(torch.autograd.Function):
             gp1, gp2 = torch.empty((B, C, H, W), dtype=torch.float32, device=Xa.device), torch.empty((B, C, H, W), dtype=torch.float32, device=Xa.device)
             d.alpha_er90, d.alpha_ir, d.out_gp_er90, d.out_gp_ir = N.ptr(a1), N.ptr(a2), N.ptr(gp1), N.ptr(gp2)
         d.out_batch = N.ptr(buf)
-        N.check(N.lib().mm_critic_inputs_forward(ctypes.byref(d), N.current_stream(Xa.device)), "mm_critic_inputs_forward")
+        N.call("mm_critic_inputs_forward", Xa.device, d)
         ctx.unmask, ctx.flags = unmask, flags
         ctx.save_for_backward(*((Xer90, Xir) if unmask == 0 else ()))            # d m reads the fakes; the other modes read nothing
         ctx.meta = tuple((tuple(x.shape), tuple(x.stride())) for x in (Xer90, Xir))
@@ -85,7 +84,7 @@ class _CriticFn(torch.autograd.Function):
         gr = N.MMCriticGrads()
         gr.g_batch, gr.grad_er90, gr.grad_ir = N.ptr(g), N.ptr(grads[0]), N.ptr(grads[1])
         gr.grad_er90_nhwc, gr.grad_ir_nhwc = ctx.flags[1], ctx.flags[2]
-        N.check(N.lib().mm_critic_inputs_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(g.device)), "mm_critic_inputs_backward")
+        N.call("mm_critic_inputs_backward", g.device, d, gr)
         return None, grads[0], grads[1], None, None, None
 
 

@@ -12,7 +12,6 @@ from its non-zeros only.  ``camera_features(x, template, p_map, p_local)`` is ``
 and ``lpl`` are constants (the reference detaches the template; an ``lpl`` that requires grad is refused).  Gradients reach
 ``x`` and the pool weights, atomic-free and bitwise reproducible.  Device tensors only."""
 import collections
-import ctypes
 import weakref
 
 import torch
@@ -128,7 +127,7 @@ def _shape_forward(x, tmpl, tables, p):
     B, C = x.shape[:2]
     out = torch.empty((B, 3 * C + 3, tmpl.shape[0]), device=x.device, dtype=torch.float32)
     d = _shape_desc(x, tmpl, tables, p, out)
-    N.check(N.lib().mm_shape_features_forward(ctypes.byref(d), N.current_stream(x.device)), "mm_shape_features_forward")
+    N.call("mm_shape_features_forward", x.device, d)
     return out
 
 
@@ -149,10 +148,9 @@ class _ShapeFeatFn(torch.autograd.Function):
         gx = torch.empty(x.shape, device=dev, dtype=x.dtype) if ctx.needs_input_grad[0] else None
         gp = torch.empty(1, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         d = _shape_desc(x, tmpl, (ci, cv, ri, rv), pd)
-        ws = torch.empty(N.lib().mm_shape_features_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
+        ws = N.workspace("mm_shape_features_query_workspace", d, dev)
         gr = N.MMShapeFeatGrads(N.ptr(g), N.ptr(gx), N.ptr(gp))
-        N.check(N.lib().mm_shape_features_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_shape_features_backward")
+        N.call("mm_shape_features_backward", dev, d, gr)
         return gx, _like(gp, ctx.p_like), None, None, None, None, None
 
 
@@ -192,7 +190,7 @@ def _camera_forward(x, tmpl, pm, pl):
     B, C = x.shape[:2]
     out = torch.empty((B, 2 * C, 2, 2), device=x.device, dtype=torch.float32)
     d = _camera_desc(x, tmpl, pm, pl, out)
-    N.check(N.lib().mm_camera_features_forward(ctypes.byref(d), N.current_stream(x.device)), "mm_camera_features_forward")
+    N.call("mm_camera_features_forward", x.device, d)
     return out
 
 
@@ -215,10 +213,9 @@ class _CameraFeatFn(torch.autograd.Function):
         gpm = torch.empty(1, device=dev, dtype=torch.float32) if need[1] else None
         gpl = torch.empty(1, device=dev, dtype=torch.float32) if need[2] else None
         d = _camera_desc(x, tmpl, pm, pl)
-        ws = torch.empty(N.lib().mm_camera_features_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
+        ws = N.workspace("mm_camera_features_query_workspace", d, dev)
         gr = N.MMCameraFeatGrads(N.ptr(g), N.ptr(gx), N.ptr(gpm), N.ptr(gpl))
-        N.check(N.lib().mm_camera_features_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_camera_features_backward")
+        N.call("mm_camera_features_backward", dev, d, gr)
         return gx, _like(gpm, ctx.p_like[0]), _like(gpl, ctx.p_like[1]), None
 
 

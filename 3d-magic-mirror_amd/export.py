@@ -17,8 +17,6 @@ with its own alpha, ``x[:3] * m + (1 - m)`` with ``m = x[3:4]`` (trainer.py:755-
 ``make_grid`` is restated from torchvision [recall-risk: torchvision is not installed where this was written; the arithmetic in
 ``grid_shape`` and DESIGN.md is from memory of torchvision.utils.make_grid and has not been run against it].  Nothing here is
 differentiable.  Device tensors only."""
-import ctypes
-
 import torch
 
 from . import _native as N
@@ -88,7 +86,7 @@ def export_images(x, channels="rgb", rounding="trunc", white=False, as_float=Fal
     shapes = {"rgb": lead + ((3, H, W) if as_float else (H, W, 3)), "mask": lead + (H, W), "rgba": lead + ((4, H, W) if as_float else (H, W, 4))}
     outs = {k: torch.empty(shapes[k], dtype=dt, device=x.device) for k in channels.split("+")}
     d.out_rgb, d.out_mask, d.out_rgba = N.ptr(outs.get("rgb")), N.ptr(outs.get("mask")), N.ptr(outs.get("rgba"))
-    N.check(N.lib().mm_export_images(ctypes.byref(d), N.current_stream(x.device)), "mm_export_images")
+    N.call("mm_export_images", x.device, d)
     return (outs["rgb"], outs["mask"]) if channels == "rgb+mask" else outs[channels]
 
 
@@ -126,5 +124,5 @@ def export_grid(x, nrow=8, padding=2, pad_value=0.0, rounding="trunc", white=Fal
     d.nrow, d.padding, d.pad_value = int(nrow), int(padding), float(pad_value)
     out = torch.empty(((Nv,) if five else ()) + (Hg, Wg, 3), dtype=torch.uint8, device=x.device)
     d.out_grid = N.ptr(out)
-    N.check(N.lib().mm_export_grid(ctypes.byref(d), N.current_stream(x.device)), "mm_export_grid")
+    N.call("mm_export_grid", x.device, d)
     return out

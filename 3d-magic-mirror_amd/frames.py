@@ -166,5 +166,5 @@ def _launch(desc, fn_name, low, fg, bg, shape, H, W, rounding, as_float):
     desc.bg_pad = (ctypes.c_int32 * 4)(*low["bg_pad"])
     desc.rounding, desc.as_float = _ROUNDING[rounding], int(bool(as_float))
     desc.renders, desc.backgrounds, desc.params_host, desc.params, desc.out = N.ptr(fg), N.ptr(bg), ctypes.c_void_p(host.data_ptr()), N.ptr(dev), N.ptr(out)
-    N.check(getattr(N.lib(), fn_name)(ctypes.byref(desc), N.current_stream(fg.device)), fn_name)
+    N.call(fn_name, fg.device, desc)
     return out

@@ -217,9 +217,9 @@ def assemble_records(pool, records, out_hw, bg=False):
     d.images, d.segs, d.offsets, d.sizes = N.ptr(pool.images), N.ptr(pool.segs), N.ptr(pool.offsets_dev), N.ptr(pool.sizes_dev)
     d.records_host, d.records = ctypes.c_void_p(host.data_ptr()), N.ptr(dev)
     d.out = N.ptr(out)
-    st = N.lib().mm_assemble_batch(ctypes.byref(d), N.current_stream(pool.device))
+    st = N.fn("mm_assemble_batch")(d, N.current_stream(pool.device))          # (not N.call: a refusal is a ValueError here)
     if st in (-2, -5):
-        raise ValueError("mm_assemble_batch refused the records: %s (MMStatus %d)" % (N.lib().mm_status_string(st).decode(), st))
+        raise ValueError("mm_assemble_batch refused the records: %s (MMStatus %d)" % (N.fn("mm_status_string")(st).decode(), st))
     N.check(st, "mm_assemble_batch")
     return out
 

@@ -8,7 +8,6 @@ one launch each way (``mix_attributes``).
 ``mix_attributes`` computes ``X = a * A[X][idx_a] + (1 - a) * A[X][idx_b]`` bit for bit as torch's eager fp32 composition does; its
 backward sums every source row's terms in a fixed order, atomic-free and bitwise reproducible (for permutations of fp32 sources it
 equals torch autograd bit for bit).  Device tensors only."""
-import ctypes
 import random
 
 import numpy as np
@@ -93,7 +92,7 @@ class _MixFn(torch.autograd.Function):
         d = _desc(ctx.shapes, ia, ib, alphas)
         d.vertices, d.delta_vertices, d.textures, d.bg, d.lights = (N.ptr(t) for t in srcs)
         d.out_vertices, d.out_delta_vertices, d.out_textures, d.out_bg, d.out_lights = (N.ptr(t) for t in outs)
-        N.check(N.lib().mm_attribute_mix_forward(ctypes.byref(d), N.current_stream(vertices.device)), "mm_attribute_mix_forward")
+        N.call("mm_attribute_mix_forward", vertices.device, d)
         ctx.save_for_backward(ia, ib, *alphas)                  # the backward needs the sources' shapes only, not their data
         ctx.has_bg = bg is not None
         return tuple(o for o in outs if o is not None)
@@ -113,10 +112,9 @@ class _MixFn(torch.autograd.Function):
         if all(u is None for u in ups):
             return (None,) * 10
         d = _desc(ctx.shapes, ia, ib, (a_shape, a_texture, a_light))
-        ws = torch.empty(N.lib().mm_interp_query_workspace(ctypes.byref(d)), dtype=torch.uint8, device=ia.device)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
+        ws = N.workspace("mm_interp_query_workspace", d, ia.device)
         gr = N.MMInterpGrads(*[N.ptr(t) for t in ups + dst])
-        N.check(N.lib().mm_attribute_mix_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(ia.device)), "mm_attribute_mix_backward")
+        N.call("mm_attribute_mix_backward", ia.device, d, gr)
         return (None,) * 5 + tuple(dst)
 
 
@@ -176,8 +174,7 @@ def resample_collapsed(delta_vertices, idx_a, idx_b, uniforms, threshold=0.4):
     ia = _indices(idx_a, B, dev, "idx_a").clone()
     ib = _indices(idx_b, B, dev, "idx_b").clone()
     n_bad = torch.empty((), dtype=torch.int32, device=dev)
-    N.check(N.lib().mm_collapse_resample(B, dv.shape[1], N.ptr(dv), N.ptr(ia), N.ptr(ib), N.ptr(u), float(threshold), N.ptr(n_bad),
-                                         N.current_stream(dev)), "mm_collapse_resample")
+    N.call("mm_collapse_resample", dev, B, dv.shape[1], N.ptr(dv), N.ptr(ia), N.ptr(ib), N.ptr(u), float(threshold), N.ptr(n_bad))
     return ia, ib, n_bad
 
 

@@ -212,13 +212,12 @@ def encode_jpeg(frames, quality=100):
     d = N.MMJpegDesc()
     d.n, d.H, d.W, d.header_bytes = n, H, W, len(low["header"])
     d.frames, d.params_host, d.params = N.ptr(x), ctypes.c_void_p(host.data_ptr()), N.ptr(par)
-    ws_bytes, files_at = N.lib().mm_jpeg_query_workspace(ctypes.byref(d)), N.lib().mm_jpeg_files_offset(ctypes.byref(d))
+    ws = N.workspace("mm_jpeg_query_workspace", d, dev)
+    ws_bytes, files_at = d.workspace_bytes, N.fn("mm_jpeg_files_offset")(d)
     if (ws_bytes, files_at) != (low["workspace_bytes"](n), low["files_offset"](n)):
         raise RuntimeError("mm_jpeg_query_workspace gives %d bytes with the files at %d, lower_jpeg %d and %d"
                            % (ws_bytes, files_at, low["workspace_bytes"](n), low["files_offset"](n)))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    d.workspace, d.workspace_bytes = N.ptr(ws), ws_bytes
-    N.check(N.lib().mm_jpeg_encode(ctypes.byref(d), N.current_stream(dev)), "mm_jpeg_encode")
+    N.call("mm_jpeg_encode", dev, d)
     off_host = torch.empty((n + 1,), dtype=torch.int64, pin_memory=True)
     off_host.copy_(ws[:8 * (n + 1)].view(torch.int64))                     # copy 1 (blocking): the offsets
     off = off_host.tolist()

@@ -1,8 +1,6 @@
 """Host side of the mesh regularisers: static template tables and the autograd wrapper over
 ``mm_mesh_reg_forward / backward`` (csrc/mm_reg.hip).  Replaces what /root/reference/networks.py:392-491 computes with ~60
 small torch launches per attribute set by one launch per direction.  No CPU path: device tensors only."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -79,9 +77,8 @@ class MeshRegFn(torch.autograd.Function):
         tab = dr._reg_tables(dev)
         losses = torch.empty(NTERMS, device=dev, dtype=torch.float32)
         d = _desc(dr, tab, terms, temp, eps, vertices, delta, fn, losses, None)
-        ws = torch.zeros(N.lib().mm_mesh_reg_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)   # zero-filled: ABI contract
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        N.check(N.lib().mm_mesh_reg_forward(ctypes.byref(d), N.current_stream(dev)), "mm_mesh_reg_forward")
+        ws = N.workspace("mm_mesh_reg_query_workspace", d, dev, zero=True)   # zero-filled: ABI contract
+        N.call("mm_mesh_reg_forward", dev, d)
         ctx.dr, ctx.cfg = dr, (terms, temp, eps)
         ctx.has = (vertices is not None, delta is not None, fn is not None)
         ctx.save_for_backward(*[t if t is not None else torch.empty(0, device=dev) for t in (vertices, delta, fn)], ws)
@@ -104,7 +101,7 @@ class MeshRegFn(torch.autograd.Function):
         if gv is None and gd is None and gf is None:
             return (None,) * 7
         gr = N.MMMeshRegGrads(N.ptr(w), N.ptr(gv), N.ptr(gd), N.ptr(gf))
-        N.check(N.lib().mm_mesh_reg_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_mesh_reg_backward")
+        N.call("mm_mesh_reg_backward", dev, d, gr)
         return None, None, None, None, gv, gd, gf
 
 

@@ -9,8 +9,6 @@ for device memory, the current stream and autograd plumbing (``cat`` / ``split``
 one-time template preparation (``index_vertices_by_faces`` on the static uv table, ``uniform_laplacian``, ``import_mesh``)
 is torch/numpy indexing exactly as in kaolin itself.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -98,8 +96,7 @@ def _faces_tables(faces, V, dev):
     off = torch.empty(V + 1, device=dev, dtype=torch.int32)
     items = torch.empty(3 * F, device=dev, dtype=torch.int32)
     if V <= _CSR_MAX_V:
-        N.check(N.lib().mm_build_vertex_corner_csr_device(V, F, N.ptr(fi), N.ptr(off), N.ptr(items), _status_word(dev).data_ptr(), N.current_stream(dev)),
-                "mm_build_vertex_corner_csr_device")
+        N.call("mm_build_vertex_corner_csr_device", dev, V, F, N.ptr(fi), N.ptr(off), N.ptr(items), _status_word(dev).data_ptr())
     else:                                                        # (huge clouds: the host builder, with its read-back)
         fh = faces.detach().to("cpu", torch.int64)
         if fh.numel() and (int(fh.max()) >= V or int(fh.min()) < 0):
@@ -126,7 +123,7 @@ class _PrepareFn(torch.autograd.Function):
         d.faces, d.vc_offsets, d.vc_items = N.ptr(faces_i32), N.ptr(vc_off), N.ptr(vc_items)
         d.vertices, d.transform = N.ptr(vertices), N.ptr(transform)
         d.face_vertices_camera, d.face_vertices_image, d.face_normals = N.ptr(fvc), N.ptr(fvi), N.ptr(fn)
-        N.check(N.lib().mm_prepare_vertices_forward(ctypes.byref(d), N.current_stream(dev)), "mm_prepare_vertices_forward")
+        N.call("mm_prepare_vertices_forward", dev, d)
         ctx.save_for_backward(vertices, transform, faces_i32, vc_off, vc_items, proj)
         return fvc, fvi, fn
 
@@ -145,10 +142,9 @@ class _PrepareFn(torch.autograd.Function):
         d.vertices, d.transform = N.ptr(vertices), N.ptr(transform)
         gv = torch.empty_like(vertices)
         gT = torch.empty_like(transform) if ctx.needs_input_grad[1] else None
-        ws = torch.empty(N.lib().mm_prepare_vertices_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
+        ws = N.workspace("mm_prepare_vertices_query_workspace", d, dev)
         g = N.MMPrepareGrads(N.ptr(g_fvc), N.ptr(g_fvi), N.ptr(g_fn), N.ptr(gv), N.ptr(gT))
-        N.check(N.lib().mm_prepare_vertices_backward(ctypes.byref(d), ctypes.byref(g), N.current_stream(dev)), "mm_prepare_vertices_backward")
+        N.call("mm_prepare_vertices_backward", dev, d, g)
         return gv, gT, None, None, None, None
 
 
@@ -188,7 +184,7 @@ class _FaceNormalsFn(torch.autograd.Function):
         fv = _f32(fv, dev)
         out = torch.empty(fv.shape[:-2] + (3,), device=dev, dtype=torch.float32)
         n = fv.numel() // 9
-        N.check(N.lib().mm_face_normals_forward(n, int(unit), N.ptr(fv), N.ptr(out), N.current_stream(dev)), "mm_face_normals_forward")
+        N.call("mm_face_normals_forward", dev, n, int(unit), N.ptr(fv), N.ptr(out))
         ctx.save_for_backward(fv)
         ctx.unit = int(unit)
         return out
@@ -198,8 +194,7 @@ class _FaceNormalsFn(torch.autograd.Function):
         (fv,) = ctx.saved_tensors
         g = g.to(torch.float32).contiguous()
         gfv = torch.empty_like(fv)
-        N.check(N.lib().mm_face_normals_backward(fv.numel() // 9, ctx.unit, N.ptr(fv), N.ptr(g), N.ptr(gfv), N.current_stream(fv.device)),
-                "mm_face_normals_backward")
+        N.call("mm_face_normals_backward", fv.device, fv.numel() // 9, ctx.unit, N.ptr(fv), N.ptr(g), N.ptr(gfv))
         return gfv, None
 
 
@@ -227,9 +222,8 @@ class _DibrFn(torch.autograd.Function):
         d.sigmainv, d.boxlen, d.multiplier, d.eps = float(sigmainv), float(boxlen), float(multiplier), float(eps)
         d.face_vertices_z, d.face_vertices_image, d.face_features, d.face_normals_z = N.ptr(fz), N.ptr(fvi), N.ptr(feats), N.ptr(fnz)
         d.interpolated_features, d.soft_mask, d.face_idx = N.ptr(interp), N.ptr(soft), N.ptr(fidx)
-        ws = torch.empty(N.lib().mm_dibr_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = N.ptr(ws), ws.numel()
-        N.check(N.lib().mm_dibr_rasterization_forward(ctypes.byref(d), N.current_stream(dev)), "mm_dibr_rasterization_forward")
+        ws = N.workspace("mm_dibr_query_workspace", d, dev)
+        N.call("mm_dibr_rasterization_forward", dev, d)
         ctx.save_for_backward(fz, fvi, feats, fnz, ws)
         ctx.cfg = (H, W, int(knum), float(sigmainv), float(boxlen), float(multiplier), float(eps))
         ctx.mark_non_differentiable(fidx)
@@ -251,7 +245,7 @@ class _DibrFn(torch.autograd.Function):
         gfvi = torch.empty_like(fvi)
         gfeat = torch.empty_like(feats) if ctx.needs_input_grad[4] else None
         g = N.MMDibrGrads(N.ptr(g_interp), N.ptr(g_soft), N.ptr(gfvi), N.ptr(gfeat))
-        N.check(N.lib().mm_dibr_rasterization_backward(ctypes.byref(d), ctypes.byref(g), N.current_stream(dev)), "mm_dibr_rasterization_backward")
+        N.call("mm_dibr_rasterization_backward", dev, d, g)
         return None, None, None, gfvi, gfeat, None, None, None, None, None, None
 
 
@@ -293,7 +287,7 @@ class _TexMapFn(torch.autograd.Function):
         n = uv.shape[1]
         out = torch.empty((B, n, C), device=dev, dtype=torch.float32)
         d = N.MMTexMapDesc(B, n, C, Ht, Wt, mode, N.ptr(uv), N.ptr(tex), N.ptr(out))
-        N.check(N.lib().mm_texture_mapping_forward(ctypes.byref(d), N.current_stream(dev)), "mm_texture_mapping_forward")
+        N.call("mm_texture_mapping_forward", dev, d)
         ctx.save_for_backward(uv, tex)
         ctx.mode = mode
         return out
@@ -311,9 +305,9 @@ class _TexMapFn(torch.autograd.Function):
         d = N.MMTexMapDesc(B, uv.shape[1], C, Ht, Wt, ctx.mode, N.ptr(uv), N.ptr(tex), None)
         ws = None
         if gtex is not None:                                     # 64-bit fixed-point scatter: a bitwise reproducible texture gradient
-            ws = torch.empty(N.lib().mm_texture_mapping_backward_query_workspace(ctypes.byref(d)), device=dev, dtype=torch.uint8)
+            ws = torch.empty(N.fn("mm_texture_mapping_backward_query_workspace")(d), device=dev, dtype=torch.uint8)     # (it lives in the grads struct)
         gr = N.MMTexMapGrads(N.ptr(g), N.ptr(guv), N.ptr(gtex), N.ptr(ws), 0 if ws is None else ws.numel())
-        N.check(N.lib().mm_texture_mapping_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_texture_mapping_backward")
+        N.call("mm_texture_mapping_backward", dev, d, gr)
         return guv, gtex, None
 
 
@@ -345,7 +339,7 @@ class _ShFn(torch.autograd.Function):
         B, n = nrm.shape[:2]
         out = torch.empty((B, n), device=dev, dtype=torch.float32)
         d = N.MMShDesc(B, n, N.ptr(nrm), N.ptr(lights), N.ptr(out))
-        N.check(N.lib().mm_sh_lighting_forward(ctypes.byref(d), N.current_stream(dev)), "mm_sh_lighting_forward")
+        N.call("mm_sh_lighting_forward", dev, d)
         ctx.save_for_backward(nrm, lights)
         return out
 
@@ -360,7 +354,7 @@ class _ShFn(torch.autograd.Function):
             return None, None
         d = N.MMShDesc(nrm.shape[0], nrm.shape[1], N.ptr(nrm), N.ptr(lights), None)
         gr = N.MMShGrads(N.ptr(g), N.ptr(gn), N.ptr(gl))
-        N.check(N.lib().mm_sh_lighting_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_sh_lighting_backward")
+        N.call("mm_sh_lighting_backward", dev, d, gr)
         return gn, gl
 
 
@@ -384,7 +378,7 @@ class _MaskIouFn(torch.autograd.Function):
         sums = torch.empty((B, 2), device=dev, dtype=torch.float32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
         d = N.MMMaskIouDesc(B, lhs.numel() // B, N.ptr(lhs), N.ptr(rhs), N.ptr(sums), N.ptr(loss))
-        N.check(N.lib().mm_mask_iou_forward(ctypes.byref(d), N.current_stream(dev)), "mm_mask_iou_forward")
+        N.call("mm_mask_iou_forward", dev, d)
         ctx.save_for_backward(lhs, rhs, sums)
         return loss
 
@@ -399,7 +393,7 @@ class _MaskIouFn(torch.autograd.Function):
         if gl is None and gr is None:
             return None, None
         d = N.MMMaskIouDesc(B, lhs.numel() // B, N.ptr(lhs), N.ptr(rhs), N.ptr(sums), None)
-        N.check(N.lib().mm_mask_iou_backward(ctypes.byref(d), N.ptr(g), N.ptr(gl), N.ptr(gr), N.current_stream(dev)), "mm_mask_iou_backward")
+        N.call("mm_mask_iou_backward", dev, d, N.ptr(g), N.ptr(gl), N.ptr(gr))
         return gl, gr
 
 

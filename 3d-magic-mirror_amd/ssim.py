@@ -22,7 +22,6 @@ Inputs are fp32 (N,C,H,W) with any strides (``ssim(rgbs[:, :3], gt[:, :3])`` on 
 Host tensors are moved to the current HIP device and the result comes back on the host, as in ``ops.mask_iou``.  fp16 / bf16 and 5-D
 (volumetric) inputs are refused.  ``ms_ssim`` is composed here from the SSIM op (which also returns cs) and ``F.avg_pool2d``.
 """
-import ctypes
 import functools
 import warnings
 
@@ -73,10 +72,8 @@ class _SsimFn(torch.autograd.Function):
             d.mean_c = red.data_ptr()
         else:
             d.mean_all = red.data_ptr()
-        nbytes = N.lib().mm_ssim_query_workspace(ctypes.byref(d))
-        ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
-        N.check(N.lib().mm_ssim_forward(ctypes.byref(d), N.current_stream(dev)), "mm_ssim_forward")
+        ws = N.workspace("mm_ssim_query_workspace", d, dev, at_least=1)       # (at least a byte: a zero-byte query must not pass NULL)
+        N.call("mm_ssim_forward", dev, d)
         ctx.desc = d
         ctx.nonneg, ctx.mean_c = nonneg, mean_c
         ctx.set_materialize_grads(False)
@@ -101,13 +98,11 @@ class _SsimFn(torch.autograd.Function):
         g_s = None if g_s is None else g_s.to(dtype=torch.float32).contiguous()
         g_cs = None if g_cs is None else g_cs.to(dtype=torch.float32).contiguous()
         d = ctx.desc
-        nbytes = N.lib().mm_ssim_query_workspace(ctypes.byref(d))
-        ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+        ws = N.workspace("mm_ssim_query_workspace", d, dev, at_least=1)
         gx = torch.empty(X.shape, device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         gy = torch.empty(Y.shape, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         g = N.MMSsimGrads(N.ptr(g_s), N.ptr(g_cs), N.ptr(gx), N.ptr(gy))
-        N.check(N.lib().mm_ssim_backward(ctypes.byref(d), ctypes.byref(g), N.current_stream(dev)), "mm_ssim_backward")
+        N.call("mm_ssim_backward", dev, d, g)
         return gx, gy, None, None, None, None, None
 
 
@@ -258,6 +253,6 @@ def recon_scores(pred, gt):
         sums = torch.empty((B, 2), device=pred.device, dtype=torch.float32)
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         d = N.MMMaskIouDesc(B, lhs.numel() // B, N.ptr(lhs), N.ptr(rhs), N.ptr(sums), N.ptr(loss))
-        N.check(N.lib().mm_mask_iou_forward(ctypes.byref(d), N.current_stream(pred.device)), "mm_mask_iou_forward")
+        N.call("mm_mask_iou_forward", pred.device, d)
         iou = sums[:, 0] / (sums[:, 1] + 1e-10)
     return s.to(out_dev), iou.to(out_dev)

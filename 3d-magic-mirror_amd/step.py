@@ -79,8 +79,7 @@ class RenderLossStep:
         # loss_scale: dL/dloss, e.g. B_rank/B_global when several steps share one batch mean
         self.loss_scale = None if loss_scale is None else torch.full((), float(loss_scale), device=dev)
         r.loss, r.grad_loss, r.grad_pred = N.ptr(self.loss), N.ptr(self.loss_scale), N.ptr(self.grad_rgba)
-        self.rws = torch.empty(N.lib().mm_recon_query_workspace(ctypes.byref(r)), device=dev, dtype=torch.uint8)
-        r.workspace, r.workspace_bytes = N.ptr(self.rws), self.rws.numel()
+        self.rws = N.workspace("mm_recon_query_workspace", r, dev)
         self.r = r
         # fused mode: recon_data folded into the render kernels (MMRenderDesc.fused_*): two ABI calls per step.  Its contour term folds in for
         # image sizes that are multiples of 4 (MMRenderDesc.fused_contour); other sizes with contour > 0 keep the three recon_data launches.
@@ -130,33 +129,31 @@ class RenderLossStep:
 
     def run(self, stream=None):
         """Enqueue one full step on ``stream`` (a torch.cuda.Stream; default: the current stream)."""
-        L = N.lib()
         s = self._stream(stream)
-        N.check(L.mm_render_forward(ctypes.byref(self.d), s), "mm_render_forward")
+        N.call("mm_render_forward", s, self.d)
         if not self.fused:
-            N.check(L.mm_recon_data_forward(ctypes.byref(self.r), s), "mm_recon_data_forward")
-            N.check(L.mm_recon_data_backward(ctypes.byref(self.r), s), "mm_recon_data_backward")
-        N.check(L.mm_render_backward(ctypes.byref(self.d), ctypes.byref(self.g), s), "mm_render_backward")
+            N.call("mm_recon_data_forward", s, self.r)
+            N.call("mm_recon_data_backward", s, self.r)
+        N.call("mm_render_backward", s, self.d, self.g)
 
     def run_deferred(self, stream=None):
         """The un-fused step with DEFERRED fusion (MMRenderDesc.fused_totals, ABI 6): render, recon_data's forward on the image, then ONE backward
         call that forms dL/d image itself from recon_data's per-image totals -- no mm_recon_data_backward, no grad_rgba round trip, the same bits."""
         if self.fused or self.r.contour > 0:
             raise RuntimeError("run_deferred is the un-fused step without the contour term")
-        L = N.lib()
         s = self._stream(stream)
-        N.check(L.mm_render_forward(ctypes.byref(self.d), s), "mm_render_forward")
-        N.check(L.mm_recon_data_forward(ctypes.byref(self.r), s), "mm_recon_data_forward")
+        N.call("mm_render_forward", s, self.d)
+        N.call("mm_recon_data_forward", s, self.r)
         d = self.render_desc()
         d.fused_gt, d.fused_image_weight, d.fused_grad_loss = N.ptr(self.gt), float(self.dr.image_weight), N.ptr(self.loss_scale)
         d.fused_totals = self.recon_totals_ptr()
         g = self.grads_struct()
         g.grad_rgba = None
-        N.check(L.mm_render_backward(ctypes.byref(d), ctypes.byref(g), s), "mm_render_backward (deferred)")
+        N.call("mm_render_backward", s, d, g, what="mm_render_backward (deferred)")
 
     def step_mode_taken(self):
         """True if the library runs this step in step mode (mm_render_step_mode: the field is set AND the shape is covered)."""
-        return bool(N.lib().mm_render_step_mode(ctypes.byref(self.d)))
+        return bool(N.fn("mm_render_step_mode")(self.d))
 
     def render_desc(self):
         """a copy of this step's MMRenderDesc (tests poke at the copy)"""
@@ -166,29 +163,27 @@ class RenderLossStep:
         return N.MMRenderGrads.from_buffer_copy(self.g)
 
     def recon_totals_ptr(self):
-        return N.lib().mm_recon_data_totals(ctypes.byref(self.r))
+        return N.fn("mm_recon_data_totals")(self.r)
 
     def run_forward(self, stream=None):
         """The forward half of run() (fused mode): render + recon_data value, on ``stream``."""
-        L = N.lib()
         s = self._stream(stream)
-        N.check(L.mm_render_forward(ctypes.byref(self.d), s), "mm_render_forward")
+        N.call("mm_render_forward", s, self.d)
         if self.fused:
-            N.check(L.mm_render_fused_loss(ctypes.byref(self.d), s), "mm_render_fused_loss")
+            N.call("mm_render_fused_loss", s, self.d)
         else:
-            N.check(L.mm_recon_data_forward(ctypes.byref(self.r), s), "mm_recon_data_forward")
+            N.call("mm_recon_data_forward", s, self.r)
 
     def run_backward(self, stream=None):
-        L = N.lib()
         s = self._stream(stream)
         if not self.fused:
-            N.check(L.mm_recon_data_backward(ctypes.byref(self.r), s), "mm_recon_data_backward")
-        N.check(L.mm_render_backward(ctypes.byref(self.d), ctypes.byref(self.g), s), "mm_render_backward")
+            N.call("mm_recon_data_backward", s, self.r)
+        N.call("mm_render_backward", s, self.d, self.g)
 
     def dropped_records(self, stream=None):
         """Per-image counts of texture-gradient records the last backward had no room for (mm_render_status; synchronises)."""
         out = (ctypes.c_int32 * self.d.B)()
-        N.lib().mm_render_status(ctypes.byref(self.d), self._stream(stream), out)
+        N.fn("mm_render_status")(self.d, self._stream(stream), out)          # (a verdict, not an error: the counts are the answer)
         return list(out)
 
     def capture(self):

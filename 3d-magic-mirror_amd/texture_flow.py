@@ -3,8 +3,6 @@
 ``sample_texture(img, texture_flow)`` is the tail of the reference's ``TextureEncoder.forward``
 (/root/reference/network/model_res.py:597-612 with makeup == 0): bicubic ``grid_sample(align_corners=True)`` of the input image
 at the decoder's flow, then the vertical mirror that makes the back of the texture equal to its front.  Device tensors only."""
-import ctypes
-
 import torch
 
 from . import _native as N
@@ -23,7 +21,7 @@ class _TexFlowFn(torch.autograd.Function):
         Ho, Wo = flow.shape[2:]
         out = torch.empty((B, C, 2 * Ho, Wo), device=dev, dtype=torch.float32)
         d = N.MMTexFlowDesc(B, C, H, W, Ho, Wo, N.ptr(img), N.ptr(flow), N.ptr(out))
-        N.check(N.lib().mm_texture_flow_forward(ctypes.byref(d), N.current_stream(dev)), "mm_texture_flow_forward")
+        N.call("mm_texture_flow_forward", dev, d)
         ctx.save_for_backward(img, flow)
         return out
 
@@ -38,7 +36,7 @@ class _TexFlowFn(torch.autograd.Function):
         g_img = torch.empty_like(img) if ctx.needs_input_grad[0] else None
         d = N.MMTexFlowDesc(B, C, H, W, Ho, Wo, N.ptr(img), N.ptr(flow), None)
         gr = N.MMTexFlowGrads(N.ptr(g), N.ptr(g_flow), N.ptr(g_img))
-        N.check(N.lib().mm_texture_flow_backward(ctypes.byref(d), ctypes.byref(gr), N.current_stream(dev)), "mm_texture_flow_backward")
+        N.call("mm_texture_flow_backward", dev, d, gr)
         return g_img, g_flow
 
 

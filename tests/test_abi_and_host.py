@@ -62,6 +62,71 @@ def test_library_exports_every_declared_symbol(pkg):
     assert lib.mm_face_normals_forward(0, 1, None, None, None) == -1
 
 
+def test_signature_table_is_the_headers(pkg):
+    """N.SIGNATURES, the binding's one declaration of the C ABI, against every function include/mm_render.h declares: the same names, as many
+    argtypes as parameters, the restype of the return type, POINTER(mirror) wherever a descriptor goes in -- and the loaded library carries it."""
+    N = pkg._native
+    hdr = open(os.path.join(ROOT, "include", "mm_render.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    decls = re.findall(r"^(int|size_t|const char\*|const float\*)\s+(mm_\w+)\s*\((.*?)\)\s*;", code, flags=re.M | re.S)
+    assert len(decls) == len({name for _, name, _ in decls}) >= 74
+    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p, "const float*": ctypes.c_void_p}
+    lib = N.lib()
+    for ret, name, params in decls:
+        assert name in N.SIGNATURES, name
+        restype, argtypes = N.SIGNATURES[name]
+        params = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+        assert len(argtypes) == len(params), (name, params)
+        assert restype is restypes[ret], name
+        for k, p in enumerate(params):
+            m = re.fullmatch(r"const (MM\w+)\* \w+", p)
+            if m:
+                assert argtypes[k] is ctypes.POINTER(getattr(N, m.group(1))), (name, p)
+        f = getattr(lib, name)
+        assert f.restype is restype and list(f.argtypes) == list(argtypes), name
+    assert set(N.SIGNATURES) == {name for _, name, _ in decls}
+    assert N.EXPORTS == tuple(N.SIGNATURES)
+
+
+def test_struct_ids_are_the_headers(pkg):
+    """N.STRUCT_IDS, what lib() holds against mm_struct_size, is the header's "Ids:" list; the unassigned ids are absent, not padded."""
+    N = pkg._native
+    hdr = open(os.path.join(ROOT, "include", "mm_render.h")).read()
+    ids = re.search(r"Ids: (.*?)\. \*/", hdr, flags=re.S).group(1).replace("\n", " ").replace("*", " ")
+    table = {int(m.group(1)): getattr(N, m.group(2)) for m in re.finditer(r"(\d+) (MM\w+)", ids)}
+    assert len(table) >= 35 and N.STRUCT_IDS == table
+    assert not {31, 34, 36} & set(N.STRUCT_IDS)
+    assert not hasattr(N, "_STRUCT_IDS")
+
+
+def test_call_path_raises_with_the_entry_points_name(pkg):
+    """N.call: the status of a refusal becomes check's RuntimeError under the export's name (or ``what``), an unknown name raises before anything
+    is called, and a Python int where a pointer belongs is an ArgumentError instead of a truncated address -- for every export, the two
+    debug/host helpers that once had no argtypes included.  The all-zero descriptor is refused by the shape check before any launch."""
+    N = pkg._native
+    null = ctypes.c_void_p(0)
+    with pytest.raises(RuntimeError) as e:
+        N.call("mm_ssim_forward", null, N.MMSsimDesc())
+    assert str(e.value) == "mm_ssim_forward failed: bad or inconsistent size (MMStatus -2)"
+    with pytest.raises(RuntimeError) as e:
+        N.call("mm_ssim_forward", null, N.MMSsimDesc(), what="label")
+    assert str(e.value) == "label failed: bad or inconsistent size (MMStatus -2)"
+    with pytest.raises(RuntimeError, match="mm_no_such_entry is not an export"):
+        N.call("mm_no_such_entry", null, N.MMSsimDesc())
+    addr = ctypes.addressof(N.MMSsimDesc())
+    with pytest.raises(ctypes.ArgumentError):
+        N.call("mm_ssim_forward", null, addr)
+    out = (ctypes.c_size_t * 16)()
+    with pytest.raises(ctypes.ArgumentError):
+        N.fn("mm_debug_workspace_layout")(addr, out)
+    with pytest.raises(ctypes.ArgumentError):
+        N.fn("mm_debug_workspace_layout")(N.MMRenderDesc(), ctypes.addressof(out))
+    with pytest.raises(ctypes.ArgumentError):
+        N.fn("mm_build_vertex_corner_table")(4, 2, None, 0.5, None)                  # (its stride is an int32, not whatever came)
+    assert N.fn("mm_debug_workspace_layout")(None, out) == -1                        # typed, it still answers: MM_ERR_NULL_POINTER
+    assert N.fn("mm_last_error_detail")().decode() == ""                              # nothing was launched
+
+
 def test_option_bits_of_the_binding_are_the_headers(pkg):
     """Every MM_OPT_* bit include/mm_render.h declares has its OPT_* twin in the ctypes binding with the same value, and no two share a bit."""
     hdr = open(os.path.join(ROOT, "include", "mm_render.h")).read()
