@@ -10,7 +10,7 @@ from .critic_inputs import CriticInputs, critic_inputs  # noqa: F401
 from .export import export_grid, export_images, grid_shape  # noqa: F401
 from .composite import composite_frames, gaussian_taps, lower_composite, resize_taps  # noqa: F401
 from .pyramid import lower_pyramid, pyramid_frames  # noqa: F401
-from .jpeg import JpegBatch, encode_jpeg, lower_jpeg  # noqa: F401
+from .jpeg import JpegBatch, encode_jpeg, jpeg_roundtrip, lower_jpeg  # noqa: F401
 from .input_batches import ImagePool, assemble_batch, assemble_records, draw_augmentation, lower_batch  # noqa: F401
 from .interpolate import interpolate_attributes, mix_attributes, resample_collapsed  # noqa: F401
-from .ssim import MS_SSIM, SSIM, ms_ssim, recon_scores, ssim  # noqa: F401
+from .ssim import MS_SSIM, SSIM, ms_ssim, recon_scores, recon_scores_as_saved, ssim  # noqa: F401

@@ -217,6 +217,14 @@ class MMJpegDesc(ctypes.Structure):
                 ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+JPEG_MODE_RGB, JPEG_MODE_L = 0, 1     # MM_JPEG_MODE_*
+
+
+class MMJpegRoundtripDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("mode", c_i), ("as_float", c_i), ("reserved", c_i), ("frames", c_p), ("coef", c_p),
+                ("params_host", c_p), ("params", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -299,6 +307,9 @@ SIGNATURES = {
     "mm_jpeg_query_workspace": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_files_offset": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_encode": (c_int, [P(MMJpegDesc), c_p]),
+    "mm_jpeg_coef_offset": (c_z, [P(MMJpegDesc)]),
+    "mm_jpeg_roundtrip_query_workspace": (c_z, [P(MMJpegRoundtripDesc)]),
+    "mm_jpeg_roundtrip": (c_int, [P(MMJpegRoundtripDesc), c_p]),
     "mm_build_vertex_corner_csr": (c_int, [c_i, c_i, c_p, c_p, c_p]),
     "mm_build_vertex_corner_csr_device": (c_int, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mm_build_vertex_corner_table": (c_int, [c_i, c_i, c_p, c_i, c_p]),
@@ -315,7 +326,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
-              35: MMPyramidDesc, 37: MMJpegDesc}
+              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 
@@ -450,7 +461,7 @@ def call(name, where, *args, what=None):
 
     The one call path of every entry point that takes a stream and returns an MMStatus.  Deliberately not folded in: input_batches.py turns a
     refusal of mm_assemble_batch into a ValueError of its own wording (it uses fn, not check); mm_render_status returns a verdict, not an
-    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
+    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_jpeg_coef_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
     and diff_render.py hands fn_addr addresses to the C++ nodes."""
     status = (_FN.get(name) or fn(name))(*args, where if type(where) is c_p else current_stream(where))
     if status:

@@ -63,6 +63,9 @@ int launch_pyramid(const MMPyramidDesc*, hipStream_t);
 size_t jpeg_workspace_bytes(const MMJpegDesc*);
 size_t jpeg_files_at(const MMJpegDesc*);
 int launch_jpeg(const MMJpegDesc*, hipStream_t);
+size_t jpeg_coef_at(const MMJpegDesc*);
+size_t jpeg_roundtrip_workspace_bytes(const MMJpegRoundtripDesc*);
+int launch_jpeg_roundtrip(const MMJpegRoundtripDesc*, hipStream_t);
 }  // namespace mm
 
 static bool sizes_positive(const MMRenderDesc* d) { return d->B > 0 && d->H > 0 && d->W > 0 && d->V > 0 && d->F > 0 && d->Ht > 0 && d->Wt > 0; }
@@ -860,6 +863,36 @@ int mm_jpeg_encode(const MMJpegDesc* d, mm_stream_t stream) {
     return mm::launch_jpeg(d, (hipStream_t)stream);
 }
 
+size_t mm_jpeg_coef_offset(const MMJpegDesc* d) {
+    return check_jpeg_shape(d) == MM_OK ? mm::jpeg_coef_at(d) : 0;
+}
+
+// the sizes a round trip may have: the encoder's, in both modes
+static int check_jpeg_roundtrip_shape(const MMJpegRoundtripDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->mode != MM_JPEG_MODE_RGB && d->mode != MM_JPEG_MODE_L) return MM_ERR_BAD_SHAPE;
+    MMJpegDesc e = {};
+    e.n = d->n; e.H = d->H; e.W = d->W; e.header_bytes = 2;
+    return check_jpeg_shape(&e);
+}
+
+size_t mm_jpeg_roundtrip_query_workspace(const MMJpegRoundtripDesc* d) {
+    return check_jpeg_roundtrip_shape(d) == MM_OK ? mm::jpeg_roundtrip_workspace_bytes(d) : 0;
+}
+
+int mm_jpeg_roundtrip(const MMJpegRoundtripDesc* d, mm_stream_t stream) {
+    const int shape = check_jpeg_roundtrip_shape(d);
+    if (shape != MM_OK) return shape;
+    const bool rgb = d->mode == MM_JPEG_MODE_RGB;
+    if (!d->params_host || !d->params || !d->out || (!d->frames && !(rgb && d->coef)) || (rgb && !d->workspace)) return MM_ERR_NULL_POINTER;
+    if (rgb && (d->workspace_bytes < mm::jpeg_roundtrip_workspace_bytes(d) || ((uintptr_t)d->workspace & 15) || ((uintptr_t)d->coef & 15))) return MM_ERR_WORKSPACE;
+    if ((uintptr_t)d->out & 3) return MM_ERR_WORKSPACE;
+    for (int i = 0; i < 128; ++i)                                 // the divisors: 8 * q, q in 1..255 (baseline)
+        if (d->params_host[i] < 8 || d->params_host[i] > 8 * 255 || (d->params_host[i] & 7)) return MM_ERR_BAD_SHAPE;
+    mm::clear_stale_error();
+    return mm::launch_jpeg_roundtrip(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -933,7 +966,7 @@ size_t mm_struct_size(int which) {
         case 27: return sizeof(MMCriticDesc);   case 28: return sizeof(MMCriticGrads);  case 29: return sizeof(MMExportDesc);
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
-        case 37: return sizeof(MMJpegDesc);                                                     // (36: unassigned)
+        case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
         default: return 0;
     }
 }

@@ -35,9 +35,11 @@
 // A stream is never assumed to fit LDS (256 x 256 noise at quality 100 is 130 KB): it lives in the workspace, MM_JPEG_BLOCK_BYTES = 208 per
 // block (a block codes to 20 + 63 * 26 bits at most), and a file's room is header + twice that + 2.  No floating point, no scratch; every
 // byte is a pure function of the frame (bitwise reproducible).
+// The round trip (mm_jpeg_roundtrip: the frames as the decoder reads those files back) is below the encoder's kernels, with its own header.
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_quant.h"                                         // unquant: the v / 255 of as_float, shared with the exports
 
 #define MM_JPG_BLOCK 256
 #define MM_JPG_BLOCK_WORDS (MM_JPEG_BLOCK_BYTES / 4)
@@ -409,7 +411,271 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_write_kernel(JpegArgs a) {
     if (nb && byte0 + nb == len) { p[0] = 0xFF; p[1] = 0xD9; }
 }
 
+// ==== the round trip: frames as Image.open(file).convert('RGB' / 'L') reads them back ==========================================================
+// What libjpeg's decoder makes of the file the encoder above writes, without the file: the file's content is the quantised coefficients, and
+// from there the decoder is integer arithmetic (>> is arithmetic), held to Pillow with no tolerance:
+//   dequantise  c[k] * table[k], table = divisor / 8: the luma table for Y and for greyscale, the chroma table for Cb and Cr
+//   IDCT        jidctint's islow: CONST_BITS 13, PASS1_BITS 2, COLUMNS first with DESCALE(x, 11), then rows with DESCALE(x, 18),
+//               DESCALE(x, n) = (x + (1 << (n - 1))) >> n; per pass over i0..i7
+//                 even  z1 = (i2 + i6) * 4433, t2 = z1 - i6 * 15137, t3 = z1 + i2 * 6270, t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13,
+//                       t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+//                 odd   a0..a3 = i7, i5, i3, i1; z1 = a0 + a3, z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3, z5 = (z3 + z4) * 9633,
+//                       a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299, z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5,
+//                       z4 = z4 * -3196 + z5, a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4
+//                 out   0..3 = t10 + a3, t11 + a2, t12 + a1, t13 + a0; 4..7 = t13 - a0, t12 - a1, t11 - a2, t10 - a3
+//               then + 128 and clamp to 0..255.  The clamp SATURATES, as libjpeg-turbo's SIMD code does; libjpeg's C range table wraps
+//               outside -384..639, which no input of the tests reaches (the host restatement counts it).
+//   colour      Y is cropped to H x W.  Cb and Cr are real on hd = ceil(H / 2) rows by wd = ceil(W / 2) columns; the row above row 0 is row
+//               0 and the row below row hd - 1 is row hd - 1, the last REAL downsampled row, not the padded IDCT output below it.
+//               wd > 2, h2v2 fancy upsampling: input row r makes output rows 2r (neighbour: the row above) and 2r + 1 (the row below);
+//                 s[x] = 3 * c[r][x] + c[neighbour][x]; out[2x] = (3 s[x] + s[x-1] + 8) >> 4; out[2x+1] = (3 s[x] + s[x+1] + 7) >> 4;
+//                 at the row's ends s[-1] := s[0] and s[wd] := s[wd-1].
+//               wd <= 2 (W <= 4): plain 2 x 2 replication -- libjpeg picks the plain upsampler for so narrow a component.
+//               With cb and cr minus 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+//               B = Y + ((116130 cb + 32768) >> 16), each clamped to 0..255.
+//   greyscale   one component, 8 x 8 blocks in raster order; columns beyond W replicate the last column, rows beyond H the last row; samples
+//               minus 128 through the encoder's jfdctint and quantiser (d = 8 * luma table, half away from zero), then dequantise, IDCT,
+//               clamp and crop.  A block stays in registers and LDS from load to store: no greyscale file is ever formed.
+// The colour path reads the int16 zigzag blocks jpeg_transform_kernel wrote, from memory -- its own pass's, or those in mm_jpeg_encode's
+// workspace -- so the decoded frames cannot drift from the files.  Dummy luma blocks lie wholly outside the image and are never read.
+//   idct      eight lanes per block: the block comes from memory into LDS, lane c dequantises column c and runs the column pass, the block
+//             is transposed through LDS, lane r runs the row pass and stores row r as 8 bytes into the padded sample planes in the workspace
+//             (Y 16my x 16mx, Cb and Cr 8my x 8mx per frame: 1.5 bytes per pixel).
+//   pixels    one lane per dword of the (n,H,W,3) output (two pixels at most, across rows and frames alike: the output is one dense run
+//             of bytes from an aligned start), or one lane per pixel of the fp32 planes: upsample, convert, store.
+// No floating point but the final v / 255 of as_float, no atomics, no scratch; every output byte is a pure function of the frame.
+struct JpegDecArgs {
+    const short* coef; const int* par;
+    unsigned char* yp; unsigned char* cp;                     // the sample planes: Y (n, 16my, 16mx); Cb and Cr (n, 2, 8my, 8mx)
+    const unsigned char* grey;                                // mode L: the input (n,H,W)
+    void* out;
+    int n, H, W, as_float;
+    int my, mx, blocks;
+    int bh, bw, hd, wd;                                       // luma (grey) blocks down and across that hold pixels; real chroma rows and columns
+    long long total_blocks, total_pixels;
+};
+
+// one pass of jidctint over eight values, descaled by N bits
+template <int N>
+__device__ inline void jpeg_idct8(const int (&i)[8], int (&o)[8]) {
+    constexpr int R = 1 << (N - 1);
+    int z1 = (i[2] + i[6]) * 4433;
+    const int t2 = z1 - i[6] * 15137, t3 = z1 + i[2] * 6270;
+    const int t0 = (i[0] + i[4]) * (1 << 13), t1 = (i[0] - i[4]) * (1 << 13);
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    int a0 = i[7], a1 = i[5], a2 = i[3], a3 = i[1];
+    z1 = a0 + a3;
+    int z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const int z5 = (z3 + z4) * 9633;
+    a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299;
+    z1 *= -7373; z2 *= -20995;
+    z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+    o[0] = (t10 + a3 + R) >> N; o[7] = (t10 - a3 + R) >> N;
+    o[1] = (t11 + a2 + R) >> N; o[6] = (t11 - a2 + R) >> N;
+    o[2] = (t12 + a1 + R) >> N; o[5] = (t12 - a1 + R) >> N;
+    o[3] = (t13 + a0 + R) >> N; o[4] = (t13 - a0 + R) >> N;
+}
+
+// a row after the row pass: + 128, clamped, as eight bytes in two words (byte c of the row at bits 8 * (c % 4) of word c / 4)
+__device__ inline uint2 jpeg_row_bytes(const int (&o)[8]) {
+    unsigned w[2] = {0u, 0u};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) w[c >> 2] |= (unsigned)min(max(o[c] + 128, 0), 255) << (8 * (c & 3));
+    return make_uint2(w[0], w[1]);
+}
+
+// lane r (of the eight of block lb) holds column r after the column pass in o: the transpose, the row pass, row r as bytes.
+// Every lane of the workgroup calls it; tile may still be read from before.
+__device__ inline uint2 jpeg_idct_rows(int (*tile)[65], int lb, int r, int (&o)[8]) {
+    int d[8];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) tile[lb][k * 8 + r] = o[k];
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 8; ++c) d[c] = tile[lb][r * 8 + c];
+    jpeg_idct8<18>(d, o);
+    return jpeg_row_bytes(o);
+}
+
+// ---- idct: coefficients -> the sample planes ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_idct_kernel(JpegDecArgs a) {
+    __shared__ int tile[MM_JPG_BLOCK / 8][65];
+    __shared__ __attribute__((aligned(16))) short zz[MM_JPG_BLOCK / 8][64];
+    const int tid = threadIdx.x, lb = tid >> 3, r = tid & 7;
+    const long long g = (long long)blockIdx.x * (MM_JPG_BLOCK / 8) + lb;
+    const long long gc = g < a.total_blocks ? g : 0;
+    const int img = (int)(gc / a.blocks), rem = (int)(gc % a.blocks);
+    const int mcu = rem / 6, j = rem % 6, my = mcu / a.mx, mx = mcu % a.mx;
+    const int by = 2 * my + (j >> 1), bx = 2 * mx + (j & 1);    // (luma)
+    const bool skip = g >= a.total_blocks || (j < 4 && (by >= a.bh || bx >= a.bw));         // a dummy holds no pixel: never read
+    if (!skip) *(uint4*)&zz[lb][r * 8] = *(const uint4*)(a.coef + (size_t)g * 64 + r * 8);
+    __syncthreads();
+    const int* div = a.par + MM_JPG_DIV + (j < 4 ? 0 : 64);
+    int d[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int nat = k * 8 + r;
+        d[k] = skip ? 0 : (int)zz[lb][jpeg_zigzag_pos[nat]] * (div[nat] >> 3);
+    }
+    jpeg_idct8<11>(d, o);
+    const uint2 row = jpeg_idct_rows(tile, lb, r, o);
+    if (skip) return;
+    if (j < 4) {
+        const size_t yw = (size_t)a.mx * 16;
+        *(uint2*)(a.yp + ((size_t)img * a.my * 16 + by * 8 + r) * yw + bx * 8) = row;
+    } else {
+        const size_t cw = (size_t)a.mx * 8;
+        *(uint2*)(a.cp + (((size_t)img * 2 + (j - 4)) * a.my * 8 + my * 8 + r) * cw + mx * 8) = row;
+    }
+}
+
+// ---- pixels: upsample, convert, store -----------------------------------------------------------------------------------------------
+// the upsampled chroma sample at (y, x) of one component's plane c (cw bytes a row)
+__device__ inline int jpeg_upsampled(const JpegDecArgs& a, const unsigned char* c, size_t cw, int y, int x) {
+    const int r = y >> 1, cx = x >> 1;
+    const unsigned char* p = c + r * cw;
+    if (a.wd <= 2) return p[cx];
+    const unsigned char* q = c + ((y & 1) ? min(r + 1, a.hd - 1) : max(r - 1, 0)) * cw;
+    const int ox = (x & 1) ? min(cx + 1, a.wd - 1) : max(cx - 1, 0);
+    const int s = 3 * p[cx] + q[cx], so = 3 * p[ox] + q[ox];
+    return (3 * s + so + ((x & 1) ? 7 : 8)) >> 4;
+}
+// pixel p of the output, over all frames: R | G << 8 | B << 16
+__device__ inline unsigned jpeg_pixel(const JpegDecArgs& a, long long p, int& img, int& y, int& x) {
+    const int hw = a.H * a.W;
+    img = (int)(p / hw);
+    const int rem = (int)(p % hw);
+    y = rem / a.W; x = rem % a.W;
+    const size_t cw = (size_t)a.mx * 8, cplane = (size_t)a.my * 8 * cw;
+    const int Y = a.yp[((size_t)img * a.my * 16 + y) * (cw * 2) + x];
+    const unsigned char* c = a.cp + (size_t)img * 2 * cplane;
+    const int cb = jpeg_upsampled(a, c, cw, y, x) - 128, cr = jpeg_upsampled(a, c + cplane, cw, y, x) - 128;
+    const int R = min(max(Y + ((91881 * cr + 32768) >> 16), 0), 255);
+    const int G = min(max(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
+    const int B = min(max(Y + ((116130 * cb + 32768) >> 16), 0), 255);
+    return (unsigned)R | (unsigned)G << 8 | (unsigned)B << 16;
+}
+
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_pixels_u8_kernel(JpegDecArgs a) {
+    const long long i = (long long)blockIdx.x * MM_JPG_BLOCK + threadIdx.x, byte0 = 4 * i, bytes = 3 * a.total_pixels;
+    if (byte0 >= bytes) return;
+    const long long p = byte0 / 3;
+    int img, y, x;
+    unsigned long long seq = jpeg_pixel(a, p, img, y, x);      // the six bytes of pixels p and p + 1
+    if (p + 1 < a.total_pixels) seq |= (unsigned long long)jpeg_pixel(a, p + 1, img, y, x) << 24;
+    const unsigned w = (unsigned)(seq >> (8 * (int)(byte0 - 3 * p)));
+    unsigned char* out = (unsigned char*)a.out + byte0;
+    if (byte0 + 4 <= bytes) *(unsigned*)out = w;
+    else for (int k = 0; k < (int)(bytes - byte0); ++k) out[k] = (unsigned char)(w >> (8 * k));
+}
+
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_pixels_f32_kernel(JpegDecArgs a) {
+    const long long p = (long long)blockIdx.x * MM_JPG_BLOCK + threadIdx.x;
+    if (p >= a.total_pixels) return;
+    int img, y, x;
+    const unsigned q = jpeg_pixel(a, p, img, y, x);
+    const size_t hw = (size_t)a.H * a.W;
+    float* o = (float*)a.out + (size_t)img * 3 * hw + (size_t)y * a.W + x;
+    o[0] = unquant(q & 255u); o[hw] = unquant((q >> 8) & 255u); o[2 * hw] = unquant(q >> 16);
+}
+
+// ---- grey: a mask through the encoder's transform and the decoder's, block by block ------------------------------------------------------
+__global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_grey_kernel(JpegDecArgs a) {
+    __shared__ int tile[MM_JPG_BLOCK / 8][65];
+    const int tid = threadIdx.x, lb = tid >> 3, r = tid & 7;
+    const long long g = (long long)blockIdx.x * (MM_JPG_BLOCK / 8) + lb;      // the block, over all frames, raster order in a frame
+    const bool live = g < a.total_blocks;
+    const long long gc = live ? g : 0;
+    const int per = a.bh * a.bw, img = (int)(gc / per), rem = (int)(gc % per), by = rem / a.bw, bx = rem % a.bw;
+    const size_t hw = (size_t)a.H * a.W;
+    const unsigned char* f = a.grey + (size_t)img * hw + (size_t)min(by * 8 + r, a.H - 1) * a.W;
+    int d[8], o[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) d[c] = (int)f[min(bx * 8 + c, a.W - 1)] - 128;
+    jpeg_fdct8<true>(d, o);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) tile[lb][r * 8 + c] = o[c];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = tile[lb][k * 8 + r];   // lane r now has column r
+    jpeg_fdct8<false>(d, o);
+    const int* div = a.par + MM_JPG_DIV;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {                             // quantise as the encoder does, dequantise as the decoder does
+        const unsigned dv = (unsigned)div[k * 8 + r];
+        const int m = (int)(((unsigned)abs(o[k]) + (dv >> 1)) / dv) * (int)(dv >> 3);
+        d[k] = o[k] < 0 ? -m : m;
+    }
+    jpeg_idct8<11>(d, o);
+    const uint2 row = jpeg_idct_rows(tile, lb, r, o);
+    const int y = by * 8 + r, x0 = bx * 8;
+    if (!live || y >= a.H) return;
+    const int nx = min(8, a.W - x0);
+    const unsigned w[2] = {row.x, row.y};
+    const size_t at = (size_t)img * hw + (size_t)y * a.W + x0;
+    if (a.as_float) {
+        for (int c = 0; c < nx; ++c) ((float*)a.out)[at + c] = unquant((w[c >> 2] >> (8 * (c & 3))) & 255u);
+    } else if (nx == 8 && (a.W & 3) == 0) {                  // rows of a multiple of four bytes: every block's row is two aligned words
+        *(uint2*)((unsigned char*)a.out + at) = row;
+    } else {
+        for (int c = 0; c < nx; ++c) ((unsigned char*)a.out)[at + c] = (unsigned char)(w[c >> 2] >> (8 * (c & 3)));
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------
+struct JpegRoundtripLayout { size_t coef, yp, cp, bytes; };
+__host__ JpegRoundtripLayout jpeg_roundtrip_layout(const MMJpegRoundtripDesc* d) {
+    JpegRoundtripLayout l = {0, 0, 0, 256};                   // mode L needs no workspace; the query still answers 256, so that 0 stays its refusal
+    if (d->mode != MM_JPEG_MODE_RGB) return l;
+    const size_t n = (size_t)d->n, mcus = (size_t)((d->H + 15) / 16) * ((d->W + 15) / 16);
+    l.yp = l.coef + (d->coef ? 0 : jpeg_up(n * mcus * 6 * 128));
+    l.cp = l.yp + jpeg_up(n * mcus * 256);
+    l.bytes = l.cp + jpeg_up(n * mcus * 128);
+    return l;
+}
+size_t jpeg_roundtrip_workspace_bytes(const MMJpegRoundtripDesc* d) { return jpeg_roundtrip_layout(d).bytes; }
+size_t jpeg_coef_at(const MMJpegDesc* d) { return jpeg_layout(d).coef; }
+
+int launch_jpeg_roundtrip(const MMJpegRoundtripDesc* d, hipStream_t s) {
+    const dim3 wg(MM_JPG_BLOCK);
+    JpegDecArgs a = {};
+    a.par = d->params; a.out = d->out;
+    a.n = d->n; a.H = d->H; a.W = d->W; a.as_float = d->as_float;
+    a.bh = (d->H + 7) / 8; a.bw = (d->W + 7) / 8;
+    a.total_pixels = (long long)d->n * d->H * d->W;
+    if (d->mode != MM_JPEG_MODE_RGB) {
+        a.grey = d->frames;
+        a.total_blocks = (long long)d->n * a.bh * a.bw;
+        hipLaunchKernelGGL(jpeg_grey_kernel, dim3((unsigned)((a.total_blocks + MM_JPG_BLOCK / 8 - 1) / (MM_JPG_BLOCK / 8))), wg, 0, s, a);
+        return launch_ok("jpeg_roundtrip");
+    }
+    const JpegRoundtripLayout l = jpeg_roundtrip_layout(d);
+    unsigned char* ws = (unsigned char*)d->workspace;
+    a.my = (d->H + 15) / 16; a.mx = (d->W + 15) / 16; a.blocks = a.my * a.mx * 6;
+    a.hd = (d->H + 1) / 2; a.wd = (d->W + 1) / 2;
+    a.total_blocks = (long long)d->n * a.blocks;
+    a.yp = ws + l.yp; a.cp = ws + l.cp;
+    const dim3 per_eight((unsigned)((a.total_blocks + MM_JPG_BLOCK / 8 - 1) / (MM_JPG_BLOCK / 8)));
+    if (d->coef) {
+        a.coef = d->coef;
+    } else {                                                  // the encoder's transform, as it stands
+        JpegArgs e = {};
+        e.frames = d->frames; e.par = d->params; e.coef = (short*)(ws + l.coef);
+        e.n = d->n; e.H = d->H; e.W = d->W;
+        e.my = a.my; e.mx = a.mx; e.blocks = a.blocks;
+        e.bh = a.bh; e.bw = a.bw; e.ch = a.hd;
+        e.total_blocks = a.total_blocks;
+        hipLaunchKernelGGL(jpeg_transform_kernel, per_eight, wg, 0, s, e);
+        a.coef = e.coef;
+    }
+    hipLaunchKernelGGL(jpeg_idct_kernel, per_eight, wg, 0, s, a);
+    if (d->as_float) hipLaunchKernelGGL(jpeg_pixels_f32_kernel, dim3((unsigned)((a.total_pixels + MM_JPG_BLOCK - 1) / MM_JPG_BLOCK)), wg, 0, s, a);
+    else hipLaunchKernelGGL(jpeg_pixels_u8_kernel, dim3((unsigned)((3 * a.total_pixels + 4 * MM_JPG_BLOCK - 1) / (4 * MM_JPG_BLOCK))), wg, 0, s, a);
+    return launch_ok("jpeg_roundtrip");
+}
+
 int launch_jpeg(const MMJpegDesc* d, hipStream_t s) {
     const JpegLayout l = jpeg_layout(d);
     unsigned char* ws = (unsigned char*)d->workspace;

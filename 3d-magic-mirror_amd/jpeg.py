@@ -11,8 +11,13 @@ baseline, 4:2:0, the standard Huffman tables, libjpeg's quality scaling.  libjpe
 order is in DESIGN.md and in the kernel's header.  The host makes the tables and the header (``lower_jpeg``); everything after SOS is
 made on the device.
 
-Out of scope: 4:4:4 and 4:2:2 subsampling, greyscale, ``optimize=True``, progressive, restart markers, EXIF / ICC, decoding, writing to
-disk beyond ``JpegBatch.write``.  Device tensors only."""
+``jpeg_roundtrip`` is the other half of what the evaluation does: the frames as ``Image.open(file).convert('RGB')`` (and, for a mask,
+``.convert('L')`` of its greyscale file) reads them back, to the byte, from the coefficients the encoder's transform leaves in memory --
+host side of ``mm_jpeg_roundtrip``.
+
+Out of scope: 4:4:4 and 4:2:2 subsampling, greyscale files, ``optimize=True``, progressive, restart markers, EXIF / ICC, writing to
+disk beyond ``JpegBatch.write``.  The round trip of our own frames is ``jpeg_roundtrip``; decoding arbitrary files (an entropy decoder)
+stays out of scope.  Device tensors only."""
 import ctypes
 import functools
 
@@ -100,8 +105,9 @@ def lower_jpeg(H, W, quality=100):
     huffman (4,256) int32; header, the bytes up to and including SOS; mcu_rows, mcu_cols, blocks (six per MCU); stream_capacity, the bytes
     kept for one frame's entropy-coded data before stuffing (208 per block, in whole 1024-byte chunks); file_capacity, the most one file
     takes (header + twice that + EOI); ``params``, all of it packed as MMJpegDesc.params wants it (int32 words; the header's bytes in
-    file order, padded to a word); and ``workspace_bytes(n)`` / ``files_offset(n)``, what n frames need and where their files start in it:
-    mm_jpeg_query_workspace and mm_jpeg_files_offset in Python.
+    file order, padded to a word); and ``workspace_bytes(n)`` / ``files_offset(n)`` / ``coef_offset(n)``, what n frames need and where their
+    files and coefficients start in it: mm_jpeg_query_workspace, mm_jpeg_files_offset and mm_jpeg_coef_offset in Python;
+    ``roundtrip_workspace_bytes(n, mode="RGB", own_coef=True)``: mm_jpeg_roundtrip_query_workspace in Python.
     The dict is cached and shared between calls: read, not written.  ValueError for what the kernel refuses."""
     H, W = int(H), int(W)
     if H < 1 or W < 1 or H > 65535 or W > 65535:
@@ -125,6 +131,10 @@ def lower_jpeg(H, W, quality=100):
 
     # offsets (n + 1) int64 | the files | coefficients (int16 x 64 per block) | bits per block | bits per frame | the unstuffed streams | 0xFF per chunk
     low["files_offset"] = lambda n: up((n + 1) * 8)
+    low["coef_offset"] = lambda n: up((n + 1) * 8) + up(n * low["file_capacity"])
+    # mm_jpeg_roundtrip's: coefficients (unless it decodes mm_jpeg_encode's) | Y planes, 256 bytes per MCU | Cb and Cr planes, 128; mode L uses none
+    low["roundtrip_workspace_bytes"] = lambda n, mode="RGB", own_coef=True: (
+        256 if mode == "L" else (up(n * blocks * 128) if own_coef else 0) + up(n * my * mx * 256) + up(n * my * mx * 128))
     low["workspace_bytes"] = lambda n: (up((n + 1) * 8) + up(n * low["file_capacity"]) + up(n * blocks * 128) + up(n * blocks * 4) + up(n * 4)
                                         + up(n * chunks * CHUNK_BYTES) + up(n * chunks * 4))
     return low
@@ -206,21 +216,111 @@ def encode_jpeg(frames, quality=100):
     n, H, W = check_frames(frames, quality)
     low = lower_jpeg(H, W, int(quality))
     N.require_device(frames)
-    x = frames.detach().contiguous()
-    dev = x.device
-    host, par = low["params"], _resident_params(dev, H, W, int(quality))
+    return _collect(_launch_encode(frames.detach().contiguous(), n, low), n, low, frames.shape[:-3])
+
+
+def _launch_encode(x, n, low, with_coef=False):
+    """``mm_jpeg_encode`` of the dense frames x on the current stream, nothing copied yet: the workspace that holds the results.
+    with_coef: the caller goes on to read the coefficients in it, so where they lie is held to ``lower_jpeg`` as well"""
+    dev, H, W = x.device, low["H"], low["W"]
+    host, par = low["params"], _resident_params(dev, H, W, low["quality"])
     d = N.MMJpegDesc()
     d.n, d.H, d.W, d.header_bytes = n, H, W, len(low["header"])
     d.frames, d.params_host, d.params = N.ptr(x), ctypes.c_void_p(host.data_ptr()), N.ptr(par)
     ws = N.workspace("mm_jpeg_query_workspace", d, dev)
-    ws_bytes, files_at = d.workspace_bytes, N.fn("mm_jpeg_files_offset")(d)
-    if (ws_bytes, files_at) != (low["workspace_bytes"](n), low["files_offset"](n)):
-        raise RuntimeError("mm_jpeg_query_workspace gives %d bytes with the files at %d, lower_jpeg %d and %d"
-                           % (ws_bytes, files_at, low["workspace_bytes"](n), low["files_offset"](n)))
+    got = (d.workspace_bytes, N.fn("mm_jpeg_files_offset")(d)) + ((N.fn("mm_jpeg_coef_offset")(d),) if with_coef else ())
+    want = (low["workspace_bytes"](n), low["files_offset"](n)) + ((low["coef_offset"](n),) if with_coef else ())
+    if got != want:
+        raise RuntimeError("mm_jpeg_query_workspace gives %s (bytes, where the files start%s), lower_jpeg %s"
+                           % (got, ", where the coefficients do" if with_coef else "", want))
     N.call("mm_jpeg_encode", dev, d)
+    return ws
+
+
+def _collect(ws, n, low, lead):
+    """the files out of ``mm_jpeg_encode``'s workspace: a ``JpegBatch`` after two blocking copies"""
+    files_at = low["files_offset"](n)
     off_host = torch.empty((n + 1,), dtype=torch.int64, pin_memory=True)
     off_host.copy_(ws[:8 * (n + 1)].view(torch.int64))                     # copy 1 (blocking): the offsets
     off = off_host.tolist()
     buf = torch.empty((off[-1],), dtype=torch.uint8, pin_memory=True)
     buf.copy_(ws[files_at:files_at + off[-1]])                            # copy 2 (blocking): exactly the bytes used
-    return JpegBatch(buf, off, frames.shape[:-3])
+    return JpegBatch(buf, off, lead)
+
+
+MODES = {"RGB": N.JPEG_MODE_RGB, "L": N.JPEG_MODE_L}
+
+
+def check_roundtrip(frames, quality, mode, files):
+    """the argument errors of ``jpeg_roundtrip``, before anything touches a device: (n, H, W).  Mode "RGB" has ``encode_jpeg``'s
+    (``check_frames``); mode "L" the same for (...,H,W)."""
+    if mode not in MODES:
+        raise ValueError("mode must be 'RGB' or 'L', got %r" % (mode,))
+    if mode == "RGB":
+        return check_frames(frames, quality)
+    if files:
+        raise ValueError("files=True needs mode 'RGB': greyscale files are out of scope (the round trip of a mask forms no file)")
+    if not torch.is_tensor(frames):
+        raise ValueError("frames must be a uint8 tensor (...,H,W), got %s" % type(frames))
+    if frames.dtype != torch.uint8:
+        raise ValueError("frames must be uint8 (...,H,W), got %s: export_images(x, 'mask') makes 8-bit masks from float renders" % frames.dtype)
+    if frames.dim() < 2:
+        raise ValueError("frames must have shape (...,H,W), got %s" % (tuple(frames.shape),))
+    if min(frames.shape) < 1:
+        raise ValueError("an empty batch: frames of shape %s" % (tuple(frames.shape),))
+    if int(np.prod(frames.shape[:-2], dtype=np.int64)) > MAX_FRAMES:
+        raise ValueError("at most %d frames in a call, got shape %s" % (MAX_FRAMES, tuple(frames.shape)))
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or quality < 1 or quality > 100:
+        raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
+    H, W = frames.shape[-2:]
+    return int(np.prod(frames.shape[:-2], dtype=np.int64)), int(H), int(W)
+
+
+def jpeg_roundtrip(frames, quality=100, mode="RGB", as_float=False, files=False):
+    """Frames as the evaluation reads them back from disk: to the byte, what ``Image.open(file)`` gives for the JPEG file
+    ``Image.fromarray(f).save(file, 'JPEG', quality=quality)`` writes of every frame f -- the reference scores these, never the renders
+    (trainer.py:697-795, test.py:302-455).  No file is parsed: a file's content is its quantised coefficients, and libjpeg's decoder is
+    integer arithmetic from there (dequantise, the islow inverse DCT, "fancy" chroma upsampling, fixed-point YCbCr -> RGB; DESIGN.md and
+    csrc/mm_jpeg.hip have the order and the edge rules).
+
+    frames       mode "RGB": device uint8 (...,H,W,3), ``encode_jpeg``'s input with its validation; the result is ``.convert('RGB')`` of the
+                 4:2:0 colour file, uint8 (...,H,W,3).  Mode "L": device uint8 (...,H,W), a mask as ``export_images(x, "mask")`` leaves it;
+                 the result is the reopened greyscale file (``Image.fromarray(m).save(...)`` of a 2-D array; ``.convert('L')`` of it is its
+                 samples), uint8 (...,H,W).  That file is never formed; ``encode_jpeg`` still refuses greyscale.
+    quality      int in 1..100
+    as_float     the same values as float32 ``v / 255`` in planes, (...,3,H,W) or (...,H,W): ``to_tensor`` of the reopened image, ready for
+                 ``ssim`` / ``recon_scores_as_saved``; the convention of ``export_images(as_float=True)``
+    files        mode "RGB" only: return ``(decoded, JpegBatch)`` from ONE transform pass; the batch is ``encode_jpeg(frames, quality)``
+                 byte for byte and the decoded frames come from the very coefficients those files carry
+
+    The outputs are fresh device tensors, frames is left unmodified, leading dimensions are kept, and nothing synchronises -- unless
+    files=True, where ``encode_jpeg``'s two copies happen.  The clamp after the inverse DCT saturates, as libjpeg-turbo's SIMD code does;
+    libjpeg's plain C table wraps for samples outside -384..639, which a frame that was itself 8-bit before the forward transform does not
+    produce at any quality the tests reach (tests/test_jpeg_roundtrip_host.py counts it).  ValueError: as ``encode_jpeg``, an unknown mode,
+    files=True with mode "L".
+
+        rgb, mask = export_images(pred, "rgb+mask")                       # was: per image save(name, 'JPEG', quality=100), then
+        rec = jpeg_roundtrip(rgb, as_float=True)                          #      to_tensor(Image.open(name).convert('RGB'))
+        rec_mask = jpeg_roundtrip(mask, mode="L", as_float=True)          #      to_tensor(Image.open(mask_name).convert('L'))"""
+    n, H, W = check_roundtrip(frames, quality, mode, files)
+    low = lower_jpeg(H, W, int(quality))
+    N.require_device(frames)
+    x = frames.detach().contiguous()
+    dev, rgb = x.device, mode == "RGB"
+    lead = tuple(frames.shape[:-3] if rgb else frames.shape[:-2])
+    shape = lead + (((3, H, W) if as_float else (H, W, 3)) if rgb else (H, W))
+    out = torch.empty(shape, dtype=torch.float32 if as_float else torch.uint8, device=dev)
+    d = N.MMJpegRoundtripDesc()
+    d.n, d.H, d.W, d.mode, d.as_float = n, H, W, MODES[mode], int(bool(as_float))
+    d.frames, d.params_host, d.params, d.out = N.ptr(x), ctypes.c_void_p(low["params"].data_ptr()), N.ptr(_resident_params(dev, H, W, int(quality))), N.ptr(out)
+    enc = None
+    if files:
+        enc = _launch_encode(x, n, low, with_coef=True)
+        d.coef = enc.data_ptr() + low["coef_offset"](n)
+    ws = N.workspace("mm_jpeg_roundtrip_query_workspace", d, dev)
+    want = low["roundtrip_workspace_bytes"](n, mode, own_coef=not files)
+    if d.workspace_bytes != want:
+        raise RuntimeError("mm_jpeg_roundtrip_query_workspace gives %d bytes, lower_jpeg %d" % (d.workspace_bytes, want))
+    N.call("mm_jpeg_roundtrip", dev, d)
+    del ws                                                               # (the allocator keeps it for the stream until the kernels are through)
+    return (out, _collect(enc, n, low, lead)) if files else out

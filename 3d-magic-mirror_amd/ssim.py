@@ -1,5 +1,5 @@
 """pytorch_msssim's ``ssim`` / ``ms_ssim`` / ``SSIM`` / ``MS_SSIM`` on the MI355X kernels (csrc/mm_ssim.hip behind ``mm_ssim_*``), and
-``recon_scores``, the reference's two evaluation numbers for a whole batch.
+``recon_scores`` / ``recon_scores_as_saved``, the reference's two evaluation numbers for a whole batch (of the tensors / of their saved JPEG files).
 
 The reference scores every test reconstruction with ``pytorch_msssim.ssim(ori, rec, data_range=1)`` (trainer.py:771-795, 911-935;
 test.py:428-457) and imports the package at module top (trainer.py:38, test.py:34).  Names, argument order and defaults here are
@@ -235,24 +235,53 @@ class MS_SSIM(torch.nn.Module):
         return ms_ssim(X, Y, data_range=self.data_range, size_average=self.size_average, win=self.win, weights=self.weights, K=self.K)
 
 
+def _mask_iou_rows(lhs, rhs):
+    """sum(l*r) / (sum(l+r-l*r) + 1e-10) per image of two dense fp32 (B,H,W) device masks: the kernel of ``ops.mask_iou``"""
+    B = lhs.shape[0]
+    sums = torch.empty((B, 2), device=lhs.device, dtype=torch.float32)
+    loss = torch.empty((), device=lhs.device, dtype=torch.float32)
+    d = N.MMMaskIouDesc(B, lhs.numel() // B, N.ptr(lhs), N.ptr(rhs), N.ptr(sums), N.ptr(loss))
+    N.call("mm_mask_iou_forward", lhs.device, d)
+    return sums[:, 0] / (sums[:, 1] + 1e-10)
+
+
 def recon_scores(pred, gt):
     """The reference's two evaluation numbers (trainer.py:771-795) for a whole batch: (B,4,H,W) fp32 pred and gt (RGB + mask) ->
     (ssim (B,), mask_iou (B,)): ``ssim`` over channels 0-2 with data_range=1, ``mask_iou`` = sum(l*r) / (sum(l+r-l*r) + 1e-10) over
     channel 3 (the same kernel as ``ops.mask_iou``; ``1 - mask_iou`` of one image is that function's value).
 
     The reference's loop scores images it has written to JPEG/PNG files and read back through a PIL resize; this helper scores the
-    tensors themselves, so its values are not identical to the loop's."""
+    tensors themselves, so its values are not identical to the loop's.  ``recon_scores_as_saved`` scores what comes back from the files."""
     if pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 4:
         raise ValueError("recon_scores expects two (B,4,H,W) tensors, got %s / %s" % (tuple(pred.shape), tuple(gt.shape)))
     pred, gt, out_dev = _on_device(pred, gt)
     with torch.no_grad():
         s = ssim(pred[:, :3], gt[:, :3], data_range=1, size_average=False)
-        B = pred.shape[0]
-        lhs = gt[:, 3].to(torch.float32).contiguous()
-        rhs = pred[:, 3].to(torch.float32).contiguous()
-        sums = torch.empty((B, 2), device=pred.device, dtype=torch.float32)
-        loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        d = N.MMMaskIouDesc(B, lhs.numel() // B, N.ptr(lhs), N.ptr(rhs), N.ptr(sums), N.ptr(loss))
-        N.call("mm_mask_iou_forward", pred.device, d)
-        iou = sums[:, 0] / (sums[:, 1] + 1e-10)
+        iou = _mask_iou_rows(gt[:, 3].to(torch.float32).contiguous(), pred[:, 3].to(torch.float32).contiguous())
+    return s.to(out_dev), iou.to(out_dev)
+
+
+def recon_scores_as_saved(pred, gt, quality=100, white_gt=False):
+    """``recon_scores`` as the reference's loop computes it: on the images it has SAVED as JPEG files and read back (trainer.py:697-795,
+    test.py:302-455), all on the device.  (B,4,H,W) fp32 pred and gt -> (ssim (B,), mask_iou (B,)), the composition of
+      1. ``export_images(x, "rgb+mask")``, rounding "trunc" (``to_pil_image``'s ``mul(255).byte()``); ``white=white_gt`` for gt only (the
+         ``opt.bg`` branch, trainer.py:754-757);
+      2. ``jpeg_roundtrip`` of the rgb in mode "RGB" (a 4:2:0 colour file, ``.convert('RGB')``) and of the mask in mode "L" (a greyscale
+         file, ``.convert('L')``), ``as_float``: ``to_tensor`` of the reopened images;
+      3. ``ssim(ori, rec, data_range=1, size_average=False)`` and the mask-IoU kernel of ``recon_scores``.
+    The ``.resize`` between open and score asks for the file's own size, which is the identity.  Equal, with torch.equal, to that
+    composition written out from the public functions."""
+    from .export import export_images
+    from .jpeg import jpeg_roundtrip
+    if pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 4:
+        raise ValueError("recon_scores_as_saved expects two (B,4,H,W) tensors, got %s / %s" % (tuple(pred.shape), tuple(gt.shape)))
+    pred, gt, out_dev = _on_device(pred, gt)
+    with torch.no_grad():
+        back = []
+        for x, white in ((gt, bool(white_gt)), (pred, False)):
+            rgb, mask = export_images(x, "rgb+mask", rounding="trunc", white=white)
+            back.append((jpeg_roundtrip(rgb, quality, "RGB", as_float=True), jpeg_roundtrip(mask, quality, "L", as_float=True)))
+        (ori, ori_mask), (rec, rec_mask) = back
+        s = ssim(ori, rec, data_range=1, size_average=False)
+        iou = _mask_iou_rows(ori_mask, rec_mask)
     return s.to(out_dev), iou.to(out_dev)

@@ -986,6 +986,49 @@ size_t mm_jpeg_files_offset(const MMJpegDesc* desc);        /* where the files s
 int mm_jpeg_encode(const MMJpegDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * JPEG round trip: n device frames as a decoder reads them back from the files above -- to the byte what Pillow's
+ * Image.open(file).convert('RGB') gives for mm_jpeg_encode's file of an (H,W,3) frame (mode RGB, 4:2:0), and what
+ * Image.open(file).convert('L') gives for the greyscale file libjpeg writes of an (H,W) frame (mode L; that file is never formed).  No
+ * entropy decoder: a file's content is its quantised coefficients.  Integer arithmetic only (>> arithmetic), libjpeg's decoder:
+ *   dequantise  c[k] * table[k], table = divisor / 8 (luma for Y and greyscale, chroma for Cb and Cr)
+ *   IDCT        jidctint (islow), CONST_BITS 13, PASS1_BITS 2, columns first descaled by 11 bits, then rows by 18, each with round-half-up
+ *               ((x + (1 << (n - 1))) >> n); + 128; clamped to 0..255 (saturating, as libjpeg-turbo's SIMD code does)
+ *   colour      Cb and Cr are real on ceil(H / 2) x ceil(W / 2); beyond its first and last REAL row a row's neighbour is that row itself.
+ *               ceil(W / 2) > 2: h2v2 "fancy" upsampling, s[x] = 3 c[r][x] + c[neighbour row][x] (the row above for output row 2r, below
+ *               for 2r + 1), out[2x] = (3 s[x] + s[x-1] + 8) >> 4, out[2x+1] = (3 s[x] + s[x+1] + 7) >> 4, s[-1] := s[0], s[wd] := s[wd-1].
+ *               ceil(W / 2) <= 2: 2 x 2 replication.  R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *               B = Y + ((116130 cb + 32768) >> 16) with cb, cr minus 128, each clamped to 0..255.
+ *   greyscale   8 x 8 blocks, edges replicated, samples minus 128 through the encoder's jfdctint and quantiser with the luma divisors,
+ *               then dequantise, IDCT, clamp, crop.
+ * Mode RGB decodes int16 zigzag blocks from memory: those mm_jpeg_encode left at mm_jpeg_coef_offset of ITS workspace, given as coef
+ * (frames may then be NULL; the decoded frames are those of the very files), or, with coef NULL, those of its own pass of the encoder's
+ * transform over frames.  params / params_host: the first 128 words of MMJpegDesc.params, the divisors (the rest may follow; it is not
+ * read).  out: bytes (n,H,W,3) / (n,H,W), or with as_float fp32 v / 255 in planes (n,3,H,W) / (n,H,W); 4-byte aligned, never the input.
+ * The workspace is the caller's, mm_jpeg_roundtrip_query_workspace bytes, 16-byte aligned (mode RGB: the coefficients unless coef is
+ * given, and the Y, Cb and Cr sample planes, 1.5 bytes per pixel of whole MCUs; mode L uses none and the query answers 256).
+ * Return codes as mm_jpeg_encode's: MM_ERR_BAD_SHAPE also for an unknown mode; MM_ERR_WORKSPACE also for a misaligned coef or out.
+ * Mode RGB: two or three launches (transform unless coef is given, idct, pixels); mode L: one.  No host synchronisation; bitwise reproducible.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_JPEG_MODE_RGB 0
+#define MM_JPEG_MODE_L 1
+typedef struct MMJpegRoundtripDesc {
+    int32_t n, H, W;                /* the frames */
+    int32_t mode;                   /* MM_JPEG_MODE_RGB or MM_JPEG_MODE_L */
+    int32_t as_float;               /* fp32 planes instead of bytes */
+    int32_t reserved;               /* 0 */
+    const uint8_t* frames;          /* (n,H,W,3) or (n,H,W), dense, any alignment */
+    const int16_t* coef;            /* mode RGB: NULL, or (n, blocks, 64) as mm_jpeg_encode leaves them; 16-byte aligned */
+    const int32_t* params_host;     /* host memory */
+    const int32_t* params;          /* device memory, the same words */
+    void* out;
+    void* workspace;
+    size_t workspace_bytes;
+} MMJpegRoundtripDesc;
+size_t mm_jpeg_coef_offset(const MMJpegDesc* desc);         /* where the coefficients lie in mm_jpeg_encode's workspace */
+size_t mm_jpeg_roundtrip_query_workspace(const MMJpegRoundtripDesc* desc);      /* reads n, H, W, mode and whether coef is NULL */
+int mm_jpeg_roundtrip(const MMJpegRoundtripDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -1009,7 +1052,8 @@ const char* mm_last_error_detail(void);
  * 12 MMDibrGrads, 13 MMTexMapDesc, 14 MMTexMapGrads, 15 MMShDesc, 16 MMShGrads, 17 MMMaskIouDesc, 18 MMSsimDesc,
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
- * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc (31, 34 and 36 are unassigned). */
+ * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
+ * 38 MMJpegRoundtripDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1028,7 +1072,8 @@ size_t mm_struct_size(int which);
  * returns 0 --, an addition, detected by mm_struct_size(32) != 0; still 9: MMRenderIndexedDesc and mm_render_indexed_*, struct id 33, an
  * addition, detected by mm_struct_size(33) != 0; still 9: MMPyramidDesc and mm_pyramid_frames, struct id 35 -- id 34 stays unassigned and
  * returns 0 --, an addition, detected by mm_struct_size(35) != 0; still 9: MMJpegDesc and mm_jpeg_*, struct id 37 -- id 36 stays
- * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0; still 9: MMJpegRoundtripDesc,
+ * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
