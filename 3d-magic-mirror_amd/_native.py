@@ -225,6 +225,14 @@ class MMJpegRoundtripDesc(ctypes.Structure):
                 ("params_host", c_p), ("params", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+GIF_SEGMENT, GIF_MAX_SEGMENT = 1024, 3838      # MM_GIF_SEGMENT, MM_GIF_MAX_SEGMENT
+
+
+class MMGifDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("segment", c_i), ("delay", c_i), ("loop", c_i), ("quantize_only", c_i), ("reserved", c_i),
+                ("frames", c_p), ("delays", c_p), ("palette", c_p), ("indices", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -310,6 +318,9 @@ SIGNATURES = {
     "mm_jpeg_coef_offset": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_roundtrip_query_workspace": (c_z, [P(MMJpegRoundtripDesc)]),
     "mm_jpeg_roundtrip": (c_int, [P(MMJpegRoundtripDesc), c_p]),
+    "mm_gif_query_workspace": (c_z, [P(MMGifDesc)]),
+    "mm_gif_file_offset": (c_z, [P(MMGifDesc)]),
+    "mm_gif_encode": (c_int, [P(MMGifDesc), c_p]),
     "mm_build_vertex_corner_csr": (c_int, [c_i, c_i, c_p, c_p, c_p]),
     "mm_build_vertex_corner_csr_device": (c_int, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mm_build_vertex_corner_table": (c_int, [c_i, c_i, c_p, c_i, c_p]),
@@ -326,7 +337,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
-              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc}
+              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 
@@ -461,7 +472,7 @@ def call(name, where, *args, what=None):
 
     The one call path of every entry point that takes a stream and returns an MMStatus.  Deliberately not folded in: input_batches.py turns a
     refusal of mm_assemble_batch into a ValueError of its own wording (it uses fn, not check); mm_render_status returns a verdict, not an
-    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_jpeg_coef_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
+    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_jpeg_coef_offset, mm_gif_file_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
     and diff_render.py hands fn_addr addresses to the C++ nodes."""
     status = (_FN.get(name) or fn(name))(*args, where if type(where) is c_p else current_stream(where))
     if status:

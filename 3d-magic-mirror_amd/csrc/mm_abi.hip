@@ -66,6 +66,9 @@ int launch_jpeg(const MMJpegDesc*, hipStream_t);
 size_t jpeg_coef_at(const MMJpegDesc*);
 size_t jpeg_roundtrip_workspace_bytes(const MMJpegRoundtripDesc*);
 int launch_jpeg_roundtrip(const MMJpegRoundtripDesc*, hipStream_t);
+size_t gif_workspace_bytes(const MMGifDesc*);
+size_t gif_file_at(const MMGifDesc*);
+int launch_gif(const MMGifDesc*, hipStream_t);
 }  // namespace mm
 
 static bool sizes_positive(const MMRenderDesc* d) { return d->B > 0 && d->H > 0 && d->W > 0 && d->V > 0 && d->F > 0 && d->Ht > 0 && d->Wt > 0; }
@@ -893,6 +896,33 @@ int mm_jpeg_roundtrip(const MMJpegRoundtripDesc* d, mm_stream_t stream) {
     return mm::launch_jpeg_roundtrip(d, (hipStream_t)stream);
 }
 
+// the sizes a GIF call may have: MM_OK, or why not
+static int check_gif_shape(const MMGifDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->n <= 0 || d->H <= 0 || d->W <= 0 || d->segment < 1 || d->segment > MM_GIF_MAX_SEGMENT) return MM_ERR_BAD_SHAPE;
+    if (d->delay < 0 || d->delay > 65535 || d->loop < -1 || d->loop > 65535) return MM_ERR_BAD_SHAPE;
+    if (d->H > 65535 || d->W > 65535 || d->n > 65535) return MM_ERR_UNSUPPORTED;
+    if ((long long)d->n * d->H * d->W >= (1LL << 29)) return MM_ERR_UNSUPPORTED;         // 7 * count stays inside 32 bits
+    return MM_OK;
+}
+
+size_t mm_gif_query_workspace(const MMGifDesc* d) {
+    return check_gif_shape(d) == MM_OK ? mm::gif_workspace_bytes(d) : 0;
+}
+
+size_t mm_gif_file_offset(const MMGifDesc* d) {
+    return check_gif_shape(d) == MM_OK ? mm::gif_file_at(d) : 0;
+}
+
+int mm_gif_encode(const MMGifDesc* d, mm_stream_t stream) {
+    const int shape = check_gif_shape(d);
+    if (shape != MM_OK) return shape;
+    if (!d->frames || !d->palette || !d->indices || !d->workspace) return MM_ERR_NULL_POINTER;
+    if (d->workspace_bytes < mm::gif_workspace_bytes(d) || ((uintptr_t)d->workspace & 15)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_gif(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -967,6 +997,7 @@ size_t mm_struct_size(int which) {
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
         case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
+        case 39: return sizeof(MMGifDesc);
         default: return 0;
     }
 }

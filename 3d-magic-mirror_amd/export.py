@@ -114,7 +114,7 @@ def export_grid(x, nrow=8, padding=2, pad_value=0.0, rounding="trunc", white=Fal
     frames of a turntable from one ``render_views`` result (trainer.py:616-631).  ``grid_shape`` has (Hg, Wg); the gutters and the
     empty cells of a short last row hold the quantised ``pad_value``.  rounding, white, layouts and dtypes as in ``export_images``.
 
-        sheet = export_grid(frames).cpu().numpy()                          # (36,Hg,Wg,3): one copy; imageio.mimsave(path, list(sheet))"""
+        sheet = export_grid(frames)                                        # (36,Hg,Wg,3), on the device; encode_gif(sheet).write(path)"""
     _check(x, rounding, white, (4, 5), "(B,C,H,W) or (B,N,C,H,W)")
     B, Nv = x.shape[0], (x.shape[1] if x.dim() == 5 else 1)
     Hg, Wg = grid_shape(B, x.shape[-2], x.shape[-1], nrow, padding)

@@ -1029,6 +1029,56 @@ size_t mm_jpeg_roundtrip_query_workspace(const MMJpegRoundtripDesc* desc);      
 int mm_jpeg_roundtrip(const MMJpegRoundtripDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * GIF: n device frames (n,H,W,3) of bytes -- what mm_export_grid, mm_export_images, mm_composite_frames and mm_pyramid_frames write, at
+ * any byte alignment -- as ONE animated GIF89a file with one global palette of 256 colours.  The file is fully specified here (no other
+ * writer's bytes are a target).  Integer arithmetic only; every atomic is an integer one, so their order cannot matter:
+ *   histogram  over all frames: bin = (r>>3)<<10 | (g>>3)<<5 | (b>>3), 32768 bins, each a pixel count and the sums of r&7, g&7, b&7
+ *   palette    median cut over the non-empty bins.  Box 0 holds them all.  While there are fewer than 256 boxes and some box has at least
+ *              two non-empty bins: split the box with the largest pixel count among those (ties: the lowest index) along the axis with
+ *              the largest max - min bin coordinate over its non-empty bins (ties: g, then r, then b) at k, the smallest coordinate in
+ *              [min, max-1] whose cumulative marginal count from min reaches (count+1)/2 (max-1 if none does).  Bins with coordinate <= k
+ *              keep the box's index, the others get index = the number of boxes so far.  Entry i, per channel: (2 s + c) / (2 c) with
+ *              c = sum count and s = sum (count * (coord << 3) + low_sum) over the box's bins in 64 bits; unused entries are 0,0,0.
+ *   indices    a pixel's index is the box of its bin (the per-bin box array is the lookup table)
+ *   LZW        a frame's indices in raster order, cut into segments of `segment` pixels (the last may be shorter) that code
+ *              independently.  The frame's stream opens with Clear (256) at 9 bits.  Each segment codes greedily, longest match, with a
+ *              fresh dictionary: next = 258, width = 9.  When a new entry receives code next: if next == 1 << width and width < 12 the
+ *              width grows by one; then next += 1.  After the segment's last data code the same test is applied once more; then Clear at
+ *              that width, or EOI (257) after the frame's last segment.  Codes are packed LSB first; the frame's last byte is zero-padded.
+ *   file       "GIF89a"; W, H (u16le), 0xF7, 0, 0; the 768 palette bytes; with loop >= 0: 21 FF 0B "NETSCAPE2.0" 03 01 <loop u16le> 00;
+ *              per frame 21 F9 04 04 <delay u16le> 00 00, 2C 0 0 0 0 <W> <H> 00, 08, the stream in sub-blocks of up to 255 bytes each
+ *              behind its length byte, 00; finally 3B.
+ * palette (768 bytes) and indices (n*H*W bytes) are the caller's device arrays and are always written; with quantize_only nothing else is.
+ * The workspace is the caller's, mm_gif_query_workspace bytes, 16-byte aligned; the library allocates nothing.  After the call it holds at
+ * byte 0 the file's length as int64 and from byte mm_gif_file_offset on the file: a caller copies the length, then exactly that many
+ * bytes.  The rest is scratch: the histogram, the frames' packed streams and a slot per segment sized for its exact worst case (every
+ * code new: code k of a segment takes 9 + (k >= 255) + (k >= 767) + (k >= 1791) bits).
+ * MM_ERR_BAD_SHAPE: n, H, W < 1; segment outside 1..MM_GIF_MAX_SEGMENT; delay outside 0..65535; loop outside -1..65535.
+ * MM_ERR_UNSUPPORTED: H, W or n > 65535; n*H*W >= 2^29 (the queries return 0).  MM_ERR_WORKSPACE: too small or misaligned.
+ * Nine stream operations (one memset, eight launches); with quantize_only four (one memset, three launches).  No host synchronisation;
+ * bitwise reproducible.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_GIF_SEGMENT 1024         /* the segment length the Python layer uses */
+#define MM_GIF_MAX_SEGMENT 3838     /* 257 + 3838 = 4095: a segment's dictionary can never fill */
+typedef struct MMGifDesc {
+    int32_t n, H, W;                /* the frames */
+    int32_t segment;                /* pixels that share a dictionary */
+    int32_t delay;                  /* centiseconds, every frame's unless delays is given */
+    int32_t loop;                   /* the NETSCAPE2.0 loop count, or -1 for no such extension */
+    int32_t quantize_only;          /* palette and indices only: no file is formed */
+    int32_t reserved;               /* 0 */
+    const uint8_t* frames;          /* (n,H,W,3), dense, any alignment */
+    const int32_t* delays;          /* NULL, or n per-frame delays in device memory (their low 16 bits are used) */
+    uint8_t* palette;               /* out: (256,3) */
+    uint8_t* indices;               /* out: (n,H,W) */
+    void* workspace;
+    size_t workspace_bytes;
+} MMGifDesc;
+size_t mm_gif_query_workspace(const MMGifDesc* desc);       /* reads n, H, W, segment, loop, quantize_only */
+size_t mm_gif_file_offset(const MMGifDesc* desc);           /* where the file starts in the workspace */
+int mm_gif_encode(const MMGifDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -1053,7 +1103,7 @@ const char* mm_last_error_detail(void);
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
- * 38 MMJpegRoundtripDesc (31, 34 and 36 are unassigned). */
+ * 38 MMJpegRoundtripDesc, 39 MMGifDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1073,7 +1123,7 @@ size_t mm_struct_size(int which);
  * addition, detected by mm_struct_size(33) != 0; still 9: MMPyramidDesc and mm_pyramid_frames, struct id 35 -- id 34 stays unassigned and
  * returns 0 --, an addition, detected by mm_struct_size(35) != 0; still 9: MMJpegDesc and mm_jpeg_*, struct id 37 -- id 36 stays
  * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0; still 9: MMJpegRoundtripDesc,
- * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0; still 9: MMGifDesc and mm_gif_*, struct id 39, an addition, detected by mm_struct_size(39) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
