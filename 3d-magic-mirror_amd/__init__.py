@@ -10,6 +10,7 @@ from .critic_inputs import CriticInputs, critic_inputs  # noqa: F401
 from .export import export_grid, export_images, grid_shape  # noqa: F401
 from .composite import composite_frames, gaussian_taps, lower_composite, resize_taps  # noqa: F401
 from .pyramid import lower_pyramid, pyramid_frames  # noqa: F401
+from .poisson import lower_poisson, poisson_frames  # noqa: F401
 from .jpeg import JpegBatch, encode_jpeg, jpeg_roundtrip, lower_jpeg  # noqa: F401
 from .gif import GIF_SEGMENT, GifFile, encode_gif, quantize_frames  # noqa: F401
 from .input_batches import ImagePool, assemble_batch, assemble_records, draw_augmentation, lower_batch  # noqa: F401

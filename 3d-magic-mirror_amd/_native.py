@@ -212,6 +212,15 @@ class MMPyramidDesc(ctypes.Structure):
                 ("renders", c_p), ("backgrounds", c_p), ("params_host", c_p), ("params", c_p), ("out", c_p)]
 
 
+POISSON_MAX_SWEEPS = 1 << 16          # MM_POISSON_MAX_SWEEPS
+
+
+class MMPoissonDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("H", c_i), ("W", c_i), ("n_fg", c_i), ("n_bg", c_i), ("bg_C", c_i), ("fg_nhwc", c_i), ("border", c_i),
+                ("bg_pad", c_i * 4), ("rounding", c_i), ("as_float", c_i), ("sweeps", c_i), ("omega", c_f),
+                ("renders", c_p), ("backgrounds", c_p), ("mask", c_p), ("params_host", c_p), ("params", c_p), ("out", c_p)]
+
+
 class MMJpegDesc(ctypes.Structure):
     _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("header_bytes", c_i), ("frames", c_p), ("params_host", c_p), ("params", c_p),
                 ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
@@ -312,6 +321,7 @@ SIGNATURES = {
     "mm_assemble_batch": (c_int, [P(MMBatchDesc), c_p]),
     "mm_composite_frames": (c_int, [P(MMCompositeDesc), c_p]),
     "mm_pyramid_frames": (c_int, [P(MMPyramidDesc), c_p]),
+    "mm_poisson_frames": (c_int, [P(MMPoissonDesc), c_p]),
     "mm_jpeg_query_workspace": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_files_offset": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_encode": (c_int, [P(MMJpegDesc), c_p]),
@@ -337,7 +347,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
-              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc}
+              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 

@@ -60,6 +60,9 @@ int launch_composite(const MMCompositeDesc*, hipStream_t);
 struct PyrArgs;
 long long pyramid_lds_bytes(const MMPyramidDesc*, PyrArgs*);
 int launch_pyramid(const MMPyramidDesc*, hipStream_t);
+struct PoiArgs;
+long long poisson_lds_bytes(const MMPoissonDesc*, PoiArgs*);
+int launch_poisson(const MMPoissonDesc*, hipStream_t);
 size_t jpeg_workspace_bytes(const MMJpegDesc*);
 size_t jpeg_files_at(const MMJpegDesc*);
 int launch_jpeg(const MMJpegDesc*, hipStream_t);
@@ -108,7 +111,7 @@ static int check_render(const MMRenderDesc* d, bool backward) {
     return MM_OK;
 }
 
-// what mm_composite_frames and mm_pyramid_frames (MMCompositeDesc, MMPyramidDesc) refuse alike: pointers, sizes, the rounding, a reflection
+// what mm_composite_frames, mm_pyramid_frames and mm_poisson_frames (MMCompositeDesc, MMPyramidDesc, MMPoissonDesc) refuse alike: pointers, sizes, the rounding, a reflection
 // pad that would reflect twice, and the host's copy of the two index tables in front of params
 template <class Desc>
 static int check_frames(const Desc* d) {
@@ -832,6 +835,19 @@ int mm_pyramid_frames(const MMPyramidDesc* d, mm_stream_t stream) {
     return mm::launch_pyramid(d, (hipStream_t)stream);
 }
 
+int mm_poisson_frames(const MMPoissonDesc* d, mm_stream_t stream) {
+    const int st = check_frames(d);
+    if (st != MM_OK) return st;
+    if ((d->border != 0 && d->border != 1) || d->B > (1 << 24)) return MM_ERR_BAD_SHAPE;
+    if (d->sweeps < 0 || d->sweeps > MM_POISSON_MAX_SWEEPS || !(d->omega > 0.0f && d->omega < 2.0f)) return MM_ERR_BAD_SHAPE;
+    const int32_t* bp = d->bg_pad;
+    const int32_t* row = d->params_host + 2 * (size_t)d->B;
+    if (check_resize_rows(row, d->H, d->H + bp[2] + bp[3]) != MM_OK || check_resize_rows(row, d->W, d->W + bp[0] + bp[1]) != MM_OK) return MM_ERR_BAD_SHAPE;
+    if (mm::poisson_lds_bytes(d, nullptr) > 160 * 1024) return MM_ERR_UNSUPPORTED;
+    mm::clear_stale_error();
+    return mm::launch_poisson(d, (hipStream_t)stream);
+}
+
 // the sizes a JPEG call may have: MM_OK, or why not
 static int check_jpeg_shape(const MMJpegDesc* d) {
     if (!d) return MM_ERR_NULL_POINTER;
@@ -997,7 +1013,7 @@ size_t mm_struct_size(int which) {
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
         case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
-        case 39: return sizeof(MMGifDesc);
+        case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc);
         default: return 0;
     }
 }

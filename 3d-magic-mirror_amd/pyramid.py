@@ -17,7 +17,8 @@ reference's line, left to right; ``export_images``' quantiser.  DESIGN.md has th
 The pyramid's sums leave [0, 1] (uniform inputs range over about -0.25 ... 1.25), where the reference's ``np.uint8`` of the value is
 undefined: this kernel saturates to 0 / 255 and sends NaN to 0, as ``export_images`` does.
 
-Out of scope: poisson_image_editing.py (imported by that script, never called); the texture mix with the mean-texture bank (:339);
+poisson_image_editing.py (imported by that script, never called) is ``poisson_frames`` (poisson.py).  Out of scope: the texture mix with the
+mean-texture bank (:339);
 reproducing the reference's random streams (the caller draws ``bg_index`` and the sigmas: ``draw_sigmas``); gradients; other
 numbers of levels.  JPEG encoding: ``encode_jpeg`` (jpeg.py).  Device tensors only."""
 import functools

@@ -939,6 +939,57 @@ typedef struct MMPyramidDesc {
 int mm_pyramid_frames(const MMPyramidDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Poisson: renders blended into backgrounds by Poisson (seamless-cloning) editing as 8-bit frames -- the system the reference's
+ * poisson_image_editing.py:33-108 builds with offset (0,0) and solves with one sparse direct solve per frame and channel on the host --
+ * in one launch: B frames (B,H,W,3) bytes, or, with as_float, (B,3,H,W) fp32 planes fl(float(q) / 255), from `renders` and `backgrounds`
+ * as MMCompositeDesc takes them.  Per frame o and colour channel c, all in fp32, every operation rounded as written, no contraction:
+ *   s         channel c of render fg_index[o], untouched
+ *   t         plane c of background bg_index[o] behind the reflection pad bg_pad, resized to (H,W): level 0 of MMPyramidDesc's
+ *             background, bit for bit (x, then y, taps ascending from 0, no blur)
+ *   in        mask[fg_index[o]][y][x] != 0 if mask is given (bytes (n_fg,H,W)); otherwise the Export quantiser's trunc byte of the
+ *             render's channel 3 != 0
+ *   pinned    x = t.  border 0 ("reference"): the cells outside the mask that are not on the image's outer row or column;
+ *             border 1 ("pinned"): every cell outside the mask.
+ *   free      every other cell: 4 x_p - sum x_q = b_p over the 4-neighbours q inside the image; inside the mask
+ *             b = fl(fl(4 s) - fl(fl(sl + sr) + fl(su + sd))) with a neighbour outside the image as 0; outside it (the outer-border cells
+ *             of border 0) b = t.
+ *   solve     x = t everywhere; then `sweeps` red-black SOR sweeps, the free cells with (y + x) even first, then those with (y + x) odd:
+ *             x <- fl(x + fl(omega * fl(fl(fl(b + fl(fl(l + r) + fl(u + d))) * 0.25) - x))), a neighbour outside the image read as 0.
+ *             Cells of one colour do not read each other.  The sweep count is fixed: no convergence test, nothing comes back.
+ *   quantise  the Export quantiser above, unchanged: rounding 0 trunc / 1 nearest, NaN -> 0, saturating (the solution leaves [0, 1]).
+ * params is ONE table of 32-bit words (floats by their bits) that the caller uploads; params_host is the host's copy of it, which is
+ * validated and sizes the kernel's LDS before anything is launched:
+ *   fg_index (B) | bg_index (B) | resize rows: bg y (H), bg x (W)
+ * a resize row being MM_PYRAMID_ROW_WORDS words {start, n, w[0..8)} as in MMPyramidDesc.
+ * MM_ERR_BAD_SHAPE: B, H, W, n_fg, n_bg < 1; bg_C not 3 or 4; a pad that is negative or >= the dimension it reflects in; an index
+ * outside [0, n_fg) / [0, n_bg); a resize row with n outside [1, MM_PYRAMID_MAX_TAPS] or taps outside the padded axis; rounding or border
+ * not 0 / 1; sweeps < 0 or > MM_POISSON_MAX_SWEEPS; omega not inside (0, 2).
+ * MM_ERR_UNSUPPORTED: more than the 160 KiB of LDS -- one workgroup holds a whole plane for the whole solve: 8 * (H + 2) * ((W + 3) / 2)
+ * + 4 * rows * W bytes (rows: the most source rows the vertical resize of 8 output rows reads), each term rounded up to 16;
+ * 36 896 bytes at 128 x 64 and 72 736 at 128 x 128 behind a pad of 16; 256 x 256 does not fit --, or more than 2^31 - 1 workgroups.
+ * No workspace, no atomics, no host synchronisation; bitwise reproducible.  Not differentiable.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_POISSON_MAX_SWEEPS (1 << 16)
+typedef struct MMPoissonDesc {
+    int32_t B, H, W;                /* the frames */
+    int32_t n_fg, n_bg, bg_C;       /* images in renders / backgrounds; channels of a background */
+    int32_t fg_nhwc;                /* layout flag of renders */
+    int32_t border;                 /* 0 reference: outer-border cells outside the mask are free; 1 pinned: they keep t */
+    int32_t bg_pad[4];              /* reflection pad of the background: left, right, top, bottom */
+    int32_t rounding;               /* 0 trunc, 1 nearest */
+    int32_t as_float;               /* fp32 planes (B,3,H,W) instead of bytes (B,H,W,3) */
+    int32_t sweeps;                 /* red-black sweeps, >= 0 */
+    float omega;                    /* the relaxation factor, inside (0, 2) */
+    const float* renders;
+    const float* backgrounds;
+    const uint8_t* mask;            /* NULL, or (n_fg,H,W) bytes: non-zero is inside */
+    const int32_t* params_host;     /* host memory */
+    const int32_t* params;          /* device memory, the same words */
+    void* out;
+} MMPoissonDesc;
+int mm_poisson_frames(const MMPoissonDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * JPEG: n device frames (n,H,W,3) of bytes -- what mm_export_images, mm_composite_frames and mm_pyramid_frames write, at any byte
  * alignment -- as n complete baseline JPEG files, byte for byte what libjpeg(-turbo) writes for 4:2:0 with the standard Huffman tables,
  * the islow DCT and quantisation tables q (Pillow's Image.save(f, 'JPEG', quality=...)).  The caller writes the file's head, SOI up to and
@@ -1103,7 +1154,7 @@ const char* mm_last_error_detail(void);
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
- * 38 MMJpegRoundtripDesc, 39 MMGifDesc (31, 34 and 36 are unassigned). */
+ * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1123,7 +1174,8 @@ size_t mm_struct_size(int which);
  * addition, detected by mm_struct_size(33) != 0; still 9: MMPyramidDesc and mm_pyramid_frames, struct id 35 -- id 34 stays unassigned and
  * returns 0 --, an addition, detected by mm_struct_size(35) != 0; still 9: MMJpegDesc and mm_jpeg_*, struct id 37 -- id 36 stays
  * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0; still 9: MMJpegRoundtripDesc,
- * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0; still 9: MMGifDesc and mm_gif_*, struct id 39, an addition, detected by mm_struct_size(39) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0; still 9: MMGifDesc and mm_gif_*, struct id 39, an addition, detected by mm_struct_size(39) != 0; still 9: MMPoissonDesc and
+ * mm_poisson_frames, struct id 40, an addition, detected by mm_struct_size(40) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
