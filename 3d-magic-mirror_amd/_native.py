@@ -498,6 +498,32 @@ def workspace(query_name, desc, device, zero=False, at_least=0):
     return t
 
 
+def up256(x):
+    """x rounded up to a multiple of 256: where the next array of a workspace starts (align256 in csrc/mm_device.h)"""
+    return (x + 255) // 256 * 256
+
+
+def checked_workspace(query_name, desc, device, want, offset_names, text):
+    """``workspace(query_name, desc, device)``, held to the Python mirror of its layout: ``want`` is (bytes, offset, ...), the offsets those
+    the exports ``offset_names`` give for desc.  Any difference raises RuntimeError(text(got, want)), both tuples like ``want``."""
+    ws = workspace(query_name, desc, device)
+    got = (desc.workspace_bytes,) + tuple(fn(name)(desc) for name in offset_names)
+    if got != tuple(want):
+        raise RuntimeError(text(got, tuple(want)))
+    return ws
+
+
+def read_back(ws, k, at):
+    """Files out of a workspace after two blocking copies through pinned host memory: the k int64 words at its head, then exactly
+    words[-1] bytes from byte ``at`` on.  (the words as a list, the bytes as a pinned uint8 tensor)"""
+    head = torch.empty((k,), dtype=torch.int64, pin_memory=True)
+    head.copy_(ws[:8 * k].view(torch.int64))                             # copy 1 (blocking): the lengths
+    words = head.tolist()
+    buf = torch.empty((words[-1],), dtype=torch.uint8, pin_memory=True)
+    buf.copy_(ws[at:at + words[-1]])                                     # copy 2 (blocking): exactly the bytes used
+    return words, buf
+
+
 def require_device(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

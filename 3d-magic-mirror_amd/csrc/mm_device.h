@@ -547,6 +547,25 @@ __device__ inline int wave_prefix_excl(int v, int lane, int& total) {
     total = __builtin_amdgcn_readlane(inc, 63);
     return inc - v;
 }
+// ... and over a workgroup of NT lanes (total in every lane): the wave scan, then the waves' totals through LDS.  Every lane of the
+// workgroup calls it; sh: NT / 64 ints, which may still be read from the call before.
+template <int NT>
+__device__ inline int block_prefix_excl(int v, int tid, int* sh, int& total) {
+    int wave_total;
+    const int e = wave_prefix_excl(v, tid & 63, wave_total);
+    __syncthreads();
+    if ((tid & 63) == 0) sh[tid >> 6] = wave_total;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < NT / MM_WAVE; ++w) {
+        const int x = sh[w];
+        base += w < (tid >> 6) ? x : 0;
+        total += x;
+    }
+    return e + base;
+}
 
 // ---- screen binning of one wave's 64 faces = mask word c of every bin -------------------------------------------------
 // A lane turns its face's pixel box (inflated by the soft-mask margin, conservative; bw <= 0: none) into bin column / row

@@ -34,13 +34,14 @@
 //              2 * segment 32-bit slots) in LDS, as many segments to a workgroup of one wave as fit 64 KiB.  The chain is serial by nature:
 //              an LDS probe per pixel.  The codes leave as the segment's own bit stream in its slot of the workspace, sized for the exact
 //              worst case (every code new), with the bit count.
-//   offsets    a workgroup per frame scans the segments' bit counts.
+//   offsets    a workgroup per frame scans the segments' bit counts (array_scan of mm_stream.h, as place does and the JPEG encoder's scans).
 //   pack       a lane per 32-bit word of a segment's stream ORs it into the frame's zeroed stream at the bit offset.
 //   place      one workgroup scans the frames' lengths; the file's length goes to byte 0 of the workspace.
 //   write      the file's head, the frames' heads, the sub-blocks with their length bytes, terminators and the trailer.
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_stream.h"                                        // array_scan, Carve: what the encoders share
 
 #define MM_GIF_BLOCK 256
 #define MM_GIF_CUT_BLOCK 1024
@@ -70,7 +71,6 @@ struct GifLayout {
     size_t file_cap;
     size_t total, file, hist, lut, raw, seg_bits, frame_len, slots, zero_bytes, bytes;      // byte offsets into the workspace
 };
-__host__ inline size_t gif_up(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ GifLayout gif_layout(const MMGifDesc* d) {
     GifLayout l;
     const size_t n = (size_t)d->n;
@@ -88,16 +88,17 @@ __host__ GifLayout gif_layout(const MMGifDesc* d) {
     const size_t stream = (size_t)((frame_bits + 7) / 8);
     l.head = 13 + 768 + (d->loop >= 0 ? 19 : 0);
     l.file_cap = (size_t)l.head + n * (20 + stream + (stream + 254) / 255) + 1;
-    l.total = 0;
-    l.file = 256;
-    l.hist = l.file + gif_up(l.file_cap);
-    l.lut = l.hist + (size_t)MM_GIF_BINS * 16;
-    l.raw = l.lut + MM_GIF_BINS;
-    l.seg_bits = l.raw + gif_up(n * (size_t)l.raw_words * 4);
+    Carve c;
+    l.total = c.take(8);                                      // (the file follows at 256: gif_file_at)
+    l.file = c.take(l.file_cap);
+    l.hist = c.take((size_t)MM_GIF_BINS * 16);
+    l.lut = c.take(MM_GIF_BINS);
+    l.raw = c.take(n * (size_t)l.raw_words * 4);
+    l.seg_bits = c.take(n * (size_t)l.segs * 8);
     l.zero_bytes = l.seg_bits - l.hist;                       // the histogram, the table and the streams start as zeros
-    l.frame_len = l.seg_bits + gif_up(n * (size_t)l.segs * 8);
-    l.slots = l.frame_len + gif_up((2 * n + 1) * 8);              // where each frame starts (n + 1), then each frame's bits
-    l.bytes = l.slots + gif_up(n * (size_t)l.segs * l.slot_words * 4);
+    l.frame_len = c.take((2 * n + 1) * 8);                    // where each frame starts (n + 1), then each frame's bits
+    l.slots = c.take(n * (size_t)l.segs * l.slot_words * 4);
+    l.bytes = c.at;
     return l;
 }
 size_t gif_workspace_bytes(const MMGifDesc* d) { return d->quantize_only ? 256 + (size_t)MM_GIF_BINS * 17 : gif_layout(d).bytes; }
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(MM_GIF_CUT_BLOCK) void gif_median_cut_kernel(GifArg
     __shared__ unsigned long long sum[256][3];
     __shared__ unsigned best_count, best_box;
     __shared__ unsigned marg[32];
-    __shared__ int wave_count[MM_GIF_CUT_BLOCK / 64];
+    __shared__ int scan_sh[MM_GIF_CUT_BLOCK / 64];
     __shared__ int cut;
     const int tid = threadIdx.x;
     const unsigned long long* hist = a.hist;
@@ -217,22 +218,17 @@ __global__ __launch_bounds__(MM_GIF_CUT_BLOCK) void gif_median_cut_kernel(GifArg
     constexpr int PER = MM_GIF_BINS / MM_GIF_CUT_BLOCK;
     int mine = 0;
     for (int j = 0; j < PER; ++j) mine += (unsigned)hist[2 * (tid * PER + j)] != 0u;
-    int wtot;
-    int at = wave_prefix_excl(mine, tid & 63, wtot);
-    if ((tid & 63) == 0) wave_count[tid >> 6] = wtot;
     if (tid < 256) {
         box[tid].count = 0; box[tid].bins = 0;
         for (int x = 0; x < 3; ++x) { box[tid].lo[x] = 31; box[tid].hi[x] = 0; sum[tid][x] = 0; }
     }
-    __syncthreads();
-    for (int w = 0; w < MM_GIF_CUT_BLOCK / 64; ++w) at += w < (tid >> 6) ? wave_count[w] : 0;
+    int M;
+    int at = block_prefix_excl<MM_GIF_CUT_BLOCK>(mine, tid, scan_sh, M);      // (its barriers also publish the boxes)
     for (int j = 0; j < PER; ++j) {
         const int bin = tid * PER + j;
         if ((unsigned)hist[2 * bin] != 0u) ent_bin[at++] = (unsigned short)bin;
     }
     __syncthreads();
-    int M = 0;
-    for (int w = 0; w < MM_GIF_CUT_BLOCK / 64; ++w) M += wave_count[w];
     // entry j * 1024 + tid lives in this lane's registers from here on: bin | box << 16 (0xFFFF: no entry) and the bin's pixel count
     unsigned ent[PER], cnt[PER];
     {
@@ -379,38 +375,11 @@ __global__ __launch_bounds__(64) void gif_code_kernel(GifArgs a) {
     a.seg_bits[seg] = bits.finish();
 }
 
-// inclusive prefix sum of 64-bit values over the workgroup of 256; sh: 256 words.  Every lane calls it.
-__device__ inline unsigned long long gif_scan(unsigned long long v, int tid, unsigned long long* sh) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < MM_GIF_BLOCK; o <<= 1) {
-        const unsigned long long t = tid >= o ? sh[tid - o] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const unsigned long long r = sh[tid];
-    __syncthreads();
-    return r;
-}
-
 // ---- offsets: per frame, the segments' bit counts -> bit offsets, in place; the frame's length in the file -----------------------------
 __global__ __launch_bounds__(MM_GIF_BLOCK) void gif_bit_offsets_kernel(GifArgs a) {
-    __shared__ unsigned long long sh[MM_GIF_BLOCK];
-    __shared__ unsigned long long last;
+    __shared__ unsigned long long sh[block_scan_words<MM_GIF_BLOCK, unsigned long long>()];
     const int tid = threadIdx.x, frame = blockIdx.x;
-    unsigned long long* bits = a.seg_bits + (size_t)frame * a.segs;
-    unsigned long long carry = 0;
-    for (long long base = 0; base < a.segs; base += MM_GIF_BLOCK) {
-        const long long i = base + tid;
-        const unsigned long long v = i < a.segs ? bits[i] : 0;
-        const unsigned long long inc = gif_scan(v, tid, sh);
-        if (i < a.segs) bits[i] = carry + inc - v;
-        if (tid == MM_GIF_BLOCK - 1) last = inc;
-        __syncthreads();
-        carry += last;
-        __syncthreads();
-    }
+    const unsigned long long carry = array_scan<false, MM_GIF_BLOCK>(a.seg_bits + (size_t)frame * a.segs, a.segs, 0ull, tid, sh);
     if (tid == 0) {
         const long long len = (long long)((carry + 7) >> 3);
         a.frame_len[frame + 1] = 20 + len + (len + 254) / 255;
@@ -437,21 +406,11 @@ __global__ __launch_bounds__(MM_GIF_BLOCK) void gif_pack_kernel(GifArgs a) {
 
 // ---- place: the frames' lengths in frame_len[1..n] -> where each starts, frame_len[0..n]; the file's length ---------------------------
 __global__ __launch_bounds__(MM_GIF_BLOCK) void gif_place_kernel(GifArgs a) {
-    __shared__ unsigned long long sh[MM_GIF_BLOCK];
-    __shared__ unsigned long long last;
+    __shared__ long long sh[block_scan_words<MM_GIF_BLOCK, long long>()];
     const int tid = threadIdx.x;
-    unsigned long long carry = (unsigned long long)a.head;
     if (tid == 0) a.frame_len[0] = a.head;
-    for (int base = 0; base < a.n; base += MM_GIF_BLOCK) {
-        const int i = base + tid;
-        const unsigned long long inc = gif_scan(i < a.n ? (unsigned long long)a.frame_len[i + 1] : 0, tid, sh);
-        if (i < a.n) a.frame_len[i + 1] = (long long)(carry + inc);
-        if (tid == MM_GIF_BLOCK - 1) last = inc;
-        __syncthreads();
-        carry += last;
-        __syncthreads();
-    }
-    if (tid == 0) *a.total = (long long)carry + 1;
+    const long long carry = array_scan<true, MM_GIF_BLOCK>(a.frame_len + 1, a.n, (long long)a.head, tid, sh);
+    if (tid == 0) *a.total = carry + 1;
 }
 
 // ---- write ----------------------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_stream.h"                                        // block_scan_excl: the workgroup scan the encoders' array scans stand on
 
 #define MM_MIX_BLOCK 256
 #define MM_MIX_PER_THREAD 4                                   // float4s (or floats) per thread per chunk
@@ -159,30 +160,14 @@ __global__ __launch_bounds__(MM_MIX_BLOCK) void mix_bwd_kernel(MixArgs a) {
 // a read of a word that integer atomics of this workgroup have changed: at agent scope, so it is served by L2 (where atomics land)
 __device__ inline int ld_l2(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// inclusive scan of v over the workgroup's 1024 threads (Hillis-Steele in LDS); every thread gets its own prefix
-__device__ inline int block_scan_incl(int v, int* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < MM_RS_BLOCK; d <<= 1) {
-        const int x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    const int r = sh[t];
-    __syncthreads();
-    return r;
-}
-
-// offs (B+1): exclusive prefix of the counts cur (B) holds on entry; cur is left equal to offs[0..B)
+// offs (B+1): exclusive prefix of the counts cur (B) holds on entry; cur is left equal to offs[0..B).  sh: as block_scan_excl wants it
 __device__ inline void counts_to_offsets(int B, int* cur, int* offs, int* sh) {
     const int t = threadIdx.x;
     const int per = (B + MM_RS_BLOCK - 1) / MM_RS_BLOCK;
     const int lo = min(B, t * per), hi = min(B, lo + per);
-    int sum = 0;
+    int sum = 0, total;
     for (int i = lo; i < hi; ++i) sum += ld_l2(&cur[i]);
-    int run = block_scan_incl(sum, sh) - sum;
+    int run = block_scan_excl<MM_RS_BLOCK>(sum, t, sh, total);
     for (int i = lo; i < hi; ++i) {
         const int c = ld_l2(&cur[i]);
         offs[i] = run;
@@ -196,7 +181,7 @@ __device__ inline void counts_to_offsets(int B, int* cur, int* offs, int* sh) {
 // (list_b), ascending in j; indices outside [0, B) are left out.  One workgroup.
 __global__ __launch_bounds__(MM_RS_BLOCK) void mix_lists_kernel(int B, const int* __restrict__ ia, const int* __restrict__ ib, int* offs_a,
                                                                 int* list_a, int* cur_a, int* offs_b, int* list_b, int* cur_b) {
-    __shared__ int sh[MM_RS_BLOCK];
+    __shared__ int sh[block_scan_words<MM_RS_BLOCK, int>()];
     __shared__ int ka_s[MM_RS_BLOCK], kb_s[MM_RS_BLOCK];
     const int t = threadIdx.x;
     for (int i = t; i < B; i += MM_RS_BLOCK) { cur_a[i] = 0; cur_b[i] = 0; }
@@ -246,7 +231,7 @@ __global__ __launch_bounds__(MM_RS_BLOCK) void collapse_resample_kernel(int B, i
     MM_FP_EXACT
     __shared__ uint64_t good_w[MM_RS_WORDS];
     __shared__ int pre[MM_RS_WORDS + 1];
-    __shared__ int sh[MM_RS_BLOCK];
+    __shared__ int sh[block_scan_words<MM_RS_BLOCK, int>()];
     const int t = threadIdx.x, lane = t & (MM_WAVE - 1);
     const int nwords = (B + MM_WAVE - 1) / MM_WAVE;
     for (int base = 0; base < nwords * MM_WAVE; base += MM_RS_BLOCK) {
@@ -262,9 +247,10 @@ __global__ __launch_bounds__(MM_RS_BLOCK) void collapse_resample_kernel(int B, i
     }
     __syncthreads();
     const int cnt = t < nwords ? __popcll(good_w[t]) : 0;      // nwords <= 1024: one word per thread
-    const int incl = block_scan_incl(cnt, sh);
-    if (t < nwords) pre[t] = incl - cnt;
-    if (t == MM_RS_BLOCK - 1) pre[nwords] = incl;
+    int total;
+    const int excl = block_scan_excl<MM_RS_BLOCK>(cnt, t, sh, total);
+    if (t < nwords) pre[t] = excl;
+    if (t == MM_RS_BLOCK - 1) pre[nwords] = total;
     __syncthreads();
     const int n_good = pre[nwords];
     if (t == 0) *n_bad = B - n_good;

@@ -23,7 +23,8 @@
 //             int16 in zigzag order, 16 bytes per lane.  The edges are clamped indices: nothing is padded in memory.
 //   count     one lane per block walks its 64 coefficients and writes the block's exact bit count.  The DC difference needs the previous
 //             block of the same component only, which is in memory already: no lane waits for another.
-//   offsets   one workgroup per frame scans the counts in MCU order: every block's bit offset, the frame's bits.
+//   offsets   one workgroup per frame scans the counts in MCU order: every block's bit offset, the frame's bits.  (This scan, place's and
+//             files' are array_scan of mm_stream.h, the loop the GIF encoder's scans share: 256 elements a pass behind a running carry.)
 //   pack      one lane per block walks again and ORs its codes into the frame's zeroed stream, big-endian 32-bit words.  Only a block's
 //             first and last word are shared with its neighbours (atomic OR, integer: the result is the same in any order), the words
 //             between them are stored plainly.
@@ -40,6 +41,7 @@
 
 #include "mm_device.h"
 #include "mm_quant.h"                                         // unquant: the v / 255 of as_float, shared with the exports
+#include "mm_stream.h"                                        // array_scan, Carve: what the encoders share
 
 #define MM_JPG_BLOCK 256
 #define MM_JPG_BLOCK_WORDS (MM_JPEG_BLOCK_BYTES / 4)
@@ -56,7 +58,6 @@ struct JpegLayout {
     size_t file_cap;                                          // bytes kept for one file
     size_t offsets, files, coef, bits, frame_bits, raw, chunk_ff, bytes;      // byte offsets into the workspace
 };
-__host__ inline size_t jpeg_up(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ JpegLayout jpeg_layout(const MMJpegDesc* d) {
     JpegLayout l;
     l.my = (d->H + 15) / 16; l.mx = (d->W + 15) / 16;
@@ -64,14 +65,15 @@ __host__ JpegLayout jpeg_layout(const MMJpegDesc* d) {
     l.chunks = (int)(((size_t)l.blocks * MM_JPEG_BLOCK_BYTES + MM_JPEG_CHUNK_BYTES - 1) / MM_JPEG_CHUNK_BYTES);
     l.file_cap = (size_t)d->header_bytes + 2 * (size_t)l.chunks * MM_JPEG_CHUNK_BYTES + 2;
     const size_t n = (size_t)d->n;
-    l.offsets = 0;
-    l.files = jpeg_up((n + 1) * 8);
-    l.coef = l.files + jpeg_up(n * l.file_cap);
-    l.bits = l.coef + jpeg_up(n * l.blocks * 128);
-    l.frame_bits = l.bits + jpeg_up(n * l.blocks * 4);
-    l.raw = l.frame_bits + jpeg_up(n * 4);
-    l.chunk_ff = l.raw + jpeg_up(n * l.chunks * MM_JPEG_CHUNK_BYTES);
-    l.bytes = l.chunk_ff + jpeg_up(n * l.chunks * 4);
+    Carve c;
+    l.offsets = c.take((n + 1) * 8);
+    l.files = c.take(n * l.file_cap);
+    l.coef = c.take(n * l.blocks * 128);
+    l.bits = c.take(n * l.blocks * 4);
+    l.frame_bits = c.take(n * 4);
+    l.raw = c.take(n * l.chunks * MM_JPEG_CHUNK_BYTES);
+    l.chunk_ff = c.take(n * l.chunks * 4);
+    l.bytes = c.at;
     return l;
 }
 size_t jpeg_workspace_bytes(const MMJpegDesc* d) { return jpeg_layout(d).bytes; }
@@ -87,24 +89,6 @@ struct JpegArgs {
 };
 
 // ---- small pieces ------------------------------------------------------------------------------------------------------------------
-// exclusive prefix sum over the workgroup of 256 (total in every lane); every lane of the workgroup calls it.  sh: 4 ints.
-__device__ inline int block_prefix_excl(int v, int tid, int* sh, int& total) {
-    int wave_total;
-    const int e = wave_prefix_excl(v, tid & 63, wave_total);
-    __syncthreads();                                          // (sh may still be read from the call before)
-    if ((tid & 63) == 0) sh[tid >> 6] = wave_total;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < MM_JPG_BLOCK / 64; ++w) {
-        const int x = sh[w];
-        base += w < (tid >> 6) ? x : 0;
-        total += x;
-    }
-    return e + base;
-}
-
 // natural index -> position in zigzag order
 __device__ const unsigned char jpeg_zigzag_pos[64] = {
     0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
@@ -301,17 +285,9 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_code_kernel(JpegArgs a) {
 
 // ---- offsets: per frame, the blocks' bit counts -> bit offsets, in place ------------------------------------------------------------
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_bit_offsets_kernel(JpegArgs a) {
-    __shared__ int sh[4];
+    __shared__ unsigned sh[block_scan_words<MM_JPG_BLOCK, unsigned>()];
     const int tid = threadIdx.x, img = blockIdx.x;
-    unsigned* bits = a.bits + (size_t)img * a.blocks;
-    unsigned carry = 0;
-    for (int base = 0; base < a.blocks; base += MM_JPG_BLOCK) {
-        const int i = base + tid;
-        int total;
-        const int e = block_prefix_excl(i < a.blocks ? (int)bits[i] : 0, tid, sh, total);
-        if (i < a.blocks) bits[i] = carry + (unsigned)e;
-        carry += (unsigned)total;
-    }
+    const unsigned carry = array_scan<false, MM_JPG_BLOCK>(a.bits + (size_t)img * a.blocks, a.blocks, 0u, tid, sh);
     // (a block of valid tables codes to 64 * 26 bits at most, so the sum fits; the clamp keeps every later index inside the frame's room whatever the tables)
     if (tid == 0) a.frame_bits[img] = min(carry, (unsigned)a.chunks * (MM_JPEG_CHUNK_BYTES * 8u));
 }
@@ -343,46 +319,23 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_count_ff_kernel(JpegArgs a)
         c = jpeg_count_ff(w, nb);
     }
     int total;
-    (void)block_prefix_excl(c, tid, sh, total);
+    (void)block_prefix_excl<MM_JPG_BLOCK>(c, tid, sh, total);
     if (tid == 0) a.chunk_ff[(size_t)img * a.chunks + chunk] = (unsigned)total;
 }
 
 // ---- place: per frame, the chunks' counts -> the stuffed bytes before each chunk, in place; the file's length -----------------------------
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_place_kernel(JpegArgs a) {
-    __shared__ int sh[4];
+    __shared__ unsigned sh[block_scan_words<MM_JPG_BLOCK, unsigned>()];
     const int tid = threadIdx.x, img = blockIdx.x;
-    unsigned* ff = a.chunk_ff + (size_t)img * a.chunks;
-    unsigned carry = 0;
-    for (int base = 0; base < a.chunks; base += MM_JPG_BLOCK) {
-        const int i = base + tid;
-        int total;
-        const int e = block_prefix_excl(i < a.chunks ? (int)ff[i] : 0, tid, sh, total);
-        if (i < a.chunks) ff[i] = carry + (unsigned)e;
-        carry += (unsigned)total;
-    }
+    const unsigned carry = array_scan<false, MM_JPG_BLOCK>(a.chunk_ff + (size_t)img * a.chunks, a.chunks, 0u, tid, sh);
     if (tid == 0) a.offsets[img + 1] = (long long)a.header_bytes + (((long long)a.frame_bits[img] + 7) >> 3) + carry + 2;
 }
 
 // ---- files: the lengths in offsets[1..n] -> offsets[0..n] -------------------------------------------------------------------------------
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_file_offsets_kernel(JpegArgs a) {
-    __shared__ long long sh[MM_JPG_BLOCK];
-    const int tid = threadIdx.x;
-    long long carry = 0;
-    if (tid == 0) a.offsets[0] = 0;
-    for (int base = 0; base < a.n; base += MM_JPG_BLOCK) {
-        const int i = base + tid;
-        sh[tid] = i < a.n ? a.offsets[i + 1] : 0;
-        __syncthreads();
-        for (int o = 1; o < MM_JPG_BLOCK; o <<= 1) {
-            const long long t = tid >= o ? sh[tid - o] : 0;
-            __syncthreads();
-            sh[tid] += t;
-            __syncthreads();
-        }
-        if (i < a.n) a.offsets[i + 1] = carry + sh[tid];
-        carry += sh[MM_JPG_BLOCK - 1];
-        __syncthreads();
-    }
+    __shared__ long long sh[block_scan_words<MM_JPG_BLOCK, long long>()];
+    if (threadIdx.x == 0) a.offsets[0] = 0;
+    (void)array_scan<true, MM_JPG_BLOCK>(a.offsets + 1, a.n, 0LL, threadIdx.x, sh);
 }
 
 // ---- write: header, stuffed bytes, EOI ----------------------------------------------------------------------------------------------
@@ -401,7 +354,7 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_write_kernel(JpegArgs a) {
     const int nb = byte0 < len ? (int)min(len - byte0, 4LL) : 0;
     const unsigned w = nb ? a.raw[((size_t)img * a.chunks + chunk) * MM_JPG_CHUNK_WORDS + tid] : 0u;
     int total;
-    const int before = block_prefix_excl(jpeg_count_ff(w, nb), tid, sh, total);
+    const int before = block_prefix_excl<MM_JPG_BLOCK>(jpeg_count_ff(w, nb), tid, sh, total);
     unsigned char* p = dst + a.header_bytes + byte0 + a.chunk_ff[(size_t)img * a.chunks + chunk] + before;
     for (int i = 0; i < nb; ++i) {
         const unsigned b = (w >> (24 - 8 * i)) & 0xFFu;
@@ -533,7 +486,7 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_idct_kernel(JpegDecArgs a) 
 
 // ---- pixels: upsample, convert, store -----------------------------------------------------------------------------------------------
 // the upsampled chroma sample at (y, x) of one component's plane c (cw bytes a row)
-__device__ inline int jpeg_upsampled(const JpegDecArgs& a, const unsigned char* c, size_t cw, int y, int x) {
+__device__ inline int jpeg_chroma_up(const JpegDecArgs& a, const unsigned char* c, size_t cw, int y, int x) {
     const int r = y >> 1, cx = x >> 1;
     const unsigned char* p = c + r * cw;
     if (a.wd <= 2) return p[cx];
@@ -551,7 +504,7 @@ __device__ inline unsigned jpeg_pixel(const JpegDecArgs& a, long long p, int& im
     const size_t cw = (size_t)a.mx * 8, cplane = (size_t)a.my * 8 * cw;
     const int Y = a.yp[((size_t)img * a.my * 16 + y) * (cw * 2) + x];
     const unsigned char* c = a.cp + (size_t)img * 2 * cplane;
-    const int cb = jpeg_upsampled(a, c, cw, y, x) - 128, cr = jpeg_upsampled(a, c + cplane, cw, y, x) - 128;
+    const int cb = jpeg_chroma_up(a, c, cw, y, x) - 128, cr = jpeg_chroma_up(a, c + cplane, cw, y, x) - 128;
     const int R = min(max(Y + ((91881 * cr + 32768) >> 16), 0), 255);
     const int G = min(max(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
     const int B = min(max(Y + ((116130 * cb + 32768) >> 16), 0), 255);
@@ -630,9 +583,11 @@ __host__ JpegRoundtripLayout jpeg_roundtrip_layout(const MMJpegRoundtripDesc* d)
     JpegRoundtripLayout l = {0, 0, 0, 256};                   // mode L needs no workspace; the query still answers 256, so that 0 stays its refusal
     if (d->mode != MM_JPEG_MODE_RGB) return l;
     const size_t n = (size_t)d->n, mcus = (size_t)((d->H + 15) / 16) * ((d->W + 15) / 16);
-    l.yp = l.coef + (d->coef ? 0 : jpeg_up(n * mcus * 6 * 128));
-    l.cp = l.yp + jpeg_up(n * mcus * 256);
-    l.bytes = l.cp + jpeg_up(n * mcus * 128);
+    Carve c;
+    l.coef = c.take(d->coef ? 0 : n * mcus * 6 * 128);
+    l.yp = c.take(n * mcus * 256);
+    l.cp = c.take(n * mcus * 128);
+    l.bytes = c.at;
     return l;
 }
 size_t jpeg_roundtrip_workspace_bytes(const MMJpegRoundtripDesc* d) { return jpeg_roundtrip_layout(d).bytes; }

@@ -38,8 +38,7 @@ def worst_bits(length):
 
 def workspace_bytes(n, H, W, segment=GIF_SEGMENT, loop=0, quantize_only=False):
     """mm_gif_query_workspace in Python: length | file | histogram | table | packed streams | bit offsets | frame offsets and bits | slots"""
-    def up(x):
-        return (x + 255) // 256 * 256
+    up = N.up256
     if quantize_only:
         return 256 + 32768 * 17
     pixels = H * W
@@ -128,10 +127,9 @@ def _launch(frames, n, H, W, segment, delay, loop, quantize_only):
         d.delays = N.ptr(keep[1])
     else:
         d.delay = delay
-    ws = N.workspace("mm_gif_query_workspace", d, dev)
-    want = workspace_bytes(n, H, W, segment, None if loop < 0 else loop, quantize_only)
-    if d.workspace_bytes != want or (not quantize_only and N.fn("mm_gif_file_offset")(d) != FILE_OFFSET):
-        raise RuntimeError("mm_gif_query_workspace gives %d bytes, gif.workspace_bytes %d" % (d.workspace_bytes, want))
+    want = (workspace_bytes(n, H, W, segment, None if loop < 0 else loop, quantize_only),) + (() if quantize_only else (FILE_OFFSET,))
+    ws = N.checked_workspace("mm_gif_query_workspace", d, dev, want, ("mm_gif_file_offset",)[:len(want) - 1],
+                             lambda got, want: "mm_gif_query_workspace gives %d bytes, gif.workspace_bytes %d" % (got[0], want[0]))
     N.call("mm_gif_encode", dev, d)
     del keep                                                             # (the allocator keeps it for the stream until the kernels are through)
     return palette, indices, ws
@@ -175,9 +173,4 @@ def encode_gif(frames, delay=10, loop=0, segment=None):
         raise ValueError("segment must be an int in 1..%d, got %r" % (MAX_SEGMENT, segment))
     N.require_device(frames)
     _, _, ws = _launch(frames, n, H, W, int(segment), delay, loop, False)
-    size = torch.empty((1,), dtype=torch.int64, pin_memory=True)
-    size.copy_(ws[:8].view(torch.int64))                                  # copy 1 (blocking): the file's length
-    total = int(size[0])
-    buf = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
-    buf.copy_(ws[FILE_OFFSET:FILE_OFFSET + total])                        # copy 2 (blocking): exactly the bytes used
-    return GifFile(buf)
+    return GifFile(N.read_back(ws, 1, FILE_OFFSET)[1])                    # two blocking copies: the file's length, exactly the bytes used

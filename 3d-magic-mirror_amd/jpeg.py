@@ -125,10 +125,7 @@ def lower_jpeg(H, W, quality=100):
     low = dict(H=H, W=W, quality=int(quality), qtables=q, divisors=8 * q, huffman=huffman_codes(), header=header, mcu_rows=my, mcu_cols=mx,
                blocks=blocks, chunks=chunks, stream_capacity=chunks * CHUNK_BYTES, file_capacity=len(header) + 2 * chunks * CHUNK_BYTES + 2,
                params=torch.from_numpy(params))
-
-    def up(x):
-        return (x + 255) // 256 * 256
-
+    up = N.up256
     # offsets (n + 1) int64 | the files | coefficients (int16 x 64 per block) | bits per block | bits per frame | the unstuffed streams | 0xFF per chunk
     low["files_offset"] = lambda n: up((n + 1) * 8)
     low["coef_offset"] = lambda n: up((n + 1) * 8) + up(n * low["file_capacity"])
@@ -173,22 +170,27 @@ class JpegBatch:
                 f.write(self._view[self.offsets[i]:self.offsets[i + 1]])
 
 
-def check_frames(frames, quality):
-    """the argument errors of ``encode_jpeg``, before anything touches a device: (n, H, W)"""
+def check_frames(frames, quality, layout="(...,H,W,3)"):
+    """the argument errors of ``encode_jpeg``, before anything touches a device: (n, H, W).  layout "(...,H,W)": the same for masks
+    (``jpeg_roundtrip``'s mode "L")"""
+    rgb = layout.endswith(",3)")
     if not torch.is_tensor(frames):
-        raise ValueError("frames must be a uint8 tensor (...,H,W,3), got %s" % type(frames))
+        raise ValueError("frames must be a uint8 tensor %s, got %s" % (layout, type(frames)))
     if frames.dtype != torch.uint8:
-        raise ValueError("frames must be uint8 (...,H,W,3), got %s: export_images makes 8-bit frames from float renders" % frames.dtype)
-    if frames.dim() < 3 or frames.shape[-1] != 3:
-        raise ValueError("frames must have shape (...,H,W,3), got %s" % (tuple(frames.shape),))
+        raise ValueError("frames must be uint8 %s, got %s: %s from float renders"
+                         % (layout, frames.dtype, "export_images makes 8-bit frames" if rgb else "export_images(x, 'mask') makes 8-bit masks"))
+    lead = frames.dim() - (3 if rgb else 2)                               # the leading dimensions
+    if lead < 0 or (rgb and frames.shape[-1] != 3):
+        raise ValueError("frames must have shape %s, got %s" % (layout, tuple(frames.shape),))
     if min(frames.shape) < 1:
         raise ValueError("an empty batch: frames of shape %s" % (tuple(frames.shape),))
-    if int(np.prod(frames.shape[:-3], dtype=np.int64)) > MAX_FRAMES:
+    n = int(np.prod(frames.shape[:lead], dtype=np.int64))
+    if n > MAX_FRAMES:
         raise ValueError("at most %d frames in a call, got shape %s" % (MAX_FRAMES, tuple(frames.shape)))
     if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or quality < 1 or quality > 100:
         raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
-    H, W = frames.shape[-3:-1]
-    return int(np.prod(frames.shape[:-3], dtype=np.int64)), int(H), int(W)
+    H, W = frames.shape[lead:lead + 2]
+    return n, int(H), int(W)
 
 
 @functools.lru_cache(maxsize=16)
@@ -227,24 +229,17 @@ def _launch_encode(x, n, low, with_coef=False):
     d = N.MMJpegDesc()
     d.n, d.H, d.W, d.header_bytes = n, H, W, len(low["header"])
     d.frames, d.params_host, d.params = N.ptr(x), ctypes.c_void_p(host.data_ptr()), N.ptr(par)
-    ws = N.workspace("mm_jpeg_query_workspace", d, dev)
-    got = (d.workspace_bytes, N.fn("mm_jpeg_files_offset")(d)) + ((N.fn("mm_jpeg_coef_offset")(d),) if with_coef else ())
     want = (low["workspace_bytes"](n), low["files_offset"](n)) + ((low["coef_offset"](n),) if with_coef else ())
-    if got != want:
-        raise RuntimeError("mm_jpeg_query_workspace gives %s (bytes, where the files start%s), lower_jpeg %s"
-                           % (got, ", where the coefficients do" if with_coef else "", want))
+    ws = N.checked_workspace("mm_jpeg_query_workspace", d, dev, want, ("mm_jpeg_files_offset", "mm_jpeg_coef_offset")[:len(want) - 1],
+                             lambda got, want: "mm_jpeg_query_workspace gives %s (bytes, where the files start%s), lower_jpeg %s"
+                             % (got, ", where the coefficients do" if with_coef else "", want))
     N.call("mm_jpeg_encode", dev, d)
     return ws
 
 
 def _collect(ws, n, low, lead):
-    """the files out of ``mm_jpeg_encode``'s workspace: a ``JpegBatch`` after two blocking copies"""
-    files_at = low["files_offset"](n)
-    off_host = torch.empty((n + 1,), dtype=torch.int64, pin_memory=True)
-    off_host.copy_(ws[:8 * (n + 1)].view(torch.int64))                     # copy 1 (blocking): the offsets
-    off = off_host.tolist()
-    buf = torch.empty((off[-1],), dtype=torch.uint8, pin_memory=True)
-    buf.copy_(ws[files_at:files_at + off[-1]])                            # copy 2 (blocking): exactly the bytes used
+    """the files out of ``mm_jpeg_encode``'s workspace: a ``JpegBatch`` after two blocking copies, the n + 1 offsets and the bytes used"""
+    off, buf = N.read_back(ws, n + 1, low["files_offset"](n))
     return JpegBatch(buf, off, lead)
 
 
@@ -260,20 +255,7 @@ def check_roundtrip(frames, quality, mode, files):
         return check_frames(frames, quality)
     if files:
         raise ValueError("files=True needs mode 'RGB': greyscale files are out of scope (the round trip of a mask forms no file)")
-    if not torch.is_tensor(frames):
-        raise ValueError("frames must be a uint8 tensor (...,H,W), got %s" % type(frames))
-    if frames.dtype != torch.uint8:
-        raise ValueError("frames must be uint8 (...,H,W), got %s: export_images(x, 'mask') makes 8-bit masks from float renders" % frames.dtype)
-    if frames.dim() < 2:
-        raise ValueError("frames must have shape (...,H,W), got %s" % (tuple(frames.shape),))
-    if min(frames.shape) < 1:
-        raise ValueError("an empty batch: frames of shape %s" % (tuple(frames.shape),))
-    if int(np.prod(frames.shape[:-2], dtype=np.int64)) > MAX_FRAMES:
-        raise ValueError("at most %d frames in a call, got shape %s" % (MAX_FRAMES, tuple(frames.shape)))
-    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or quality < 1 or quality > 100:
-        raise ValueError("quality must be an int in 1..100, got %r" % (quality,))
-    H, W = frames.shape[-2:]
-    return int(np.prod(frames.shape[:-2], dtype=np.int64)), int(H), int(W)
+    return check_frames(frames, quality, "(...,H,W)")
 
 
 def jpeg_roundtrip(frames, quality=100, mode="RGB", as_float=False, files=False):
@@ -317,10 +299,8 @@ def jpeg_roundtrip(frames, quality=100, mode="RGB", as_float=False, files=False)
     if files:
         enc = _launch_encode(x, n, low, with_coef=True)
         d.coef = enc.data_ptr() + low["coef_offset"](n)
-    ws = N.workspace("mm_jpeg_roundtrip_query_workspace", d, dev)
-    want = low["roundtrip_workspace_bytes"](n, mode, own_coef=not files)
-    if d.workspace_bytes != want:
-        raise RuntimeError("mm_jpeg_roundtrip_query_workspace gives %d bytes, lower_jpeg %d" % (d.workspace_bytes, want))
+    ws = N.checked_workspace("mm_jpeg_roundtrip_query_workspace", d, dev, (low["roundtrip_workspace_bytes"](n, mode, own_coef=not files),), (),
+                             lambda got, want: "mm_jpeg_roundtrip_query_workspace gives %d bytes, lower_jpeg %d" % (got[0], want[0]))
     N.call("mm_jpeg_roundtrip", dev, d)
     del ws                                                               # (the allocator keeps it for the stream until the kernels are through)
     return (out, _collect(enc, n, low, lead)) if files else out

@@ -276,7 +276,9 @@ def _cases():
     for nbytes in (254, 255, 256, 509, 510, 511):
         symbols, seg = stream_of(nbytes)
         c["stream of %d" % nbytes] = (as_frame(symbols), {"segment": seg})
-    for n in (1, 2, 257):
+    for nseg in (257, 513):                                              # more segments in a frame than a workgroup scans in one pass, twice over
+        c["%d segments" % nseg] = (as_frame(noise(4 * nseg, nseg) % 7 * 31).reshape(2, 1, 2 * nseg, 3), {"segment": 2})
+    for n in (1, 2, 257, 513):
         c["%d frames" % n] = (COLOURS[(np.arange(n * 6) * 7) % 256].reshape(n, 2, 3, 3), {})
     c["delays"] = (COLOURS[np.arange(4 * 6) % 256].reshape(4, 2, 3, 3), {"delay": [1, 20, 300, 65535], "loop": 3})
     c["no loop"] = (COLOURS[np.arange(2 * 6) % 256].reshape(2, 2, 3, 3), {"delay": 7, "loop": None})
@@ -327,7 +329,12 @@ def test_cases_reach_what_they_are_named_for():
     assert k["longest"] >= 44 and k["bump_before_clear"] == 0              # strings of 1, 2, 3, ... pixels: 44 * 45 / 2 < 1024
     for nbytes in (254, 255, 256, 509, 510, 511):
         assert counted("stream of %d" % nbytes)["stream_bytes"] == [nbytes]
-    assert len(counted("257 frames")["stream_bytes"]) == 257
+    for n in (257, 513):
+        assert len(counted("%d frames" % n)["stream_bytes"]) == n
+    for nseg in (257, 513):                                              # two frames: the second one's offsets restart behind a carry
+        frames, kw = CASES["%d segments" % nseg]
+        assert frames.shape[0] == 2 and (frames.shape[1] * frames.shape[2] + kw["segment"] - 1) // kw["segment"] == nseg
+        assert len(counted("%d segments" % nseg)["stream_bytes"]) == 2
 
 
 def run_case_without_pillow(name, counters):
