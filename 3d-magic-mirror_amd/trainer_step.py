@@ -171,22 +171,37 @@ class TrainerStep:
     def _u(self, *shape, lo=0.0, hi=1.0):
         return torch.rand(*shape, device=self.dev, generator=self.gen) * (hi - lo) + lo
 
-    def step(self, optimize=True):
+    def draws(self):
+        """The random draws of one iteration, taken from self.gen in the iteration's order: the sign and size of render #3's azimuths (as
+        ``azimuths90``, their product), the two permutations, the three lerp weights, then Ai's camera."""
+        o, Bn = self.opt, self.B
+        sign = torch.where(self._u(Bn) < 0.5, -1.0, 1.0)
+        d = {"sign": sign, "azimuths90": -self._u(Bn, lo=o.hard_range, hi=180.0 - o.hard_range) * sign}
+        d["ra"], d["rb"] = torch.randperm(Bn, device=self.dev, generator=self.gen), torch.randperm(Bn, device=self.dev, generator=self.gen)
+        d["a_s"], d["a_t"], d["a_l"] = self._u(Bn, 1, 1), self._u(Bn, 1, 1, 1), self._u(Bn, 1)
+        d["azimuths"] = -self._u(Bn, lo=-o.azi_scope / 2, hi=o.azi_scope / 2)
+        d["elevations"] = self._u(Bn, lo=self.netE.elev[0], hi=self.netE.elev[1])
+        d["distances"] = self._u(Bn, lo=self.netE.dist[0], hi=self.netE.dist[1])
+        d["biases"] = self._u(Bn, 2, lo=-o.bias_range, hi=o.bias_range)
+        return d
+
+    def iteration(self, Ae, encode, draws=None):
+        """Everything of the iteration between the encoder and the backward: the four renders, the critic, recon_data and the regularisers
+        on the attributes ``Ae`` (what netE(Xa) returned), with ``Aire = encode(Xir.detach().clone())`` and the random draws of ``draws()``
+        (taken here, after render #1, unless given).  Returns the loss terms, NOT detached, as a dict (loss, data, reg, flip, ic, fake) and
+        leaves the four attribute sets and the three images in ``self.last_sets``."""
         o, dr, Bn = self.opt, self.dr, self.B
-        self.optimizerE.zero_grad(set_to_none=True)
-        Ae = self.netE(self.Xa)
         if not self.many:
             Xer, Ae = self._render(0, Ae)                                                  # render #1
+        d = self.draws() if draws is None else draws
         Ae90 = deep_copy(Ae)
-        sign = torch.where(self._u(Bn) < 0.5, -1.0, 1.0)
-        Ae90["azimuths"] = -self._u(Bn, lo=o.hard_range, hi=180.0 - o.hard_range) * sign
-        ra, rb = torch.randperm(Bn, device=self.dev, generator=self.gen), torch.randperm(Bn, device=self.dev, generator=self.gen)
-        Aa, Ab = deep_copy(Ae, ra), deep_copy(Ae, rb)
-        a_s, a_t, a_l = self._u(Bn, 1, 1), self._u(Bn, 1, 1, 1), self._u(Bn, 1)
-        Ai = {"azimuths": -self._u(Bn, lo=-o.azi_scope / 2, hi=o.azi_scope / 2),
-              "elevations": self._u(Bn, lo=self.netE.elev[0], hi=self.netE.elev[1]),
-              "distances": self._u(Bn, lo=self.netE.dist[0], hi=self.netE.dist[1]),
-              "biases": self._u(Bn, 2, lo=-o.bias_range, hi=o.bias_range),
+        Ae90["azimuths"] = d["azimuths90"]
+        Aa, Ab = deep_copy(Ae, d["ra"]), deep_copy(Ae, d["rb"])
+        a_s, a_t, a_l = d["a_s"], d["a_t"], d["a_l"]
+        Ai = {"azimuths": d["azimuths"],
+              "elevations": d["elevations"],
+              "distances": d["distances"],
+              "biases": d["biases"],
               "vertices": a_s * Aa["vertices"] + (1 - a_s) * Ab["vertices"],
               "delta_vertices": a_s * Aa["delta_vertices"] + (1 - a_s) * Ab["delta_vertices"],
               "textures": a_t * Aa["textures"] + (1 - a_t) * Ab["textures"],
@@ -200,7 +215,7 @@ class TrainerStep:
         else:
             Xir, Ai = self._render(1, Ai)                                                  # render #2
             Xer90, Ae90 = self._render(2, Ae90) if o.hard else (Xer, Ae)                   # render #3
-        Aire = self.netE(Xir.detach().clone())
+        Aire = encode(Xir.detach().clone())
         if self.lean:
             Aire = dr.render_geometry(**Aire)                                              # render #4: its image is discarded (trainer.py:367)
         else:
@@ -218,12 +233,17 @@ class TrainerStep:
         lossR_data = o.lambda_data * dr.recon_data(Xer, self.Xa, no_mask=o.bg, contour=o.lambda_contour)
         lossR_reg, lossR_flip, lossR_IC = dr.regularization(Ae, Ai, Aire, o)
         lossR = lossR_fake + lossR_reg + lossR_flip + lossR_data + lossR_IC
-        lossR.backward()
+        self.last_sets = {"Ae": Ae, "Ae90": Ae90, "Ai": Ai, "Aire": Aire, "Xer": Xer, "Xir": Xir, "Xer90": Xer90}
+        return {"loss": lossR, "data": lossR_data, "reg": lossR_reg, "flip": lossR_flip, "ic": lossR_IC, "fake": lossR_fake}
+
+    def step(self, optimize=True):
+        self.optimizerE.zero_grad(set_to_none=True)
+        terms = self.iteration(self.netE(self.Xa), self.netE)
+        terms["loss"].backward()
         if optimize:
             self.optimizerE.step()
-        self.last = {"loss": lossR.detach(), "data": lossR_data.detach(), "reg": lossR_reg.detach(), "flip": lossR_flip.detach(),
-                     "ic": lossR_IC.detach(), "fake": lossR_fake.detach()}
-        return lossR.detach()
+        self.last = {k: v.detach() for k, v in terms.items()}
+        return self.last["loss"]
 
     def render_path_only(self):
         """The same four renders + recon_data + regularisers + backward on DETACHED attributes of the last netE output: the

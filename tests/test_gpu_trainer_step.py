@@ -1,7 +1,9 @@
 """BASELINE config 3 as written: the trainer-shaped step (ResNet-18 encoders on stock PyTorch-ROCm -> four renders in
 trainer.py's dependency order -> recon_data -> regularisers -> ONE backward -> Adam) around the HIP render path.
-There is nothing in the reference to compare a whole step against (no kaolin, no torchvision, no checkpoint): the
-checks are that the step runs at full size through the C ABI, that every encoder parameter that should receive gradient
+The iteration between the encoder and the backward is held to a float64 composition of the oracles in tests/test_gpu_iteration.py
+(losses, face_idx and every attribute gradient); the encoders and Adam are stock PyTorch and have no reference here (no kaolin, no
+torchvision, no checkpoint).  The checks in this file are
+that the step runs at full size through the C ABI, that every encoder parameter that should receive gradient
 does, that the image gradient reaches the rasteriser through all three image renders, and that a few Adam steps on a
 fixed batch reduce the reconstruction loss."""
 import importlib
