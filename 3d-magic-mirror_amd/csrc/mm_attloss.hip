@@ -24,16 +24,6 @@ struct AttArgs {
 __device__ inline float att_term(float d, int l1) { return l1 ? fabsf(d) : d * d; }
 __device__ inline float att_dterm(float d, int l1) { return l1 ? (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) : 2.f * d; }
 
-__device__ inline float block_sum4(float v, float* s_red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
-
-#define MM_DEG2RAD_F 0.017453292519943295f
-
 __global__ __launch_bounds__(256) void att_fwd_kernel(AttArgs a) {
     __shared__ float s_red[4];
     __shared__ int s_last;
@@ -69,40 +59,31 @@ __global__ __launch_bounds__(256) void att_fwd_kernel(AttArgs a) {
             for (; i < n; i += gstride) s += att_term(a.p_te[i] - a.t_te[i], a.l1);
         }
     }
-    part[5] = block_sum4(s, s_red);
+    part[5] = block_sum(s, s_red);
     s = 0.f;
     for (size_t i = gid; i < (size_t)a.B * a.V * 3; i += gstride) s += att_term(a.p_ve[i] - a.t_ve[i], a.l1);
-    part[4] = block_sum4(s, s_red);
+    part[4] = block_sum(s, s_red);
     if (blockIdx.x == 0) {                                        // the small ones
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s6 = 0.f;
         for (int i = tid; i < a.B; i += 256) {
-            const float pa = a.p_az[i] * MM_DEG2RAD_F, ta = a.t_az[i] * MM_DEG2RAD_F;
+            const float pa = a.p_az[i] * MM_DEG2RAD, ta = a.t_az[i] * MM_DEG2RAD;
             s0 += att_term(cosf(pa) - cosf(ta), a.l1) + att_term(sinf(pa) - sinf(ta), a.l1);
-            const float pe = a.p_el[i] * MM_DEG2RAD_F, te = a.t_el[i] * MM_DEG2RAD_F;
+            const float pe = a.p_el[i] * MM_DEG2RAD, te = a.t_el[i] * MM_DEG2RAD;
             s1 += att_term(cosf(pe) - cosf(te), a.l1) + att_term(sinf(pe) - sinf(te), a.l1);
             s2 += att_term(a.p_di[i] - a.t_di[i], a.l1);
         }
         for (int i = tid; i < a.B * 2; i += 256) s3 += att_term(a.p_bi[i] - a.t_bi[i], a.l1);
         for (int i = tid; i < a.B * 9; i += 256) s6 += att_term(a.p_li[i] - a.t_li[i], a.l1);
-        part[0] = block_sum4(s0, s_red); part[1] = block_sum4(s1, s_red); part[2] = block_sum4(s2, s_red);
-        part[3] = block_sum4(s3, s_red); part[6] = block_sum4(s6, s_red);
+        part[0] = block_sum(s0, s_red); part[1] = block_sum(s1, s_red); part[2] = block_sum(s2, s_red);
+        part[3] = block_sum(s3, s_red); part[6] = block_sum(s6, s_red);
     }
     if (tid < 7) {
         float mine = 0.f;
 #pragma unroll
         for (int k = 0; k < 7; ++k) if (k == tid) mine = part[k];
-        const float old = __hip_atomic_exchange(a.partial + (size_t)blockIdx.x * 8 + tid, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("" :: "v"(old));                            // returning: performed before the ticket below (see vertex_bwd)
+        publish_exchange(a.partial + (size_t)blockIdx.x * 8 + tid, mine);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned prev = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = prev == gridDim.x - 1;
-        if (s_last) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!last_workgroup(a.ticket, gridDim.x, true, s_last)) return;     // (the hand-off: mm_device.h)
     // the last workgroup adds the partials up: rows strided over its 256 threads (seven agent-scope loads per row, all rows of a thread in
     // flight together), then a fixed-order block reduction -- reproducible run to run.  (Seven threads walking the up to 1024 rows one
     // dependent load after the other took 140 of this kernel's 155 us.)
@@ -113,7 +94,7 @@ __global__ __launch_bounds__(256) void att_fwd_kernel(AttArgs a) {
     }
     float tot = 0.f;
 #pragma unroll
-    for (int k = 0; k < 7; ++k) { const float t = block_sum4(acc[k], s_red); if (k == tid) tot = t; }
+    for (int k = 0; k < 7; ++k) { const float t = block_sum(acc[k], s_red); if (k == tid) tot = t; }
     if (tid >= 7) return;
     const float n[7] = {(float)a.B * 2.f, (float)a.B * 2.f, (float)a.B, (float)a.B * 2.f, (float)a.B * (float)a.V * 3.f,
                         (float)a.B * (float)a.T, (float)a.B * 9.f};
@@ -143,14 +124,14 @@ __global__ __launch_bounds__(256) void att_bwd_kernel(AttArgs a) {
     for (int i = tid; i < a.B; i += 256) {
         // angle2xy: d/d angle[deg] of term(cos - cos_t) + term(sin - sin_t)
         const float ca = w[0] / ((float)a.B * 2.f), ce = w[1] / ((float)a.B * 2.f);
-        const float pa = a.p_az[i] * MM_DEG2RAD_F, ta = a.t_az[i] * MM_DEG2RAD_F;
+        const float pa = a.p_az[i] * MM_DEG2RAD, ta = a.t_az[i] * MM_DEG2RAD;
         const float dc = att_dterm(cosf(pa) - cosf(ta), a.l1), ds = att_dterm(sinf(pa) - sinf(ta), a.l1);
-        if (a.g_az) a.g_az[i] = ca * (dc * (-sinf(pa)) + ds * cosf(pa)) * MM_DEG2RAD_F;
-        if (a.h_az) a.h_az[i] = ca * (dc * sinf(ta) - ds * cosf(ta)) * MM_DEG2RAD_F;
-        const float pe = a.p_el[i] * MM_DEG2RAD_F, te = a.t_el[i] * MM_DEG2RAD_F;
+        if (a.g_az) a.g_az[i] = ca * (dc * (-sinf(pa)) + ds * cosf(pa)) * MM_DEG2RAD;
+        if (a.h_az) a.h_az[i] = ca * (dc * sinf(ta) - ds * cosf(ta)) * MM_DEG2RAD;
+        const float pe = a.p_el[i] * MM_DEG2RAD, te = a.t_el[i] * MM_DEG2RAD;
         const float ec = att_dterm(cosf(pe) - cosf(te), a.l1), es = att_dterm(sinf(pe) - sinf(te), a.l1);
-        if (a.g_el) a.g_el[i] = ce * (ec * (-sinf(pe)) + es * cosf(pe)) * MM_DEG2RAD_F;
-        if (a.h_el) a.h_el[i] = ce * (ec * sinf(te) - es * cosf(te)) * MM_DEG2RAD_F;
+        if (a.g_el) a.g_el[i] = ce * (ec * (-sinf(pe)) + es * cosf(pe)) * MM_DEG2RAD;
+        if (a.h_el) a.h_el[i] = ce * (ec * sinf(te) - es * cosf(te)) * MM_DEG2RAD;
         att_grad_store(a.g_di, a.h_di, i, (w[2] / (float)a.B) * att_dterm(a.p_di[i] - a.t_di[i], a.l1));
     }
     for (int i = tid; i < a.B * 2; i += 256) att_grad_store(a.g_bi, a.h_bi, i, (w[3] / ((float)a.B * 2.f)) * att_dterm(a.p_bi[i] - a.t_bi[i], a.l1));

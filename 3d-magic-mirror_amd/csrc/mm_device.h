@@ -643,43 +643,94 @@ __device__ inline float loss_contour_total(const long long* ltot, int b) {
     return (float)s3 * (1.f / 4294967296.f);
 }
 
-// Wave-wide sum / max, the result in every lane.  Four DPP steps (VALU cross-lane operands: no LDS crossbar traffic, no
-// ds_bpermute latency chain) leave every 16-lane row holding its own total; the four row totals are read as scalars.  Fixed order.
-template <int CTRL>
-__device__ inline float dpp_move(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false)); }
-__device__ inline float row16_sum(float v) {
-    v += dpp_move<0xB1>(v);        // quad_perm [1,0,3,2]
-    v += dpp_move<0x4E>(v);        // quad_perm [2,3,0,1]
-    v += dpp_move<0x141>(v);       // row_half_mirror
-    v += dpp_move<0x140>(v);       // row_mirror
-    return v;
+// ---- reductions: one wave fold, one workgroup sum, one last-workgroup hand-off ----------------------------------------------------
+// Wave-wide fold of a 32-bit value, the result in every lane.  Four DPP steps (VALU cross-lane operands: no LDS crossbar traffic, no
+// ds_bpermute latency chain) leave every 16-lane row holding its own result; the four rows' are read as scalars and combined as
+// (r0 . r1) . (r2 . r3).  Fixed order: a float sum is the same bits run to run.
+template <int CTRL, typename T>
+__device__ inline T dpp_move(T v) { return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false)); }
+template <typename T>
+__device__ inline T lane_value(T v, int lane) { return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
+template <typename T, typename Op>
+__device__ inline T wave_reduce(T v, Op op) {
+    v = op(v, dpp_move<0xB1>(v));        // quad_perm [1,0,3,2]
+    v = op(v, dpp_move<0x4E>(v));        // quad_perm [2,3,0,1]
+    v = op(v, dpp_move<0x141>(v));       // row_half_mirror
+    v = op(v, dpp_move<0x140>(v));       // row_mirror
+    return op(op(lane_value(v, 0), lane_value(v, 16)), op(lane_value(v, 32), lane_value(v, 48)));
 }
-__device__ inline float lane_value(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-__device__ inline float wave_sum(float v) {
-    v = row16_sum(v);
-    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
-}
-__device__ inline int wave_max_i32(int v) {                      // (same four DPP steps; the result in every lane)
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false)); v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false)); v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false));
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-__device__ inline unsigned wave_min_u32(unsigned v) {
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false)); v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false)); v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false));
-    return min(min((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
-               min((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
-}
-__device__ inline unsigned wave_or_u32(unsigned v) {
-    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false); v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
-    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false); v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);
-    return ((unsigned)__builtin_amdgcn_readlane((int)v, 0) | (unsigned)__builtin_amdgcn_readlane((int)v, 16)) |
-           ((unsigned)__builtin_amdgcn_readlane((int)v, 32) | (unsigned)__builtin_amdgcn_readlane((int)v, 48));
-}
+__device__ inline float wave_sum(float v) { return wave_reduce(v, [](float a, float b) { return a + b; }); }
+__device__ inline float wave_max(float v) { return wave_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
+__device__ inline int wave_max_i32(int v) { return wave_reduce(v, [](int a, int b) { return max(a, b); }); }
+__device__ inline unsigned wave_min_u32(unsigned v) { return wave_reduce(v, [](unsigned a, unsigned b) { return min(a, b); }); }
+__device__ inline unsigned wave_or_u32(unsigned v) { return wave_reduce(v, [](unsigned a, unsigned b) { return a | b; }); }
 __device__ inline uint64_t wave_or_u64(uint64_t v) { return ((uint64_t)wave_or_u32((unsigned)(v >> 32)) << 32) | wave_or_u32((unsigned)v); }
-__device__ inline float wave_max(float v) {
-    v = fmaxf(v, dpp_move<0xB1>(v)); v = fmaxf(v, dpp_move<0x4E>(v)); v = fmaxf(v, dpp_move<0x141>(v)); v = fmaxf(v, dpp_move<0x140>(v));
-    return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
+
+// Fixed-order sum over a workgroup of FOUR waves, the total in every thread: the wave fold, then ((w0 + w1) + w2) + w3.  s_red: four
+// floats of LDS that the call before may still be reading (hence the barrier in front).
+__device__ inline float block_sum(float v, float* s_red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+// ... and K sums at once over a workgroup of NW waves behind ONE barrier: lane 0 of every wave parks its K wave sums, thread k < K gets the
+// total of v[k] (every other thread 0).  Four waves add ((w0 + w1) + w2) + w3; sixteen add 0.f + w0 + ... + w15 -- not the same thing for a
+// sum of negative zeros (0.f + -0.f = +0.f), and every caller's outputs are pinned to the bit, so each wave count keeps its form.  s_red
+// must be idle on entry (no barrier in front).
+template <int NW, int K>
+__device__ inline float block_sum_wide(const float (&v)[K], float (&s_red)[NW][K]) {
+    static_assert(NW == 4 || NW == 16, "one fixed order per wave count");
+    const int tid = threadIdx.x;
+    float s[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = wave_sum(v[k]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) s_red[tid >> 6][k] = s[k];
+    }
+    __syncthreads();
+    if (tid >= K) return 0.f;
+    if constexpr (NW == 4) return ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    float total = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) total += s_red[w][tid];
+    return total;
+}
+
+// The last-workgroup hand-off: every workgroup of a group publishes its partial results, and the one that arrives LAST folds them all.
+// Every thread of the workgroup calls last_workgroup() after its publishing stores; it returns true in the last of `arrivals` workgroups
+// to draw from *ticket (zero before the first draws).  What makes that workgroup's loads see every other's partials, WITHOUT a fence:
+//   * the partials are published WRITE-THROUGH at agent scope (sc1: they land at the memory side, not in the storing XCD's L2) -- a relaxed
+//     agent-scope __hip_atomic_store, or publish_exchange() below -- and the folding workgroup reads them with relaxed agent-scope
+//     __hip_atomic_load (sc1: past its own L1).  An agent-scope release fence would write back the XCD's WHOLE L2 and an acquire would
+//     invalidate it, once per workgroup: without them vertex_bwd went from 213 to 53 us at B=384.
+//   * every wave drains its own stores (s_waitcnt vmcnt(0)) BEFORE the barrier, so that when thread 0 leaves the barrier every publishing
+//     store of the workgroup has been acknowledged; only then is the ticket drawn.  The drain is an asm with a "memory" clobber: the
+//     compiler moves no store across it.
+//   * publish_exchange is a RETURNING atomic: its old value only comes back once the write has been performed at the memory side, and
+//     pinning that value in a register (the empty asm) keeps the compiler from turning it into a non-returning one, which vmcnt would not
+//     wait to see performed.
+//   * the ticket is a relaxed agent-scope fetch_add performed at the memory side, where all draws are ordered: the draw that returns
+//     arrivals - 1 comes after every other workgroup's draw, hence after their drained partials.
+//   * the second barrier hands thread 0's verdict (s_last, LDS) to the workgroup.
+// reset: the last workgroup puts the ticket back to zero at once -- every workgroup has drawn by then, so nobody can see the zero as a
+// fresh count, and a workspace zero-filled once serves every later call on the stream.  A caller whose ticket is cleared elsewhere passes false.
+__device__ inline void publish_exchange(float* p, float v) {
+    const float old = __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("" :: "v"(old));
+}
+__device__ inline bool last_workgroup(unsigned* ticket, unsigned arrivals, bool reset, int& s_last) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = prev == arrivals - 1;
+        if (reset && s_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    return s_last != 0;
 }
 
 }  // namespace mm

@@ -61,10 +61,9 @@ __global__ __launch_bounds__(256) void recon_partial_kernel(LossArgs a) {
             cs += (cp - cg) * (cp - cg);
         }
     }
-    l1 = wave_sum(l1); up = wave_sum(up); down = wave_sum(down); cs = wave_sum(cs);
-    if ((tid & 63) == 0) { s_red[tid >> 6][0] = l1; s_red[tid >> 6][1] = up; s_red[tid >> 6][2] = down; s_red[tid >> 6][3] = cs; }
-    __syncthreads();
-    if (tid < 4) a.partial[((size_t)b * MM_LOSS_CHUNKS + chunk) * 4 + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    const float sums[4] = {l1, up, down, cs};
+    const float total = block_sum_wide(sums, s_red);
+    if (tid < 4) a.partial[((size_t)b * MM_LOSS_CHUNKS + chunk) * 4 + tid] = total;
 }
 
 __global__ __launch_bounds__(64) void recon_final_kernel(LossArgs a) {

@@ -140,14 +140,8 @@ __global__ __launch_bounds__(256) void prepare_bwd_kernel(MMPrepareDesc d, MMPre
         }
     }
     if (!g.grad_transform) return;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = wave_sum(acc[i]);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s_red[tid >> 6][i] = acc[i];
-    }
-    __syncthreads();
-    if (tid < 12) ((float*)d.workspace)[((size_t)b * gridDim.x + blockIdx.x) * 12 + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    const float total = block_sum_wide(acc, s_red);
+    if (tid < 12) ((float*)d.workspace)[((size_t)b * gridDim.x + blockIdx.x) * 12 + tid] = total;
 }
 
 // The vertex -> corner CSR of a face list, on the device (mm_build_vertex_corner_csr_device): ONE workgroup -- histogram of the corners'
@@ -457,18 +451,8 @@ __global__ __launch_bounds__(1024) void sh_bwd_lights_kernel(MMShDesc d, MMShGra
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const float s = wave_sum(acc[i]);
-        if ((tid & 63) == 0) s_red[tid >> 6][i] = s;
-    }
-    __syncthreads();
-    if (tid < 9) {
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) s += s_red[w][tid];
-        g.grad_lights[b * 9 + tid] = s;
-    }
+    const float total = block_sum_wide(acc, s_red);
+    if (tid < 9) g.grad_lights[b * 9 + tid] = total;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -480,15 +464,9 @@ __global__ __launch_bounds__(1024) void mask_iou_sums_kernel(MMMaskIouDesc d) {
     const float* l = d.lhs + (size_t)b * d.N; const float* r = d.rhs + (size_t)b * d.N;
     float up = 0.f, down = 0.f;
     for (int i = tid; i < d.N; i += 1024) { const float mul = l[i] * r[i]; up += mul; down += (l[i] + r[i]) - mul; }
-    up = wave_sum(up); down = wave_sum(down);
-    if ((tid & 63) == 0) { s_red[tid >> 6][0] = up; s_red[tid >> 6][1] = down; }
-    __syncthreads();
-    if (tid < 2) {
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) s += s_red[w][tid];
-        d.sums[b * 2 + tid] = s;
-    }
+    const float sums[2] = {up, down};
+    const float total = block_sum_wide(sums, s_red);
+    if (tid < 2) d.sums[b * 2 + tid] = total;
 }
 
 __global__ __launch_bounds__(64) void mask_iou_final_kernel(MMMaskIouDesc d) {

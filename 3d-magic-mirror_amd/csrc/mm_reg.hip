@@ -37,15 +37,6 @@ struct RegArgs {
     float *g_vertices, *g_delta, *g_fn;
 };
 
-// fixed-order sum over the workgroup (4 waves): butterfly inside a wave, then waves 0..3 in order; every thread gets the total
-__device__ inline float block_sum(float v, float* s_red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
-
 __device__ inline float depth_weight(const RegArgs& a, int term, float x, float y) {
     const float yr = y / a.ratio;
     const float r2 = x * x + yr * yr;
@@ -145,25 +136,14 @@ __global__ __launch_bounds__(256) void mesh_reg_fwd_kernel(RegArgs a) {
         part[MM_REG_FLIP] = block_sum(s, s_red);
     }
 
-    // per-image partial sums -> the last workgroup to arrive adds them up in image order.  Agent-scope atomic stores / loads
-    // and a returning ticket: no L2-wide fence (see vertex_bwd).
+    // per-image partial sums -> the last workgroup to arrive adds them up in image order (the hand-off: mm_device.h, last_workgroup)
     if (tid < MM_REG_TERMS && (group >> tid & 1u)) {
         float mine = 0.f;
 #pragma unroll
         for (int k = 0; k < MM_REG_TERMS; ++k) if (k == tid) mine = part[k];
-        // RETURNING exchange: its value only comes back once the write has been performed at the memory side
-        const float old = __hip_atomic_exchange(a.partial + b * MM_REG_TERMS + tid, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("" :: "v"(old));
+        publish_exchange(a.partial + b * MM_REG_TERMS + tid, mine);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned prev = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = prev == gridDim.x * gridDim.y - 1;
-        if (s_last) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!last_workgroup(a.ticket, gridDim.x * gridDim.y, true, s_last)) return;   // (ticket back to zero: ready for the next call)
     // the partials of all images, fetched by all threads at once (image = thread index, 256 per pass), parked in LDS and added up by one
     // thread per term in image order: bitwise reproducible, one trip to memory instead of B
     __shared__ float s_part[256][MM_REG_TERMS + 1];

@@ -141,6 +141,7 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_tile_kernel(SsimIn X, SsimIn 
         }
     }
     if (BWD) return;
+    // (not block_sum_wide: this tile sum adds its waves as a tree, (w0 + w1) + (w2 + w3), and the SSIM values are pinned to that order)
     s_sum = wave_sum(s_sum);
     c_sum = wave_sum(c_sum);
     if ((tid & 63) == 0) { red[tid >> 6][0] = s_sum; red[tid >> 6][1] = c_sum; }

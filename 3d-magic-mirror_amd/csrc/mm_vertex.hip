@@ -288,20 +288,13 @@ __global__ __launch_bounds__(256) void MM_VX(vertex_bwd_kernel)(VertexBwdArgs a)
             for (int j = 0; j < 3; ++j) acc[9 + j] = d[j];
         }
     }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = wave_sum(acc[i]);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s_red[tid >> 6][i] = acc[i];
-    }
-    __syncthreads();
+    const float dT_wg = block_sum_wide(acc, s_red);
     if (tid < 12) {
         // This workgroup's partial of dL/dT, WRITE-THROUGH (agent-scope relaxed atomic store = sc1: it lands at the memory side, not in
         // this XCD's L2), so that the image's last workgroup can read it with agent-scope loads and NO fence on either side
         // (cdna_hip_programming.md G16, form "sc1 stores and sc1 loads on both sides").  No float atomics: the sum below runs
         // over the workgroups in index order, so the camera gradients are bitwise reproducible.
-        __hip_atomic_store(a.dTpart + ((size_t)b * gridDim.x + blockIdx.x) * 12 + tid,
-                           ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.dTpart + ((size_t)b * gridDim.x + blockIdx.x) * 12 + tid, dT_wg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (blockIdx.x == 0 && !a.geometry_only) {   // dL/dlights (needs nothing of this kernel: the image's FIRST workgroup adds it up, off the last one's tail): sum of the pixel-backward workgroup partials; waves 1..3 take 3 components each, lanes stride over
         // the partials (independent loads), fixed butterfly order
@@ -330,17 +323,9 @@ __global__ __launch_bounds__(256) void MM_VX(vertex_bwd_kernel)(VertexBwdArgs a)
             }
         }
     }
-    // ---- publish, take a ticket; the last workgroup of this image finishes the camera chain
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the storing wave drains its stores before the ticket is drawn
-    __syncthreads();
-    if (tid == 0) {
-        // No agent-scope fences here: a release fence writes back the XCD's whole L2 and an acquire invalidates it, once per
-        // workgroup (removing them took this kernel from 213 to 53 us at B=384).
-        const unsigned prev = __hip_atomic_fetch_add(a.ticket + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (prev == gridDim.x - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
+    // ---- publish, take a ticket; the last workgroup of this image finishes the camera chain (the hand-off: mm_device.h).  The image's ticket
+    // is not reset here: thread 0 clears it below, after the camera chain, and the forward clears it too
+    if (!last_workgroup(a.ticket + b, gridDim.x, false, s_last)) return;
     if (tid >= 64 && tid < 100) reinterpret_cast<float*>(&s_cam)[tid - 64] = a.cam[b * 48 + tid - 64];   // the forward's camera (no trig here)
     {   // dL/dT = sum of the workgroups' partials in a FIXED order: thread (gl, comp) adds rows gl, gl + 21, gl + 42, ... of its component --
         // all of its loads in flight together: ONE trip to memory however many workgroups the image has (6 890 vertices: 216 rows; a pass of

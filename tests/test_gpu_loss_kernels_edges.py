@@ -1,5 +1,6 @@
 """Attribute losses (csrc/mm_attloss.hip) and mesh regularisers (csrc/mm_reg.hip) at the sizes, pointers, masks and degenerate
-inputs their ordinary tests (tests/test_gpu_mesh_reg.py) never reach.
+inputs their ordinary tests (tests/test_gpu_mesh_reg.py) never reach; and the last-workgroup hand-off they share with the vertex
+backward (csrc/mm_device.h: last_workgroup) on its smallest grids, one workgroup per image in vertex_bwd_kernel included.
 
 Reference: oracle/reg_oracle.py in float64 with autograd (tests/test_abi_and_host.py pins it to the reference's own goldens).
 Bars, from tests/test_gpu_mesh_reg.py: loss values 2e-5 * max(1, |ref|); gradients 2e-4 * max|ref grad| + 1e-9 (regularisers) or
@@ -277,6 +278,63 @@ def test_mesh_reg_batch_beyond_one_pass(pkg, L):
     dv[256:] *= 1.5                                              # the images of the second trip carry their own weight in every sum
     vertices = dr.vertices_init[None] + dv
     _reg_check(dr, tuple(range(8)), vertices=vertices, delta=dv, fn=_normals(B, dr.num_faces, g), tag="B=300")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the last-workgroup hand-off (csrc/mm_device.h, last_workgroup) on its smallest grids
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_mesh_reg_one_image_smallest_grid(pkg, small_template):
+    """B = 1: the forward's grid is the four workgroups of one image (it has no smaller one), and the last of them folds a single row."""
+    dr = _small_dr(pkg, small_template)
+    g = torch.Generator().manual_seed(71)
+    dv = _delta(1, dr.num_vertices, g)
+    _reg_check(dr, tuple(range(8)), vertices=dr.vertices_init[None] + dv, delta=dv, fn=_normals(1, dr.num_faces, g), tag="B=1")
+
+
+def test_vertex_backward_one_workgroup_per_image(pkg, oracle, octahedron_template):
+    """V = 6 <= 32: vertex_bwd_kernel's grid is (1, B), so every image's only workgroup draws ticket 0 of 1, is the last, reads back the
+    one dL/dT row it has just published and runs the camera chain.  B = 3 < 128 keeps the call off the per-image kernel, which has no
+    ticket.  The camera gradients (what the last workgroup writes) and dL/dvertices against the CPU oracle at the render tests' bar,
+    1e-4 of each gradient's own maximum (tests/parity_bar.py: stricter than GRAD_BAR here; the float64 oracle decides an fp32
+    conditioning case); then the step again on the same workspace: the ticket the lone workgroup cleared serves the next backward, and
+    the gradients come out the same to the bit."""
+    from parity_bar import grad_close
+    B, S = 3, 32
+    dr = pkg.DiffRender(octahedron_template, S)
+    assert dr.num_vertices == 6 and (dr.num_vertices + 31) // 32 == 1 and B < 128
+    leaves = ("vertices", "azimuths", "elevations", "distances", "biases")
+    att, gt = pkg.synthetic.synthetic_batch(dr.vertices_init, B, S, S, seed=72)
+    inp = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in att.items()}
+    inp["faces"], inp["face_uvs"] = dr.faces.numpy().astype(np.int32), dr.face_uvs.numpy()[0]
+    proj = dr.cam_proj.numpy().reshape(3)
+    runs = []
+    for _ in range(2):
+        datt = {k: (v.to(DEV).requires_grad_(k in leaves) if torch.is_tensor(v) else v) for k, v in att.items()}
+        rgbs, _ = dr.render(no_mask=True, **datt)
+        dr.recon_data(rgbs, gt.to(DEV), no_mask=True).backward()
+        torch.cuda.synchronize()
+        runs.append({k: datt[k].grad.cpu() for k in leaves})
+
+    def backward(dtype):
+        rgba, fidx, _, _ = oracle.render_forward(inp, S, S, True, proj, dtype=dtype)
+        _, dpred = oracle.recon_data(rgba.transpose(0, 3, 1, 2), gt.numpy(), image_weight=dr.image_weight, want_grad=True, dtype=dtype)
+        return fidx, oracle.render_backward(inp, S, S, True, proj, np.ascontiguousarray(dpred.transpose(0, 2, 3, 1)), dtype=dtype)
+
+    fidx_o, g_o = backward(np.float32)
+    assert (dr.last_face_idx.cpu().numpy() == fidx_o).all() and (fidx_o >= 0).mean() > 0.03
+    g64 = []
+
+    def ref64(k):                                                # (the float64 backward: only run on a miss of the fp32 bar)
+        if not g64:
+            g64.append(backward(np.float64)[1])
+        return g64[0][k]
+
+    for k in leaves:
+        assert np.abs(g_o[k]).max() > 0, k
+        e = float(np.abs(runs[0][k].numpy() - g_o[k]).max()) / float(np.abs(g_o[k]).max())
+        print("lone workgroup d/d%s: err %.3e of max|ref| %.3e" % (k, e, float(np.abs(g_o[k]).max())))
+        grad_close(runs[0][k].numpy(), g_o[k], rtol=1e-4, what=k, ref64=lambda k=k: ref64(k))
+        assert torch.equal(runs[0][k], runs[1][k]), k
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
