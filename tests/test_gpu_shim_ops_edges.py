@@ -4,8 +4,9 @@ tests/test_gpu_shim_ops.py runs each operator at one or two small shapes, mostly
 expressions as the kernels.  Here every operator that torch can express is held to a float64 CPU restatement of what kaolin
 does, differentiated by torch autograd, at the shapes where kernels go wrong:
 exact rounding ties and border coordinates, sizes of one, sizes that straddle the kernels' unrolls, trips and lane counts,
-degenerate inputs and the branches for inputs that take no part in the gradient.  dibr_rasterization has no torch form and is
-held to the oracle (face_idx bit-exact, values, gradients with the float64 oracle as the conditioning referee).
+degenerate inputs and the branches for inputs that take no part in the gradient.  dibr_rasterization is held to the oracle here
+(face_idx bit-exact, values, gradients with the float64 oracle as the conditioning referee); its torch form -- decisions by brute force,
+the derivative autograd's -- is tests/render_ref.py, which tests/test_gpu_render_ref.py holds the whole operator chain to.
 Bars: values within 1e-4 on the max(1, |ref|) scale; gradients within 1e-4 of the reference's own maximum (tests/parity_bar.py);
 equality where the kernel is exact."""
 import importlib

@@ -1,5 +1,6 @@
 """fp64 central-difference check of the oracle's full backward (render -> recon_data) for every differentiable input.
-The oracle's gradient is derived, not recalled, so it is checked against its own forward."""
+The oracle's gradient is derived, not recalled, so it is checked against its own forward.
+The ELEMENTWISE pin of that backward, on the branches one random direction cannot see, is tests/test_render_ref_host.py (autograd of the forward restated in torch)."""
 import numpy as np
 import pytest
 
