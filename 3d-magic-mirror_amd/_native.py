@@ -242,6 +242,14 @@ class MMGifDesc(ctypes.Structure):
                 ("frames", c_p), ("delays", c_p), ("palette", c_p), ("indices", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+PNG_SEGMENT, PNG_MAX_SEGMENT, PNG_CRC_PIECE = 1024, 8192, 64      # MM_PNG_SEGMENT, MM_PNG_MAX_SEGMENT, MM_PNG_CRC_PIECE
+
+
+class MMPngDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("channels", c_i), ("filter", c_i), ("segment", c_i),
+                ("frames", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -331,6 +339,9 @@ SIGNATURES = {
     "mm_gif_query_workspace": (c_z, [P(MMGifDesc)]),
     "mm_gif_file_offset": (c_z, [P(MMGifDesc)]),
     "mm_gif_encode": (c_int, [P(MMGifDesc), c_p]),
+    "mm_png_query_workspace": (c_z, [P(MMPngDesc)]),
+    "mm_png_files_offset": (c_z, [P(MMPngDesc)]),
+    "mm_png_encode": (c_int, [P(MMPngDesc), c_p]),
     "mm_build_vertex_corner_csr": (c_int, [c_i, c_i, c_p, c_p, c_p]),
     "mm_build_vertex_corner_csr_device": (c_int, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mm_build_vertex_corner_table": (c_int, [c_i, c_i, c_p, c_i, c_p]),
@@ -347,7 +358,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
-              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc}
+              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 

@@ -72,6 +72,11 @@ int launch_jpeg_roundtrip(const MMJpegRoundtripDesc*, hipStream_t);
 size_t gif_workspace_bytes(const MMGifDesc*);
 size_t gif_file_at(const MMGifDesc*);
 int launch_gif(const MMGifDesc*, hipStream_t);
+size_t png_workspace_bytes(const MMPngDesc*);
+size_t png_files_at(const MMPngDesc*);
+long long png_idat_cap(const MMPngDesc*);
+long long png_all_segs(const MMPngDesc*);
+int launch_png(const MMPngDesc*, hipStream_t);
 }  // namespace mm
 
 static bool sizes_positive(const MMRenderDesc* d) { return d->B > 0 && d->H > 0 && d->W > 0 && d->V > 0 && d->F > 0 && d->Ht > 0 && d->Wt > 0; }
@@ -939,6 +944,33 @@ int mm_gif_encode(const MMGifDesc* d, mm_stream_t stream) {
     return mm::launch_gif(d, (hipStream_t)stream);
 }
 
+// the sizes a PNG call may have: MM_OK, or why not
+static int check_png_shape(const MMPngDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->n <= 0 || d->H <= 0 || d->W <= 0 || (d->channels != 1 && d->channels != 3 && d->channels != 4)) return MM_ERR_BAD_SHAPE;
+    if (d->filter < -1 || d->filter > 4 || d->segment < 1 || d->segment > MM_PNG_MAX_SEGMENT) return MM_ERR_BAD_SHAPE;
+    if (d->H > 65535 || d->W > 65535 || d->n > 65535) return MM_ERR_UNSUPPORTED;
+    if (mm::png_idat_cap(d) > 0x7fffffffLL || mm::png_all_segs(d) > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;      // a chunk's length; the grids
+    return MM_OK;
+}
+
+size_t mm_png_query_workspace(const MMPngDesc* d) {
+    return check_png_shape(d) == MM_OK ? mm::png_workspace_bytes(d) : 0;
+}
+
+size_t mm_png_files_offset(const MMPngDesc* d) {
+    return check_png_shape(d) == MM_OK ? mm::png_files_at(d) : 0;
+}
+
+int mm_png_encode(const MMPngDesc* d, mm_stream_t stream) {
+    const int shape = check_png_shape(d);
+    if (shape != MM_OK) return shape;
+    if (!d->frames || !d->workspace) return MM_ERR_NULL_POINTER;
+    if (d->workspace_bytes < mm::png_workspace_bytes(d) || ((uintptr_t)d->workspace & 15)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_png(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -1013,7 +1045,7 @@ size_t mm_struct_size(int which) {
         case 30: return sizeof(MMBatchDesc);    case 32: return sizeof(MMCompositeDesc);   // (31: unassigned)
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
         case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
-        case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc);
+        case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc); case 41: return sizeof(MMPngDesc);
         default: return 0;
     }
 }

@@ -1,7 +1,7 @@
-// mm_stream.h -- what the frame ENCODERS share (mm_jpeg.hip, mm_gif.hip), the counterpart of mm_frame.h for the frame makers: an array
+// mm_stream.h -- what the frame ENCODERS share (mm_jpeg.hip, mm_gif.hip, mm_png.hip), the counterpart of mm_frame.h for the frame makers: an array
 // longer than a workgroup turned into its prefix sums, and the host's carve of a workspace.  mm_interp.hip borrows the workgroup scan.
 // Every scan here runs in one workgroup per frame or per call, between the passes that do the work: none is worth another algorithm.
-// What the encoders do NOT share: their bit sinks (GifBits: LSB first, a private slot, plain stores; JpegWriter: MSB first, a shared
+// What the encoders do NOT share: their bit sinks (GifBits, and PngBits after it: LSB first, a private slot, plain stores; JpegWriter: MSB first, a shared
 // stream, atomic OR on a block's first and last word), their pack kernels, and byte stuffing against sub-blocks.  Those differ in substance.
 #pragma once
 #include "mm_device.h"

@@ -151,7 +151,7 @@ class JpegBatch:
     def __getitem__(self, i):
         n = len(self)
         if not isinstance(i, (int, np.integer)):
-            raise TypeError("a JpegBatch is indexed by an int, got %r" % (i,))
+            raise TypeError("a %s is indexed by an int, got %r" % (type(self).__name__, i))
         if i < -n or i >= n:
             raise IndexError("file %d of %d" % (i, n))
         i = int(i) % n

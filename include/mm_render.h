@@ -1130,6 +1130,49 @@ size_t mm_gif_file_offset(const MMGifDesc* desc);           /* where the file st
 int mm_gif_encode(const MMGifDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * PNG: n device frames (n,H,W,channels) of bytes, channels 1 (grey), 3 (RGB) or 4 (RGBA) -- what mm_export_images and mm_export_grid
+ * write, at any byte alignment -- as n PNG files, back to back.  Lossless: a decoder returns the frames to the bit.  The file is fully
+ * specified here (no other writer's bytes are a target).  Integer arithmetic only; every atomic is an integer OR or XOR:
+ *   file       89 50 4E 47 0D 0A 1A 0A; IHDR: W, H (u32be), 8, colour type 0 / 2 / 6, 0, 0, 0; one IDAT; IEND.  A chunk is its data's length
+ *              u32be, its type, its data and the CRC-32 of type + data u32be.
+ *   filter     the stream S is H rows of 1 + W * channels bytes: the filter type, then the filtered row.  bpp = channels; a is the byte bpp
+ *              to the left, b the byte above, c above-left, 0 outside the image, of the raw rows.  0 None, 1 Sub x - a, 2 Up x - b,
+ *              3 Average x - (a + b) / 2 (floor), 4 Paeth (p = a + b - c: a if |p-a| <= |p-b| and |p-a| <= |p-c|, else b if
+ *              |p-b| <= |p-c|, else c), all mod 256.  filter -1 chooses per row the type with the smallest sum of
+ *              (v < 128 ? v : 256 - v) over the filtered bytes, ties to the lowest type; 0..4 forces that type on every row.
+ *   zlib       78 01, the deflate blocks, zero bits up to a byte, Adler-32 of S (u32be)
+ *   deflate    S is cut into segments of `segment` bytes (the last may be shorter), each one block with the fixed Huffman codes: BFINAL
+ *              (1 on the last only), then 1, 0, the symbols, end-of-block.  Blocks follow each other bit by bit.
+ *   matching   inside a segment [s, e), greedy: at i with i + 3 <= e, j is the latest position in [s, i) with S[j..j+3) == S[i..i+3) and
+ *              L the longest length <= min(258, e - i) with S[j+k] == S[i+k] for k < L (overlap allowed).  With such a j the match
+ *              (L, i - j) is emitted and i += L; otherwise the literal S[i] and i += 1.
+ *   codes      RFC 1951 3.2.6, fixed: Huffman codes most significant bit first into the LSB-first stream, extra bits least significant first.
+ * The workspace is the caller's, mm_png_query_workspace bytes, 16-byte aligned; the library allocates nothing.  After the call it holds at
+ * byte 0 the n + 1 int64 offsets of the files (the last is the end of the last file) relative to byte mm_png_files_offset, where the
+ * files lie back to back: a caller copies the offsets, then exactly offsets[n] bytes.  The rest is scratch: S, a slot per segment sized for
+ * its exact worst case (3 + 9 len + 7 bits: a match never costs more than its bytes as literals) and the frames' packed streams.
+ * MM_ERR_BAD_SHAPE: n, H, W < 1; channels not 1, 3 or 4; filter outside -1..4; segment outside 1..MM_PNG_MAX_SEGMENT.
+ * MM_ERR_UNSUPPORTED: H, W or n > 65535; a frame whose IDAT could exceed 2^31 - 1 bytes; more than 2^31 - 1 segments in the call (the
+ * queries return 0).  MM_ERR_WORKSPACE: too small or misaligned.
+ * Eight stream operations (one memset, seven launches).  No host synchronisation; bitwise reproducible.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_PNG_SEGMENT 1024         /* the segment length the Python layer uses (tools/bench_png.py measured 1024, 2048 and 4096) */
+#define MM_PNG_MAX_SEGMENT 8192     /* a segment's bytes and its table of 16-bit positions (2 * segment slots) fit 64 KiB of LDS */
+#define MM_PNG_CRC_PIECE 64         /* bytes of an IDAT whose CRC one lane takes */
+typedef struct MMPngDesc {
+    int32_t n, H, W;                /* the frames */
+    int32_t channels;               /* 1, 3 or 4: colour type 0, 2 or 6 */
+    int32_t filter;                 /* -1: adaptive; 0..4: that filter type on every row */
+    int32_t segment;                /* bytes of S that share a match window */
+    const uint8_t* frames;          /* (n,H,W,channels), dense, any alignment */
+    void* workspace;
+    size_t workspace_bytes;
+} MMPngDesc;
+size_t mm_png_query_workspace(const MMPngDesc* desc);       /* reads n, H, W, channels, segment */
+size_t mm_png_files_offset(const MMPngDesc* desc);          /* where the files start in the workspace */
+int mm_png_encode(const MMPngDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -1154,7 +1197,7 @@ const char* mm_last_error_detail(void);
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
- * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc (31, 34 and 36 are unassigned). */
+ * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1175,7 +1218,8 @@ size_t mm_struct_size(int which);
  * returns 0 --, an addition, detected by mm_struct_size(35) != 0; still 9: MMJpegDesc and mm_jpeg_*, struct id 37 -- id 36 stays
  * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0; still 9: MMJpegRoundtripDesc,
  * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0; still 9: MMGifDesc and mm_gif_*, struct id 39, an addition, detected by mm_struct_size(39) != 0; still 9: MMPoissonDesc and
- * mm_poisson_frames, struct id 40, an addition, detected by mm_struct_size(40) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_poisson_frames, struct id 40, an addition, detected by mm_struct_size(40) != 0; still 9: MMPngDesc and mm_png_*, struct id 41, an
+ * addition, detected by mm_struct_size(41) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
