@@ -227,10 +227,16 @@ class MMJpegDesc(ctypes.Structure):
 
 
 JPEG_MODE_RGB, JPEG_MODE_L = 0, 1     # MM_JPEG_MODE_*
+JPEG_SAMPLING_420, JPEG_SAMPLING_422, JPEG_SAMPLING_444 = 0, 1, 2      # MM_JPEG_SAMPLING_*
+
+
+class MMJpegModesDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("header_bytes", c_i), ("mode", c_i), ("sampling", c_i), ("frames", c_p), ("params_host", c_p),
+                ("params", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
 class MMJpegRoundtripDesc(ctypes.Structure):
-    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("mode", c_i), ("as_float", c_i), ("reserved", c_i), ("frames", c_p), ("coef", c_p),
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("mode", c_i), ("as_float", c_i), ("sampling", c_i), ("frames", c_p), ("coef", c_p),
                 ("params_host", c_p), ("params", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
@@ -333,6 +339,10 @@ SIGNATURES = {
     "mm_jpeg_query_workspace": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_files_offset": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_encode": (c_int, [P(MMJpegDesc), c_p]),
+    "mm_jpeg_modes_query_workspace": (c_z, [P(MMJpegModesDesc)]),
+    "mm_jpeg_modes_files_offset": (c_z, [P(MMJpegModesDesc)]),
+    "mm_jpeg_modes_coef_offset": (c_z, [P(MMJpegModesDesc)]),
+    "mm_jpeg_modes_encode": (c_int, [P(MMJpegModesDesc), c_p]),
     "mm_jpeg_coef_offset": (c_z, [P(MMJpegDesc)]),
     "mm_jpeg_roundtrip_query_workspace": (c_z, [P(MMJpegRoundtripDesc)]),
     "mm_jpeg_roundtrip": (c_int, [P(MMJpegRoundtripDesc), c_p]),
@@ -358,7 +368,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
-              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc}
+              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc, 42: MMJpegModesDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 
@@ -493,7 +503,7 @@ def call(name, where, *args, what=None):
 
     The one call path of every entry point that takes a stream and returns an MMStatus.  Deliberately not folded in: input_batches.py turns a
     refusal of mm_assemble_batch into a ValueError of its own wording (it uses fn, not check); mm_render_status returns a verdict, not an
-    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_jpeg_coef_offset, mm_gif_file_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
+    error; the *_query_workspace functions, mm_jpeg_files_offset, mm_jpeg_coef_offset and their mm_jpeg_modes_* forms, mm_gif_file_offset, mm_recon_data_totals and mm_render_step_mode return values (fn(name)(desc));
     and diff_render.py hands fn_addr addresses to the C++ nodes."""
     status = (_FN.get(name) or fn(name))(*args, where if type(where) is c_p else current_stream(where))
     if status:

@@ -63,10 +63,12 @@ int launch_pyramid(const MMPyramidDesc*, hipStream_t);
 struct PoiArgs;
 long long poisson_lds_bytes(const MMPoissonDesc*, PoiArgs*);
 int launch_poisson(const MMPoissonDesc*, hipStream_t);
-size_t jpeg_workspace_bytes(const MMJpegDesc*);
-size_t jpeg_files_at(const MMJpegDesc*);
-int launch_jpeg(const MMJpegDesc*, hipStream_t);
-size_t jpeg_coef_at(const MMJpegDesc*);
+size_t jpeg_workspace_bytes(const MMJpegModesDesc*);
+size_t jpeg_files_at(const MMJpegModesDesc*);
+int launch_jpeg(const MMJpegModesDesc*, hipStream_t);
+size_t jpeg_coef_at(const MMJpegModesDesc*);
+int jpeg_layout_of(int mode, int sampling);
+long long jpeg_frame_blocks(int H, int W, int layout);
 size_t jpeg_roundtrip_workspace_bytes(const MMJpegRoundtripDesc*);
 int launch_jpeg_roundtrip(const MMJpegRoundtripDesc*, hipStream_t);
 size_t gif_workspace_bytes(const MMGifDesc*);
@@ -854,24 +856,30 @@ int mm_poisson_frames(const MMPoissonDesc* d, mm_stream_t stream) {
 }
 
 // the sizes a JPEG call may have: MM_OK, or why not
-static int check_jpeg_shape(const MMJpegDesc* d) {
+static int check_jpeg_shape(const MMJpegModesDesc* d) {
     if (!d) return MM_ERR_NULL_POINTER;
     if (d->n <= 0 || d->H <= 0 || d->W <= 0 || d->header_bytes < 2 || d->header_bytes > MM_JPEG_MAX_HEADER) return MM_ERR_BAD_SHAPE;
+    const int layout = mm::jpeg_layout_of(d->mode, d->sampling);
+    if (layout < 0) return MM_ERR_BAD_SHAPE;
     if (d->H > 65535 || d->W > 65535 || d->n > 65535) return MM_ERR_UNSUPPORTED;
-    const long long blocks = 6LL * ((d->H + 15) / 16) * ((d->W + 15) / 16);
+    const long long blocks = mm::jpeg_frame_blocks(d->H, d->W, layout);     // the layout's own: 6, 4, 3 or 1 per MCU
     if (blocks > MM_JPEG_MAX_BLOCKS || blocks * d->n > (1LL << 30)) return MM_ERR_UNSUPPORTED;
     return MM_OK;
 }
 
-size_t mm_jpeg_query_workspace(const MMJpegDesc* d) {
+size_t mm_jpeg_modes_query_workspace(const MMJpegModesDesc* d) {
     return check_jpeg_shape(d) == MM_OK ? mm::jpeg_workspace_bytes(d) : 0;
 }
 
-size_t mm_jpeg_files_offset(const MMJpegDesc* d) {
+size_t mm_jpeg_modes_files_offset(const MMJpegModesDesc* d) {
     return check_jpeg_shape(d) == MM_OK ? mm::jpeg_files_at(d) : 0;
 }
 
-int mm_jpeg_encode(const MMJpegDesc* d, mm_stream_t stream) {
+size_t mm_jpeg_modes_coef_offset(const MMJpegModesDesc* d) {
+    return check_jpeg_shape(d) == MM_OK ? mm::jpeg_coef_at(d) : 0;
+}
+
+int mm_jpeg_modes_encode(const MMJpegModesDesc* d, mm_stream_t stream) {
     const int shape = check_jpeg_shape(d);
     if (shape != MM_OK) return shape;
     if (!d->frames || !d->params_host || !d->params || !d->workspace) return MM_ERR_NULL_POINTER;
@@ -887,16 +895,42 @@ int mm_jpeg_encode(const MMJpegDesc* d, mm_stream_t stream) {
     return mm::launch_jpeg(d, (hipStream_t)stream);
 }
 
+// MMJpegDesc is MMJpegModesDesc with mode RGB and sampling 4:2:0: mm_jpeg_* forward
+static const MMJpegModesDesc* jpeg_as_modes(const MMJpegDesc* d, MMJpegModesDesc* e) {
+    if (!d) return nullptr;
+    *e = MMJpegModesDesc{};
+    e->n = d->n; e->H = d->H; e->W = d->W; e->header_bytes = d->header_bytes;
+    e->mode = MM_JPEG_MODE_RGB; e->sampling = MM_JPEG_SAMPLING_420;
+    e->frames = d->frames; e->params_host = d->params_host; e->params = d->params;
+    e->workspace = d->workspace; e->workspace_bytes = d->workspace_bytes;
+    return e;
+}
+
+size_t mm_jpeg_query_workspace(const MMJpegDesc* d) {
+    MMJpegModesDesc e;
+    return mm_jpeg_modes_query_workspace(jpeg_as_modes(d, &e));
+}
+
+size_t mm_jpeg_files_offset(const MMJpegDesc* d) {
+    MMJpegModesDesc e;
+    return mm_jpeg_modes_files_offset(jpeg_as_modes(d, &e));
+}
+
+int mm_jpeg_encode(const MMJpegDesc* d, mm_stream_t stream) {
+    MMJpegModesDesc e;
+    return mm_jpeg_modes_encode(jpeg_as_modes(d, &e), stream);
+}
+
 size_t mm_jpeg_coef_offset(const MMJpegDesc* d) {
-    return check_jpeg_shape(d) == MM_OK ? mm::jpeg_coef_at(d) : 0;
+    MMJpegModesDesc e;
+    return mm_jpeg_modes_coef_offset(jpeg_as_modes(d, &e));
 }
 
 // the sizes a round trip may have: the encoder's, in both modes
 static int check_jpeg_roundtrip_shape(const MMJpegRoundtripDesc* d) {
     if (!d) return MM_ERR_NULL_POINTER;
-    if (d->mode != MM_JPEG_MODE_RGB && d->mode != MM_JPEG_MODE_L) return MM_ERR_BAD_SHAPE;
-    MMJpegDesc e = {};
-    e.n = d->n; e.H = d->H; e.W = d->W; e.header_bytes = 2;
+    MMJpegModesDesc e = {};                                       // (an unknown mode or sampling, or a sampling with mode L: refused there)
+    e.n = d->n; e.H = d->H; e.W = d->W; e.header_bytes = 2; e.mode = d->mode; e.sampling = d->sampling;
     return check_jpeg_shape(&e);
 }
 
@@ -1046,6 +1080,7 @@ size_t mm_struct_size(int which) {
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
         case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
         case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc); case 41: return sizeof(MMPngDesc);
+        case 42: return sizeof(MMJpegModesDesc);
         default: return 0;
     }
 }

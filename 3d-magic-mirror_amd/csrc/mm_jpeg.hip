@@ -1,7 +1,8 @@
 // mm_jpeg.hip -- 8-bit device frames (n,H,W,3) as baseline JPEG files, for gfx950: what the reference's scripts do on the host per image with
 // to_pil_image(X[i, :3].cpu()).save(name, 'JPEG', quality=100) (trainer.py:51, test.py:53, generate_market++.py:55,
 // tool/generate_market_test.py:57, ...).  Every file equals Pillow's (libjpeg-turbo's) byte for byte: baseline, 4:2:0, the standard
-// Huffman tables.  The host makes the tables and the header; everything after SOS is made here.  Integer arithmetic only (>> is
+// Huffman tables.  The MCU is a template parameter (JpegMcu below): 4:2:0 is written out here; 4:2:2, 4:4:4 and greyscale -- masks (n,H,W),
+// the files to_pil_image(X[i, 3]).save(...) writes -- differ in the edges, the chroma and the block order alone, as said at JpegMcu.  The host makes the tables and the header; everything after SOS is made here.  Integer arithmetic only (>> is
 // arithmetic), in libjpeg's order:
 //   colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
 //             Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
@@ -39,6 +40,8 @@
 // The round trip (mm_jpeg_roundtrip: the frames as the decoder reads those files back) is below the encoder's kernels, with its own header.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mm_device.h"
 #include "mm_quant.h"                                         // unquant: the v / 255 of as_float, shared with the exports
 #include "mm_stream.h"                                        // array_scan, Carve: what the encoders share
@@ -53,15 +56,67 @@ namespace mm {
 // where the tables lie in MMJpegDesc.params (32-bit words)
 enum { MM_JPG_DIV = 0, MM_JPG_HUFF = 128, MM_JPG_HEADER = 128 + 1024 };
 
+// What an MCU is, said once.  A layout's number is its MM_JPEG_SAMPLING_* for colour (0: 4:2:0, 1: 4:2:2, 2: 4:4:4) and 3 for greyscale.
+// The first LUMA blocks of an MCU are luma (or grey), LH across and LV down in raster order, and use the luma divisors and tables; in a
+// colour layout one block each of Cb and Cr follows, with the chroma divisors and tables.  Colour, DCT, quantiser and entropy coder are
+// the same in every layout; per layout:
+//   4:2:0      16 x 16 pixels, Y00 Y01 Y10 Y11 Cb Cr: the header of this file.
+//   4:2:2      16 wide, 8 high, Y0 Y1 Cb Cr.  Columns beyond W replicate the input's last column up to the MCU, rows beyond H its last row
+//              up to the block.  c[x] = (C[2x] + C[2x+1] + bias) >> 1, bias 0 on even x and 1 on odd x.  Y1 is a dummy where
+//              2 mx + 1 >= ceil(W / 8) (W mod 16 in 1..8).  No vertical dummy, no downsampled-row rule.
+//   4:4:4      8 x 8 pixels, Y Cb Cr; edges replicated on all three planes; no downsampling, no dummies.
+//   greyscale  a non-interleaved scan: an MCU is one 8 x 8 block, ceil(H / 8) x ceil(W / 8) in raster order, edges replicated, no dummies;
+//              the frames are (n,H,W), one byte a pixel; the luma divisors and tables, one DC predictor.
+// Decoding (the round trip below): the sample planes are Y 8 LV my x 8 LH mx and Cb, Cr 8 my x 8 mx per frame.  4:4:4 is not upsampled;
+// 4:2:2 has real chroma on H x wd, wd = ceil(W / 2): wd > 2, h2v1 fancy, out[2x] = (3 s[x] + s[x-1] + 1) >> 2, out[2x+1] =
+// (3 s[x] + s[x+1] + 2) >> 2, s[-1] := s[0], s[wd] := s[wd-1]; wd <= 2, replication; no vertical neighbour.
+enum { MM_JPG_420 = 0, MM_JPG_422 = 1, MM_JPG_444 = 2, MM_JPG_GREY = 3 };
+template <int L>
+struct JpegMcu {
+    static_assert(L >= MM_JPG_420 && L <= MM_JPG_GREY, "a layout");
+    static constexpr int LH_SHIFT = L <= MM_JPG_422 ? 1 : 0, LH = 1 << LH_SHIFT, LV = L == MM_JPG_420 ? 2 : 1;      // luma blocks across and down
+    static constexpr int LUMA = LH * LV, BLOCKS = L == MM_JPG_GREY ? 1 : LUMA + 2;
+    static constexpr int W = 8 * LH, H = 8 * LV;              // the MCU in pixels
+    static constexpr int CHANNELS = L == MM_JPG_GREY ? 1 : 3; // bytes a pixel of the input
+};
+// the same for the host's arithmetic
+struct JpegMcuShape { int blocks, w, h; };
+template <int N = 4, class F>
+__host__ inline void jpeg_by_layout(int layout, F f) {       // f(std::integral_constant<int, layout>): the host's dispatch on the template parameter
+    switch (layout) {
+        case MM_JPG_420: f(std::integral_constant<int, MM_JPG_420>()); break;
+        case MM_JPG_422: f(std::integral_constant<int, MM_JPG_422>()); break;
+        case MM_JPG_444: f(std::integral_constant<int, MM_JPG_444>()); break;
+        default: if constexpr (N > MM_JPG_GREY) f(std::integral_constant<int, MM_JPG_GREY>()); break;
+    }
+}
+__host__ JpegMcuShape jpeg_mcu_shape(int layout) {
+    JpegMcuShape m = {};
+    jpeg_by_layout(layout, [&](auto L) { using M = JpegMcu<decltype(L)::value>; m = {M::BLOCKS, M::W, M::H}; });
+    return m;
+}
+// mode and sampling as the descriptors carry them -> the layout, or -1 for what is refused (an unknown value; a sampling with mode L)
+int jpeg_layout_of(int mode, int sampling) {
+    if (mode == MM_JPEG_MODE_L) return sampling == 0 ? MM_JPG_GREY : -1;
+    if (mode != MM_JPEG_MODE_RGB || sampling < MM_JPEG_SAMPLING_420 || sampling > MM_JPEG_SAMPLING_444) return -1;
+    return sampling;
+}
+long long jpeg_frame_blocks(int H, int W, int layout) {
+    const JpegMcuShape m = jpeg_mcu_shape(layout);
+    return (long long)m.blocks * ((H + m.h - 1) / m.h) * ((W + m.w - 1) / m.w);
+}
+
 struct JpegLayout {
-    int my, mx, blocks, chunks;                               // MCU rows and columns, blocks and 1024-byte chunks of one frame
+    int layout, my, mx, blocks, chunks;                       // MCU rows and columns, blocks and 1024-byte chunks of one frame
     size_t file_cap;                                          // bytes kept for one file
     size_t offsets, files, coef, bits, frame_bits, raw, chunk_ff, bytes;      // byte offsets into the workspace
 };
-__host__ JpegLayout jpeg_layout(const MMJpegDesc* d) {
+__host__ JpegLayout jpeg_layout(const MMJpegModesDesc* d) {
     JpegLayout l;
-    l.my = (d->H + 15) / 16; l.mx = (d->W + 15) / 16;
-    l.blocks = l.my * l.mx * 6;
+    l.layout = jpeg_layout_of(d->mode, d->sampling);
+    const JpegMcuShape m = jpeg_mcu_shape(l.layout);
+    l.my = (d->H + m.h - 1) / m.h; l.mx = (d->W + m.w - 1) / m.w;
+    l.blocks = l.my * l.mx * m.blocks;
     l.chunks = (int)(((size_t)l.blocks * MM_JPEG_BLOCK_BYTES + MM_JPEG_CHUNK_BYTES - 1) / MM_JPEG_CHUNK_BYTES);
     l.file_cap = (size_t)d->header_bytes + 2 * (size_t)l.chunks * MM_JPEG_CHUNK_BYTES + 2;
     const size_t n = (size_t)d->n;
@@ -76,15 +131,15 @@ __host__ JpegLayout jpeg_layout(const MMJpegDesc* d) {
     l.bytes = c.at;
     return l;
 }
-size_t jpeg_workspace_bytes(const MMJpegDesc* d) { return jpeg_layout(d).bytes; }
-size_t jpeg_files_at(const MMJpegDesc* d) { return jpeg_layout(d).files; }
+size_t jpeg_workspace_bytes(const MMJpegModesDesc* d) { return jpeg_layout(d).bytes; }
+size_t jpeg_files_at(const MMJpegModesDesc* d) { return jpeg_layout(d).files; }
 
 struct JpegArgs {
     const unsigned char* frames; const int* par;
     long long* offsets; unsigned char* files; short* coef; unsigned* bits; unsigned* frame_bits; unsigned* raw; unsigned* chunk_ff;
     int n, H, W, header_bytes;
     int my, mx, blocks, chunks;
-    int bh, bw, ch;                                           // luma blocks down and across that hold pixels; chroma rows that do
+    int bh, bw, ch;                                           // luma blocks down and across that hold pixels; 4:2:0: chroma rows that do
     long long total_blocks;
 };
 
@@ -120,7 +175,16 @@ __device__ inline void jpeg_fdct8(const int (&d)[8], int (&o)[8]) {
 }
 
 // ---- transform: frames -> quantised coefficients, zigzag order, MCU order ---------------------------------------------------------
+// Cb or Cr of one pixel
+__device__ inline int jpeg_chroma(const unsigned char* p, bool cb) {
+    const int R = p[0], G = p[1], B = p[2];
+    return cb ? (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+              : (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+}
+
+template <int L>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_transform_kernel(JpegArgs a) {
+    using M = JpegMcu<L>;
     __shared__ int tile[MM_JPG_BLOCK / 8][65];                // a block's 64 values after the row pass (65: the blocks' rows on different banks)
     __shared__ __attribute__((aligned(16))) short zz[MM_JPG_BLOCK / 8][64];
     const int tid = threadIdx.x, lb = tid >> 3, r = tid & 7;
@@ -128,20 +192,33 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_transform_kernel(JpegArgs a
     const bool live = g < a.total_blocks;
     const long long gc = live ? g : 0;
     const int img = (int)(gc / a.blocks), rem = (int)(gc % a.blocks);
-    const int mcu = rem / 6, j = rem % 6, my = mcu / a.mx, mx = mcu % a.mx;
-    const unsigned char* f = a.frames + (size_t)img * a.H * a.W * 3;
+    const int mcu = rem / M::BLOCKS, j = rem % M::BLOCKS, my = mcu / a.mx, mx = mcu % a.mx;
+    const unsigned char* f = a.frames + (size_t)img * a.H * a.W * M::CHANNELS;
     bool dummy = false;
     int d[8], o[8];
-    if (j < 4) {
-        const int by = 2 * my + (j >> 1), bx = 2 * mx + (j & 1);
+    if (j < M::LUMA) {
+        const int by = M::LV * my + (j >> M::LH_SHIFT), bx = M::LH * mx + (j & (M::LH - 1));
         dummy = by >= a.bh || bx >= a.bw;
         const int y = min(by * 8 + r, a.H - 1);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const unsigned char* p = f + ((size_t)y * a.W + min(bx * 8 + c, a.W - 1)) * 3;
-            d[c] = ((19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16) - 128;
+            const unsigned char* p = f + ((size_t)y * a.W + min(bx * 8 + c, a.W - 1)) * M::CHANNELS;
+            if constexpr (L == MM_JPG_GREY) d[c] = (int)p[0] - 128;
+            else d[c] = ((19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16) - 128;
         }
-    } else {
+    } else if constexpr (L == MM_JPG_444) {                   // chroma as it is
+        const size_t y = (size_t)min(my * 8 + r, a.H - 1) * a.W;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) d[c] = jpeg_chroma(f + (y + min(mx * 8 + c, a.W - 1)) * 3, j == M::LUMA) - 128;
+    } else if constexpr (L == MM_JPG_422) {                   // 16 pixels of one row, halved across
+        const size_t y = (size_t)min(my * 8 + r, a.H - 1) * a.W;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int x0 = min(2 * (mx * 8 + c), a.W - 1), x1 = min(2 * (mx * 8 + c) + 1, a.W - 1);
+            const int sum = (c & 1) + jpeg_chroma(f + (y + x0) * 3, j == M::LUMA) + jpeg_chroma(f + (y + x1) * 3, j == M::LUMA);   // bias 0 on even output columns, 1 on odd ones
+            d[c] = (sum >> 1) - 128;
+        }
+    } else if constexpr (L == MM_JPG_420) {
         const int cy = min(my * 8 + r, a.ch - 1);             // beyond the chroma rows: the downsampled last row
         const size_t y0 = (size_t)min(2 * cy, a.H - 1) * a.W, y1 = (size_t)min(2 * cy + 1, a.H - 1) * a.W;
 #pragma unroll
@@ -150,11 +227,7 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_transform_kernel(JpegArgs a
             const unsigned char* q[4] = {f + (y0 + x0) * 3, f + (y0 + x1) * 3, f + (y1 + x0) * 3, f + (y1 + x1) * 3};
             int sum = (c & 1) + 1;                            // the bias: 1 on even output columns, 2 on odd ones
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int R = q[i][0], G = q[i][1], B = q[i][2];
-                sum += j == 4 ? (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
-                              : (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
-            }
+            for (int i = 0; i < 4; ++i) sum += jpeg_chroma(q[i], j == M::LUMA);
             d[c] = (sum >> 2) - 128;
         }
     }
@@ -165,7 +238,7 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_transform_kernel(JpegArgs a
 #pragma unroll
     for (int k = 0; k < 8; ++k) d[k] = tile[lb][k * 8 + r];   // lane r now has column r
     jpeg_fdct8<false>(d, o);
-    const int* div = a.par + MM_JPG_DIV + (j < 4 ? 0 : 64);
+    const int* div = a.par + MM_JPG_DIV + (j < M::LUMA ? 0 : 64);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int nat = k * 8 + r;
@@ -179,19 +252,24 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_transform_kernel(JpegArgs a
 }
 
 // ---- the walk over a block, shared by the count and the pack ----------------------------------------------------------------------
+template <int L>
 __device__ inline bool jpeg_is_dummy(const JpegArgs& a, int mcu, int j) {
-    return j < 4 && (2 * (mcu / a.mx) + (j >> 1) >= a.bh || 2 * (mcu % a.mx) + (j & 1) >= a.bw);
+    using M = JpegMcu<L>;
+    if constexpr (M::LUMA == 1) return false;                 // one luma block an MCU: it always holds pixels
+    return j < M::LUMA && (M::LV * (mcu / a.mx) + (j >> M::LH_SHIFT) >= a.bh || M::LH * (mcu % a.mx) + (j & (M::LH - 1)) >= a.bw);
 }
-// the DC a block codes: its own, or for a dummy that of the block before it in MCU order (Y00 is never a dummy)
+// the DC a block codes: its own, or for a dummy that of the block before it in MCU order (an MCU's first block is never a dummy)
+template <int L>
 __device__ inline int jpeg_dc(const JpegArgs& a, const short* frame_coef, int mcu, int j) {
-    while (jpeg_is_dummy(a, mcu, j)) --j;
-    return frame_coef[((size_t)mcu * 6 + j) * 64];
+    while (jpeg_is_dummy<L>(a, mcu, j)) --j;
+    return frame_coef[((size_t)mcu * JpegMcu<L>::BLOCKS + j) * 64];
 }
 // the predictor: the DC coded by the previous block of the same component
+template <int L>
 __device__ inline int jpeg_dc_pred(const JpegArgs& a, const short* frame_coef, int mcu, int j) {
-    if (j >= 1 && j < 4) return jpeg_dc(a, frame_coef, mcu, j - 1);
+    if (j >= 1 && j < JpegMcu<L>::LUMA) return jpeg_dc<L>(a, frame_coef, mcu, j - 1);
     if (mcu == 0) return 0;
-    return jpeg_dc(a, frame_coef, mcu - 1, j == 0 ? 3 : j);
+    return jpeg_dc<L>(a, frame_coef, mcu - 1, j == 0 ? JpegMcu<L>::LUMA - 1 : j);
 }
 
 struct JpegCounter {
@@ -258,18 +336,19 @@ __device__ inline void jpeg_walk(const uint4* coef, int dc, int pred, const unsi
     sink.finish();
 }
 
-template <bool PACK>
+template <int L, bool PACK>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_code_kernel(JpegArgs a) {
+    using M = JpegMcu<L>;
     __shared__ unsigned huff[1024];
     const int tid = threadIdx.x;
     for (int i = tid; i < 1024; i += MM_JPG_BLOCK) huff[i] = (unsigned)a.par[MM_JPG_HUFF + i];
     __syncthreads();
     const long long g = (long long)blockIdx.x * MM_JPG_BLOCK + tid;
     if (g >= a.total_blocks) return;
-    const int img = (int)(g / a.blocks), rem = (int)(g % a.blocks), mcu = rem / 6, j = rem % 6;
+    const int img = (int)(g / a.blocks), rem = (int)(g % a.blocks), mcu = rem / M::BLOCKS, j = rem % M::BLOCKS;
     const short* fc = a.coef + (size_t)img * a.blocks * 64;
-    const int dc = jpeg_dc(a, fc, mcu, j), pred = jpeg_dc_pred(a, fc, mcu, j);
-    const unsigned* dc_tab = huff + (j < 4 ? 0 : 512);
+    const int dc = jpeg_dc<L>(a, fc, mcu, j), pred = jpeg_dc_pred<L>(a, fc, mcu, j);
+    const unsigned* dc_tab = huff + (j < M::LUMA ? 0 : 512);
     const uint4* coef = (const uint4*)(a.coef + (size_t)g * 64);
     if (PACK) {
         const unsigned at = a.bits[g];                        // the block's bit offset in its frame's stream
@@ -453,19 +532,21 @@ __device__ inline uint2 jpeg_idct_rows(int (*tile)[65], int lb, int r, int (&o)[
 }
 
 // ---- idct: coefficients -> the sample planes ----------------------------------------------------------------------------------------
+template <int L>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_idct_kernel(JpegDecArgs a) {
+    using M = JpegMcu<L>;
     __shared__ int tile[MM_JPG_BLOCK / 8][65];
     __shared__ __attribute__((aligned(16))) short zz[MM_JPG_BLOCK / 8][64];
     const int tid = threadIdx.x, lb = tid >> 3, r = tid & 7;
     const long long g = (long long)blockIdx.x * (MM_JPG_BLOCK / 8) + lb;
     const long long gc = g < a.total_blocks ? g : 0;
     const int img = (int)(gc / a.blocks), rem = (int)(gc % a.blocks);
-    const int mcu = rem / 6, j = rem % 6, my = mcu / a.mx, mx = mcu % a.mx;
-    const int by = 2 * my + (j >> 1), bx = 2 * mx + (j & 1);    // (luma)
-    const bool skip = g >= a.total_blocks || (j < 4 && (by >= a.bh || bx >= a.bw));         // a dummy holds no pixel: never read
+    const int mcu = rem / M::BLOCKS, j = rem % M::BLOCKS, my = mcu / a.mx, mx = mcu % a.mx;
+    const int by = M::LV * my + (j >> M::LH_SHIFT), bx = M::LH * mx + (j & (M::LH - 1));    // (luma)
+    const bool skip = g >= a.total_blocks || (j < M::LUMA && (by >= a.bh || bx >= a.bw));   // a dummy holds no pixel: never read
     if (!skip) *(uint4*)&zz[lb][r * 8] = *(const uint4*)(a.coef + (size_t)g * 64 + r * 8);
     __syncthreads();
-    const int* div = a.par + MM_JPG_DIV + (j < 4 ? 0 : 64);
+    const int* div = a.par + MM_JPG_DIV + (j < M::LUMA ? 0 : 64);
     int d[8], o[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -475,18 +556,27 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_idct_kernel(JpegDecArgs a) 
     jpeg_idct8<11>(d, o);
     const uint2 row = jpeg_idct_rows(tile, lb, r, o);
     if (skip) return;
-    if (j < 4) {
-        const size_t yw = (size_t)a.mx * 16;
-        *(uint2*)(a.yp + ((size_t)img * a.my * 16 + by * 8 + r) * yw + bx * 8) = row;
+    if (j < M::LUMA) {
+        const size_t yw = (size_t)a.mx * M::W;
+        *(uint2*)(a.yp + ((size_t)img * a.my * M::H + by * 8 + r) * yw + bx * 8) = row;
     } else {
         const size_t cw = (size_t)a.mx * 8;
-        *(uint2*)(a.cp + (((size_t)img * 2 + (j - 4)) * a.my * 8 + my * 8 + r) * cw + mx * 8) = row;
+        *(uint2*)(a.cp + (((size_t)img * 2 + (j - M::LUMA)) * a.my * 8 + my * 8 + r) * cw + mx * 8) = row;
     }
 }
 
 // ---- pixels: upsample, convert, store -----------------------------------------------------------------------------------------------
 // the upsampled chroma sample at (y, x) of one component's plane c (cw bytes a row)
+template <int L>
 __device__ inline int jpeg_chroma_up(const JpegDecArgs& a, const unsigned char* c, size_t cw, int y, int x) {
+    if constexpr (L == MM_JPG_444) return c[y * cw + x];      // no upsampling
+    if constexpr (L == MM_JPG_422) {                          // h2v1: no vertical neighbour
+        const int cx = x >> 1;
+        const unsigned char* p = c + y * cw;
+        if (a.wd <= 2) return p[cx];
+        const int ox = (x & 1) ? min(cx + 1, a.wd - 1) : max(cx - 1, 0);
+        return (3 * p[cx] + p[ox] + ((x & 1) ? 2 : 1)) >> 2;
+    }
     const int r = y >> 1, cx = x >> 1;
     const unsigned char* p = c + r * cw;
     if (a.wd <= 2) return p[cx];
@@ -496,39 +586,43 @@ __device__ inline int jpeg_chroma_up(const JpegDecArgs& a, const unsigned char* 
     return (3 * s + so + ((x & 1) ? 7 : 8)) >> 4;
 }
 // pixel p of the output, over all frames: R | G << 8 | B << 16
+template <int L>
 __device__ inline unsigned jpeg_pixel(const JpegDecArgs& a, long long p, int& img, int& y, int& x) {
+    using M = JpegMcu<L>;
     const int hw = a.H * a.W;
     img = (int)(p / hw);
     const int rem = (int)(p % hw);
     y = rem / a.W; x = rem % a.W;
     const size_t cw = (size_t)a.mx * 8, cplane = (size_t)a.my * 8 * cw;
-    const int Y = a.yp[((size_t)img * a.my * 16 + y) * (cw * 2) + x];
+    const int Y = a.yp[((size_t)img * a.my * M::H + y) * (cw * M::LH) + x];
     const unsigned char* c = a.cp + (size_t)img * 2 * cplane;
-    const int cb = jpeg_chroma_up(a, c, cw, y, x) - 128, cr = jpeg_chroma_up(a, c + cplane, cw, y, x) - 128;
+    const int cb = jpeg_chroma_up<L>(a, c, cw, y, x) - 128, cr = jpeg_chroma_up<L>(a, c + cplane, cw, y, x) - 128;
     const int R = min(max(Y + ((91881 * cr + 32768) >> 16), 0), 255);
     const int G = min(max(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
     const int B = min(max(Y + ((116130 * cb + 32768) >> 16), 0), 255);
     return (unsigned)R | (unsigned)G << 8 | (unsigned)B << 16;
 }
 
+template <int L>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_pixels_u8_kernel(JpegDecArgs a) {
     const long long i = (long long)blockIdx.x * MM_JPG_BLOCK + threadIdx.x, byte0 = 4 * i, bytes = 3 * a.total_pixels;
     if (byte0 >= bytes) return;
     const long long p = byte0 / 3;
     int img, y, x;
-    unsigned long long seq = jpeg_pixel(a, p, img, y, x);      // the six bytes of pixels p and p + 1
-    if (p + 1 < a.total_pixels) seq |= (unsigned long long)jpeg_pixel(a, p + 1, img, y, x) << 24;
+    unsigned long long seq = jpeg_pixel<L>(a, p, img, y, x);   // the six bytes of pixels p and p + 1
+    if (p + 1 < a.total_pixels) seq |= (unsigned long long)jpeg_pixel<L>(a, p + 1, img, y, x) << 24;
     const unsigned w = (unsigned)(seq >> (8 * (int)(byte0 - 3 * p)));
     unsigned char* out = (unsigned char*)a.out + byte0;
     if (byte0 + 4 <= bytes) *(unsigned*)out = w;
     else for (int k = 0; k < (int)(bytes - byte0); ++k) out[k] = (unsigned char)(w >> (8 * k));
 }
 
+template <int L>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_pixels_f32_kernel(JpegDecArgs a) {
     const long long p = (long long)blockIdx.x * MM_JPG_BLOCK + threadIdx.x;
     if (p >= a.total_pixels) return;
     int img, y, x;
-    const unsigned q = jpeg_pixel(a, p, img, y, x);
+    const unsigned q = jpeg_pixel<L>(a, p, img, y, x);
     const size_t hw = (size_t)a.H * a.W;
     float* o = (float*)a.out + (size_t)img * 3 * hw + (size_t)y * a.W + x;
     o[0] = unquant(q & 255u); o[hw] = unquant((q >> 8) & 255u); o[2 * hw] = unquant(q >> 16);
@@ -582,16 +676,17 @@ struct JpegRoundtripLayout { size_t coef, yp, cp, bytes; };
 __host__ JpegRoundtripLayout jpeg_roundtrip_layout(const MMJpegRoundtripDesc* d) {
     JpegRoundtripLayout l = {0, 0, 0, 256};                   // mode L needs no workspace; the query still answers 256, so that 0 stays its refusal
     if (d->mode != MM_JPEG_MODE_RGB) return l;
-    const size_t n = (size_t)d->n, mcus = (size_t)((d->H + 15) / 16) * ((d->W + 15) / 16);
+    const JpegMcuShape m = jpeg_mcu_shape(jpeg_layout_of(d->mode, d->sampling));
+    const size_t n = (size_t)d->n, mcus = (size_t)((d->H + m.h - 1) / m.h) * ((d->W + m.w - 1) / m.w);
     Carve c;
-    l.coef = c.take(d->coef ? 0 : n * mcus * 6 * 128);
-    l.yp = c.take(n * mcus * 256);
+    l.coef = c.take(d->coef ? 0 : n * mcus * m.blocks * 128);
+    l.yp = c.take(n * mcus * m.w * m.h);
     l.cp = c.take(n * mcus * 128);
     l.bytes = c.at;
     return l;
 }
 size_t jpeg_roundtrip_workspace_bytes(const MMJpegRoundtripDesc* d) { return jpeg_roundtrip_layout(d).bytes; }
-size_t jpeg_coef_at(const MMJpegDesc* d) { return jpeg_layout(d).coef; }
+size_t jpeg_coef_at(const MMJpegModesDesc* d) { return jpeg_layout(d).coef; }
 
 int launch_jpeg_roundtrip(const MMJpegRoundtripDesc* d, hipStream_t s) {
     const dim3 wg(MM_JPG_BLOCK);
@@ -608,8 +703,10 @@ int launch_jpeg_roundtrip(const MMJpegRoundtripDesc* d, hipStream_t s) {
     }
     const JpegRoundtripLayout l = jpeg_roundtrip_layout(d);
     unsigned char* ws = (unsigned char*)d->workspace;
-    a.my = (d->H + 15) / 16; a.mx = (d->W + 15) / 16; a.blocks = a.my * a.mx * 6;
-    a.hd = (d->H + 1) / 2; a.wd = (d->W + 1) / 2;
+    const int layout = jpeg_layout_of(d->mode, d->sampling);
+    const JpegMcuShape m = jpeg_mcu_shape(layout);
+    a.my = (d->H + m.h - 1) / m.h; a.mx = (d->W + m.w - 1) / m.w; a.blocks = a.my * a.mx * m.blocks;
+    a.hd = (d->H + 1) / 2; a.wd = (d->W + 1) / 2;             // (4:2:0 reads both, 4:2:2 wd, 4:4:4 neither)
     a.total_blocks = (long long)d->n * a.blocks;
     a.yp = ws + l.yp; a.cp = ws + l.cp;
     const dim3 per_eight((unsigned)((a.total_blocks + MM_JPG_BLOCK / 8 - 1) / (MM_JPG_BLOCK / 8)));
@@ -622,16 +719,19 @@ int launch_jpeg_roundtrip(const MMJpegRoundtripDesc* d, hipStream_t s) {
         e.my = a.my; e.mx = a.mx; e.blocks = a.blocks;
         e.bh = a.bh; e.bw = a.bw; e.ch = a.hd;
         e.total_blocks = a.total_blocks;
-        hipLaunchKernelGGL(jpeg_transform_kernel, per_eight, wg, 0, s, e);
+        jpeg_by_layout<3>(layout, [&](auto L) { hipLaunchKernelGGL(jpeg_transform_kernel<decltype(L)::value>, per_eight, wg, 0, s, e); });
         a.coef = e.coef;
     }
-    hipLaunchKernelGGL(jpeg_idct_kernel, per_eight, wg, 0, s, a);
-    if (d->as_float) hipLaunchKernelGGL(jpeg_pixels_f32_kernel, dim3((unsigned)((a.total_pixels + MM_JPG_BLOCK - 1) / MM_JPG_BLOCK)), wg, 0, s, a);
-    else hipLaunchKernelGGL(jpeg_pixels_u8_kernel, dim3((unsigned)((3 * a.total_pixels + 4 * MM_JPG_BLOCK - 1) / (4 * MM_JPG_BLOCK))), wg, 0, s, a);
+    jpeg_by_layout<3>(layout, [&](auto L) {
+        constexpr int V = decltype(L)::value;
+        hipLaunchKernelGGL(jpeg_idct_kernel<V>, per_eight, wg, 0, s, a);
+        if (d->as_float) hipLaunchKernelGGL(jpeg_pixels_f32_kernel<V>, dim3((unsigned)((a.total_pixels + MM_JPG_BLOCK - 1) / MM_JPG_BLOCK)), wg, 0, s, a);
+        else hipLaunchKernelGGL(jpeg_pixels_u8_kernel<V>, dim3((unsigned)((3 * a.total_pixels + 4 * MM_JPG_BLOCK - 1) / (4 * MM_JPG_BLOCK))), wg, 0, s, a);
+    });
     return launch_ok("jpeg_roundtrip");
 }
 
-int launch_jpeg(const MMJpegDesc* d, hipStream_t s) {
+int launch_jpeg(const MMJpegModesDesc* d, hipStream_t s) {
     const JpegLayout l = jpeg_layout(d);
     unsigned char* ws = (unsigned char*)d->workspace;
     JpegArgs a = {};
@@ -645,10 +745,13 @@ int launch_jpeg(const MMJpegDesc* d, hipStream_t s) {
     if (hipMemsetAsync(a.raw, 0, (size_t)d->n * l.chunks * MM_JPEG_CHUNK_BYTES, s) != hipSuccess) return launch_ok("jpeg_zero");
     const dim3 wg(MM_JPG_BLOCK), per_frame((unsigned)d->n), per_chunk((unsigned)l.chunks, (unsigned)d->n);
     const unsigned per_block = (unsigned)((a.total_blocks + MM_JPG_BLOCK - 1) / MM_JPG_BLOCK);
-    hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((a.total_blocks + MM_JPG_BLOCK / 8 - 1) / (MM_JPG_BLOCK / 8))), wg, 0, s, a);
-    hipLaunchKernelGGL(jpeg_code_kernel<false>, dim3(per_block), wg, 0, s, a);
-    hipLaunchKernelGGL(jpeg_bit_offsets_kernel, per_frame, wg, 0, s, a);
-    hipLaunchKernelGGL(jpeg_code_kernel<true>, dim3(per_block), wg, 0, s, a);
+    jpeg_by_layout(l.layout, [&](auto L) {
+        constexpr int V = decltype(L)::value;
+        hipLaunchKernelGGL(jpeg_transform_kernel<V>, dim3((unsigned)((a.total_blocks + MM_JPG_BLOCK / 8 - 1) / (MM_JPG_BLOCK / 8))), wg, 0, s, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(jpeg_code_kernel<V, false>), dim3(per_block), wg, 0, s, a);
+        hipLaunchKernelGGL(jpeg_bit_offsets_kernel, per_frame, wg, 0, s, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(jpeg_code_kernel<V, true>), dim3(per_block), wg, 0, s, a);
+    });
     hipLaunchKernelGGL(jpeg_count_ff_kernel, per_chunk, wg, 0, s, a);
     hipLaunchKernelGGL(jpeg_place_kernel, per_frame, wg, 0, s, a);
     hipLaunchKernelGGL(jpeg_file_offsets_kernel, dim3(1), wg, 0, s, a);

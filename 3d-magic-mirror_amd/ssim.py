@@ -261,7 +261,7 @@ def recon_scores(pred, gt):
     return s.to(out_dev), iou.to(out_dev)
 
 
-def recon_scores_as_saved(pred, gt, quality=100, white_gt=False):
+def recon_scores_as_saved(pred, gt, quality=100, white_gt=False, files=False):
     """``recon_scores`` as the reference's loop computes it: on the images it has SAVED as JPEG files and read back (trainer.py:697-795,
     test.py:302-455), all on the device.  (B,4,H,W) fp32 pred and gt -> (ssim (B,), mask_iou (B,)), the composition of
       1. ``export_images(x, "rgb+mask")``, rounding "trunc" (``to_pil_image``'s ``mul(255).byte()``); ``white=white_gt`` for gt only (the
@@ -270,18 +270,28 @@ def recon_scores_as_saved(pred, gt, quality=100, white_gt=False):
          file, ``.convert('L')``), ``as_float``: ``to_tensor`` of the reopened images;
       3. ``ssim(ori, rec, data_range=1, size_average=False)`` and the mask-IoU kernel of ``recon_scores``.
     The ``.resize`` between open and score asks for the file's own size, which is the identity.  Equal, with torch.equal, to that
-    composition written out from the public functions."""
+    composition written out from the public functions.
+
+    files=True: ``(ssim, mask_iou, (ori, ori_mask, rec, rec_mask))``, the third being the four ``JpegBatch``es the loop writes, B files
+    each: the colour ones from the round trip's own transform pass (``jpeg_roundtrip(files=True)``), the two masks from
+    ``encode_jpeg(mask, quality, mode="L")``.  The masks' transform therefore runs twice, once inside the round trip (which keeps a block in
+    registers and forms no file) and once for the file: a mask is a third of a frame's bytes and one block an MCU, so the second pass
+    costs less than the copy it saves.  The scores are torch.equal to those of files=False."""
     from .export import export_images
-    from .jpeg import jpeg_roundtrip
+    from .jpeg import encode_jpeg, jpeg_roundtrip
     if pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 4:
         raise ValueError("recon_scores_as_saved expects two (B,4,H,W) tensors, got %s / %s" % (tuple(pred.shape), tuple(gt.shape)))
     pred, gt, out_dev = _on_device(pred, gt)
     with torch.no_grad():
-        back = []
+        back, saved = [], []
         for x, white in ((gt, bool(white_gt)), (pred, False)):
             rgb, mask = export_images(x, "rgb+mask", rounding="trunc", white=white)
-            back.append((jpeg_roundtrip(rgb, quality, "RGB", as_float=True), jpeg_roundtrip(mask, quality, "L", as_float=True)))
+            colour = jpeg_roundtrip(rgb, quality, "RGB", as_float=True, files=bool(files))
+            if files:
+                colour, batch = colour
+                saved += [batch, encode_jpeg(mask, quality, mode="L")]
+            back.append((colour, jpeg_roundtrip(mask, quality, "L", as_float=True)))
         (ori, ori_mask), (rec, rec_mask) = back
         s = ssim(ori, rec, data_range=1, size_average=False)
         iou = _mask_iou_rows(ori_mask, rec_mask)
-    return s.to(out_dev), iou.to(out_dev)
+    return (s.to(out_dev), iou.to(out_dev)) + ((tuple(saved),) if files else ())

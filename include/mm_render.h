@@ -1037,6 +1037,43 @@ size_t mm_jpeg_files_offset(const MMJpegDesc* desc);        /* where the files s
 int mm_jpeg_encode(const MMJpegDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * JPEG, every layout: mm_jpeg_encode with the MCU as a parameter -- the files Pillow's save(f, 'JPEG', quality=q, subsampling=s) writes
+ * of an (H,W,3) frame for s = 4:2:0, 4:2:2 and 4:4:4, and the greyscale file it writes of an (H,W) frame.  MMJpegDesc and mm_jpeg_* are
+ * this with mode RGB and sampling 4:2:0 (they forward here).  Colour conversion, DCT, quantiser, entropy coder, padding, stuffing and EOI
+ * are mm_jpeg_encode's; the layouts differ in the MCU alone:
+ *   4:2:0      16 x 16 pixels, blocks Y00 Y01 Y10 Y11 Cb Cr: above.
+ *   4:2:2      16 wide, 8 high, blocks Y0 Y1 Cb Cr.  Columns beyond W replicate the input's last column up to the MCU, rows beyond H its last
+ *              row up to the block.  Chroma is (c[2x] + c[2x+1] + bias) >> 1, bias 0 on even output columns and 1 on odd ones.  Y1 is a
+ *              dummy (no AC, Y0's DC) where 2 mx + 1 >= ceil(W / 8).  No vertical dummy and no downsampled-row rule.
+ *   4:4:4      8 x 8 pixels, blocks Y Cb Cr, edges replicated on all three planes; no downsampling, no dummies.
+ *   greyscale  mode L: frames are (n,H,W).  A non-interleaved scan: an MCU is one 8 x 8 block, ceil(H / 8) x ceil(W / 8) of them in raster
+ *              order, edges replicated, no dummies; the luma divisors, the luma tables, one DC predictor.
+ * params is MMJpegDesc's table in every layout (both divisor tables and all four code tables, whichever the layout reads); the file's
+ * head differs: a greyscale head has one DQT, a one-component SOF0 and SOS and the two luma DHT segments; a colour head has Y's sampling
+ * byte 0x22, 0x21 or 0x11.  The workspace is laid out as mm_jpeg_encode's, counted in the layout's own blocks (6, 4, 3 or 1 per MCU).
+ * Return codes as mm_jpeg_encode's; MM_ERR_BAD_SHAPE also for an unknown mode or sampling and for a sampling other than 0 with mode L;
+ * the block limits of MM_ERR_UNSUPPORTED count the layout's own blocks.  Every refusal comes before any GPU work.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_JPEG_SAMPLING_420 0
+#define MM_JPEG_SAMPLING_422 1
+#define MM_JPEG_SAMPLING_444 2
+typedef struct MMJpegModesDesc {
+    int32_t n, H, W;                /* the frames */
+    int32_t header_bytes;           /* bytes of the file's head in params */
+    int32_t mode;                   /* MM_JPEG_MODE_RGB or MM_JPEG_MODE_L (below) */
+    int32_t sampling;               /* MM_JPEG_SAMPLING_*; 0 with mode L */
+    const uint8_t* frames;          /* (n,H,W,3), or (n,H,W) in mode L; dense, any alignment */
+    const int32_t* params_host;     /* host memory */
+    const int32_t* params;          /* device memory, the same words */
+    void* workspace;
+    size_t workspace_bytes;
+} MMJpegModesDesc;
+size_t mm_jpeg_modes_query_workspace(const MMJpegModesDesc* desc);      /* reads n, H, W, header_bytes, mode, sampling */
+size_t mm_jpeg_modes_files_offset(const MMJpegModesDesc* desc);         /* where the files start in the workspace */
+size_t mm_jpeg_modes_coef_offset(const MMJpegModesDesc* desc);          /* where the coefficients lie in it, for mm_jpeg_roundtrip */
+int mm_jpeg_modes_encode(const MMJpegModesDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * JPEG round trip: n device frames as a decoder reads them back from the files above -- to the byte what Pillow's
  * Image.open(file).convert('RGB') gives for mm_jpeg_encode's file of an (H,W,3) frame (mode RGB, 4:2:0), and what
  * Image.open(file).convert('L') gives for the greyscale file libjpeg writes of an (H,W) frame (mode L; that file is never formed).  No
@@ -1057,7 +1094,12 @@ int mm_jpeg_encode(const MMJpegDesc* desc, mm_stream_t stream);
  * read).  out: bytes (n,H,W,3) / (n,H,W), or with as_float fp32 v / 255 in planes (n,3,H,W) / (n,H,W); 4-byte aligned, never the input.
  * The workspace is the caller's, mm_jpeg_roundtrip_query_workspace bytes, 16-byte aligned (mode RGB: the coefficients unless coef is
  * given, and the Y, Cb and Cr sample planes, 1.5 bytes per pixel of whole MCUs; mode L uses none and the query answers 256).
- * Return codes as mm_jpeg_encode's: MM_ERR_BAD_SHAPE also for an unknown mode; MM_ERR_WORKSPACE also for a misaligned coef or out.
+ * Sampling (mode RGB): the file is that of mm_jpeg_modes_encode with the same sampling, and the sample planes follow its MCU.
+ *   4:4:4       no upsampling; convert as above.
+ *   4:2:2       Cb and Cr are real on H x ceil(W / 2).  ceil(W / 2) > 2: h2v1 "fancy" upsampling, out[2x] = (3 s[x] + s[x-1] + 1) >> 2,
+ *               out[2x+1] = (3 s[x] + s[x+1] + 2) >> 2, s[-1] := s[0], s[wd] := s[wd-1]; otherwise replication.  No vertical neighbour.
+ * Return codes as mm_jpeg_encode's: MM_ERR_BAD_SHAPE also for an unknown mode or sampling and for a sampling other than 0 with mode L;
+ * MM_ERR_WORKSPACE also for a misaligned coef or out.
  * Mode RGB: two or three launches (transform unless coef is given, idct, pixels); mode L: one.  No host synchronisation; bitwise reproducible.
  * ------------------------------------------------------------------------------------------------------------------ */
 #define MM_JPEG_MODE_RGB 0
@@ -1066,9 +1108,9 @@ typedef struct MMJpegRoundtripDesc {
     int32_t n, H, W;                /* the frames */
     int32_t mode;                   /* MM_JPEG_MODE_RGB or MM_JPEG_MODE_L */
     int32_t as_float;               /* fp32 planes instead of bytes */
-    int32_t reserved;               /* 0 */
+    int32_t sampling;               /* mode RGB: MM_JPEG_SAMPLING_* (0: 4:2:0, as every caller before it had a meaning); mode L: 0 */
     const uint8_t* frames;          /* (n,H,W,3) or (n,H,W), dense, any alignment */
-    const int16_t* coef;            /* mode RGB: NULL, or (n, blocks, 64) as mm_jpeg_encode leaves them; 16-byte aligned */
+    const int16_t* coef;            /* mode RGB: NULL, or (n, blocks, 64) as mm_jpeg_encode / mm_jpeg_modes_encode of the same sampling leaves them; 16-byte aligned */
     const int32_t* params_host;     /* host memory */
     const int32_t* params;          /* device memory, the same words */
     void* out;
@@ -1197,7 +1239,7 @@ const char* mm_last_error_detail(void);
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
- * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc (31, 34 and 36 are unassigned). */
+ * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc, 42 MMJpegModesDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1219,7 +1261,8 @@ size_t mm_struct_size(int which);
  * unassigned and returns 0 --, an addition, detected by mm_struct_size(37) != 0; still 9: MMJpegRoundtripDesc,
  * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0; still 9: MMGifDesc and mm_gif_*, struct id 39, an addition, detected by mm_struct_size(39) != 0; still 9: MMPoissonDesc and
  * mm_poisson_frames, struct id 40, an addition, detected by mm_struct_size(40) != 0; still 9: MMPngDesc and mm_png_*, struct id 41, an
- * addition, detected by mm_struct_size(41) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * addition, detected by mm_struct_size(41) != 0; still 9: MMJpegModesDesc and mm_jpeg_modes_*, struct id 42, an addition, detected by
+ * mm_struct_size(42) != 0, and MMJpegRoundtripDesc.reserved named sampling, where 0, all a caller could pass, keeps its meaning).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
