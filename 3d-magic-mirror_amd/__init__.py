@@ -14,6 +14,7 @@ from .poisson import lower_poisson, poisson_frames  # noqa: F401
 from .jpeg import JpegBatch, encode_jpeg, jpeg_roundtrip, lower_jpeg  # noqa: F401
 from .gif import GIF_SEGMENT, GifFile, encode_gif, quantize_frames  # noqa: F401
 from .png import PNG_MAX_SEGMENT, PNG_SEGMENT, PngBatch, encode_png, lower_png  # noqa: F401
+from .fid import FID_SPLIT, FidStatistics, fid_score, frechet_distance, inception_input  # noqa: F401
 from .input_batches import ImagePool, assemble_batch, assemble_records, draw_augmentation, lower_batch  # noqa: F401
 from .interpolate import interpolate_attributes, mix_attributes, resample_collapsed  # noqa: F401
 from .ssim import MS_SSIM, SSIM, ms_ssim, recon_scores, recon_scores_as_saved, ssim  # noqa: F401

@@ -256,6 +256,18 @@ class MMPngDesc(ctypes.Structure):
                 ("frames", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+FID_MAX_SIDE, FID_SUM_ROWS, FID_SPLIT = 1024, 256, 4096      # MM_FID_MAX_SIDE, MM_FID_SUM_ROWS, MM_FID_SPLIT
+
+
+class MMFidInputDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("H", c_i), ("W", c_i), ("Ho", c_i), ("Wo", c_i), ("normalize", c_i), ("frames", c_p), ("params_host", c_p),
+                ("params", c_p), ("out", c_p)]
+
+
+class MMFidStatsDesc(ctypes.Structure):
+    _fields_ = [("N", c_i), ("D", c_i), ("x", c_p), ("mu", c_p), ("sigma", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 PROF_RENDER = ("vertex_fwd", "raster_fwd", "pixel_bwd", "gather_bwd", "vertex_bwd", "order")
 ABI_VERSION = 9
 OPT_WALK_BLOCK, OPT_WALK_WAVE = 1 << 1, 1 << 2
@@ -352,6 +364,9 @@ SIGNATURES = {
     "mm_png_query_workspace": (c_z, [P(MMPngDesc)]),
     "mm_png_files_offset": (c_z, [P(MMPngDesc)]),
     "mm_png_encode": (c_int, [P(MMPngDesc), c_p]),
+    "mm_fid_input": (c_int, [P(MMFidInputDesc), c_p]),
+    "mm_fid_stats_query_workspace": (c_z, [P(MMFidStatsDesc)]),
+    "mm_fid_stats": (c_int, [P(MMFidStatsDesc), c_p]),
     "mm_build_vertex_corner_csr": (c_int, [c_i, c_i, c_p, c_p, c_p]),
     "mm_build_vertex_corner_csr_device": (c_int, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mm_build_vertex_corner_table": (c_int, [c_i, c_i, c_p, c_i, c_p]),
@@ -368,7 +383,8 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               14: MMTexMapGrads, 15: MMShDesc, 16: MMShGrads, 17: MMMaskIouDesc, 18: MMSsimDesc, 19: MMSsimGrads, 20: MMShapeFeatDesc,
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
-              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc, 42: MMJpegModesDesc}
+              35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc, 42: MMJpegModesDesc,
+              43: MMFidInputDesc, 44: MMFidStatsDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 

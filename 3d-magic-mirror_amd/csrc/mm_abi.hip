@@ -79,6 +79,9 @@ size_t png_files_at(const MMPngDesc*);
 long long png_idat_cap(const MMPngDesc*);
 long long png_all_segs(const MMPngDesc*);
 int launch_png(const MMPngDesc*, hipStream_t);
+int launch_fid_input(const MMFidInputDesc*, hipStream_t);
+size_t fid_stats_workspace_bytes(const MMFidStatsDesc*);
+int launch_fid_stats(const MMFidStatsDesc*, hipStream_t);
 }  // namespace mm
 
 static bool sizes_positive(const MMRenderDesc* d) { return d->B > 0 && d->H > 0 && d->W > 0 && d->V > 0 && d->F > 0 && d->Ht > 0 && d->Wt > 0; }
@@ -1005,6 +1008,43 @@ int mm_png_encode(const MMPngDesc* d, mm_stream_t stream) {
     return mm::launch_png(d, (hipStream_t)stream);
 }
 
+int mm_fid_input(const MMFidInputDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->n <= 0 || d->H < 1 || d->W < 1 || d->Ho < 1 || d->Wo < 1) return MM_ERR_BAD_SHAPE;
+    if (d->H > MM_FID_MAX_SIDE || d->W > MM_FID_MAX_SIDE || d->Ho > MM_FID_MAX_SIDE || d->Wo > MM_FID_MAX_SIDE) return MM_ERR_BAD_SHAPE;
+    if (!d->frames || !d->params_host || !d->params || !d->out) return MM_ERR_NULL_POINTER;
+    if ((uintptr_t)d->params & 15) return MM_ERR_BAD_SHAPE;
+    if ((long long)d->n * ((d->Ho + 7) / 8) > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;
+    const int32_t* row = d->params_host;                          // every tap inside its axis, before anything is launched
+    for (int i = 0; i < d->Wo + d->Ho; ++i, row += 4) {
+        const int32_t n_in = i < d->Wo ? d->W : d->H;
+        if (row[0] < 0 || row[0] >= n_in || row[1] < 0 || row[1] >= n_in) return MM_ERR_BAD_SHAPE;
+    }
+    mm::clear_stale_error();
+    return mm::launch_fid_input(d, (hipStream_t)stream);
+}
+
+// the sizes a statistics call may have: MM_OK, or why not
+static int check_fid_stats_shape(const MMFidStatsDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->N < 2 || d->D < 1) return MM_ERR_BAD_SHAPE;
+    if (d->D > 65535 || d->N > 65535 * MM_FID_SUM_ROWS) return MM_ERR_UNSUPPORTED;      // the grids' y and the tile count
+    return MM_OK;
+}
+
+size_t mm_fid_stats_query_workspace(const MMFidStatsDesc* d) {
+    return check_fid_stats_shape(d) == MM_OK ? mm::fid_stats_workspace_bytes(d) : 0;
+}
+
+int mm_fid_stats(const MMFidStatsDesc* d, mm_stream_t stream) {
+    const int shape = check_fid_stats_shape(d);
+    if (shape != MM_OK) return shape;
+    if (!d->x || !d->mu || !d->sigma || !d->workspace) return MM_ERR_NULL_POINTER;
+    if (d->workspace_bytes < mm::fid_stats_workspace_bytes(d) || ((uintptr_t)d->workspace & 255)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_fid_stats(d, (hipStream_t)stream);
+}
+
 int mm_build_vertex_corner_csr(int32_t V, int32_t F, const int32_t* faces, int32_t* offsets, int32_t* items) {
     if (!faces || !offsets || !items) return MM_ERR_NULL_POINTER;
     if (V <= 0 || F <= 0) return MM_ERR_BAD_SHAPE;
@@ -1080,7 +1120,7 @@ size_t mm_struct_size(int which) {
         case 33: return sizeof(MMRenderIndexedDesc); case 35: return sizeof(MMPyramidDesc);     // (34: unassigned)
         case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
         case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc); case 41: return sizeof(MMPngDesc);
-        case 42: return sizeof(MMJpegModesDesc);
+        case 42: return sizeof(MMJpegModesDesc); case 43: return sizeof(MMFidInputDesc); case 44: return sizeof(MMFidStatsDesc);
         default: return 0;
     }
 }

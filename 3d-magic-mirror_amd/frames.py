@@ -37,23 +37,28 @@ def gaussian_taps(kernel_size, sigma):
     return pdf / pdf.sum(-1, keepdim=True)
 
 
-def resize_taps(n_in, n_out, antialias=False):
+def resize_taps(n_in, n_out, antialias=False, coords=np.float32):
     """One axis of torch's bilinear resize with align_corners=False as taps: (start (n_out,) int32, count (n_out,) int32, weights
     (n_out, MAX_TAPS) float32, zero beyond count); output i = sum_t weights[i, t] * input[start[i] + t].
 
     antialias=False (tensors under torchvision 0.12): src = max(scale (i + 0.5) - 0.5, 0), taps floor(src) and the next, weights
     1 - l and l.  antialias=True (current torchvision): the triangle filter of support max(scale, 1) around scale (i + 0.5),
     normalised.  Taps of weight 0 at either end are dropped (so n_in == n_out is the identity, one tap of 1); more than MAX_TAPS taps
-    -- an antialiased ratio beyond 3.5 -- are refused."""
+    -- an antialiased ratio beyond 3.5 -- are refused.
+
+    coords (antialias=False): the type the source coordinate is formed in.  np.float32 is torch's fp32 kernel, whose coordinate carries the
+    rounding of a number as large as n_in (1e-5 of a weight at n_in = 128); np.float64 is the resize of a float64 tensor, each weight
+    then rounded to fp32 once (fid.py: its inputs are held to the float64 composition)."""
     n_in, n_out = int(n_in), int(n_out)
     if n_in < 1 or n_out < 1:
         raise ValueError("n_in and n_out must be positive, got %r" % ((n_in, n_out),))
     i = np.arange(n_out)
     if not antialias:
-        scale = np.float32(n_in) / np.float32(n_out)
-        src = np.maximum(scale * (i.astype(np.float32) + np.float32(0.5)) - np.float32(0.5), np.float32(0))
+        ct = np.dtype(coords).type
+        scale = ct(n_in) / ct(n_out)
+        src = np.maximum(scale * (i.astype(ct) + ct(0.5)) - ct(0.5), ct(0))
         i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
-        lam = (src - i0.astype(np.float32)).astype(np.float64)
+        lam = (src - i0.astype(ct)).astype(np.float64)
         lam = np.where(i0 + 1 > n_in - 1, 0.0, np.clip(lam, 0.0, 1.0))
         start, size = i0, np.full(n_out, 2)
         w = np.zeros((n_out, 2))

@@ -1215,6 +1215,51 @@ size_t mm_png_files_offset(const MMPngDesc* desc);          /* where the files s
 int mm_png_encode(const MMPngDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * FID around the Inception network (csrc/mm_fid.hip; fid_score.py:71-255, inception.py:129-163).  The network stays the caller's.
+ *
+ * mm_fid_input: 8-bit frames to the network's input batch, one launch, no workspace: out[f, c, y, x] from frames[f, :, :, c] as
+ *   t(b) = float(b) / 255.0f (IEEE), h(r) = w0x * t(r, i0x) + w1x * t(r, i1x) on the source rows r = i0y and i1y, v = w0y * h(i0y) + w1y * h(i1y),
+ *   out = 2 * v - 1 with `normalize`, v without; every product and sum rounded in fp32, nothing contracted.  The rows {i0, i1, w0, w1} of the
+ *   two axes are torch's bilinear resize with align_corners=False lowered by the caller (a single tap is w1 = 0 and i1 = i0 or the clamped
+ *   neighbour; no resize is i0 = i1 = the index, w0 = 1, w1 = 0).  params_host is read before the call returns: every index is held to its axis.
+ *   MM_ERR_BAD_SHAPE: n < 1; H, W, Ho or Wo outside 1..MM_FID_MAX_SIDE; an index outside its axis.  MM_ERR_UNSUPPORTED: more than 2^31 - 1
+ *   workgroups (n * ceil(Ho / 8)).  No host synchronisation; every output float is written by one lane (bitwise reproducible).
+ *
+ * mm_fid_stats: mu (D) and sigma (D,D) in float64 of N rows of fp32 features, with the meaning of np.mean(act, 0) and
+ *   np.cov(act, rowvar=False) of their float64 copy: the data is centred by mu first and the Gram matrix divided once by N - 1.
+ *   Order: column sums in float64 over chunks of MM_FID_SUM_ROWS rows, rows ascending, the chunks then added ascending, mu = sum / N; the
+ *   centred Gram matrix over splits of MM_FID_SPLIT rows, four rows per v_mfma_f64_16x16x4_f64 step, rows ascending, for the 64 x 64 tiles on or
+ *   above the diagonal; the splits added ascending, one division, and (i, j) and (j, i) stored from the same value.  Rows beyond N and columns
+ *   beyond D enter as zeros.  No floating-point atomics; bitwise reproducible; sigma is exactly symmetric.  Four launches.
+ *   The workspace is the caller's, mm_fid_stats_query_workspace bytes, 256-byte aligned; its contents mean nothing after the call.
+ *   MM_ERR_BAD_SHAPE: N < 2 or D < 1.  MM_ERR_UNSUPPORTED: D > 65535 or N > 65535 * MM_FID_SUM_ROWS (the query returns 0).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_FID_MAX_SIDE 1024        /* H, W, Ho, Wo: sixteen source rows of 3 W bytes fit the default 64 KiB of LDS */
+#define MM_FID_SUM_ROWS 256         /* rows of one column-sum chunk */
+#define MM_FID_SPLIT 4096           /* rows of one split of the Gram matrix: D = 2048 has 528 tiles, more than two per CU, in every split */
+typedef struct MMFidInputDesc {
+    int32_t n, H, W;                /* the frames */
+    int32_t Ho, Wo;                 /* the output planes */
+    int32_t normalize;              /* 1: 2 v - 1 */
+    const uint8_t* frames;          /* (n,H,W,3), dense, any alignment */
+    const int32_t* params_host;     /* (Wo + Ho, 4) int32 {i0, i1, w0, w1 (float bits)}: the rows of x, then of y */
+    const int32_t* params;          /* the same on the device, 16-byte aligned */
+    float* out;                     /* (n,3,Ho,Wo), dense; 16-byte stores where it is 16-byte aligned */
+} MMFidInputDesc;
+int mm_fid_input(const MMFidInputDesc* desc, mm_stream_t stream);
+
+typedef struct MMFidStatsDesc {
+    int32_t N, D;                   /* rows and columns of the features */
+    const float* x;                 /* (N,D), dense */
+    double* mu;                     /* (D) */
+    double* sigma;                  /* (D,D) */
+    void* workspace;
+    size_t workspace_bytes;
+} MMFidStatsDesc;
+size_t mm_fid_stats_query_workspace(const MMFidStatsDesc* desc);      /* reads N, D */
+int mm_fid_stats(const MMFidStatsDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -1239,7 +1284,8 @@ const char* mm_last_error_detail(void);
  * 19 MMSsimGrads, 20 MMShapeFeatDesc, 21 MMShapeFeatGrads, 22 MMCameraFeatDesc, 23 MMCameraFeatGrads, 24 MMInterpDesc,
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
- * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc, 42 MMJpegModesDesc (31, 34 and 36 are unassigned). */
+ * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc, 42 MMJpegModesDesc,
+ * 43 MMFidInputDesc, 44 MMFidStatsDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1262,7 +1308,9 @@ size_t mm_struct_size(int which);
  * mm_jpeg_roundtrip_query_workspace / mm_jpeg_roundtrip and mm_jpeg_coef_offset, struct id 38, an addition, detected by mm_struct_size(38) != 0; still 9: MMGifDesc and mm_gif_*, struct id 39, an addition, detected by mm_struct_size(39) != 0; still 9: MMPoissonDesc and
  * mm_poisson_frames, struct id 40, an addition, detected by mm_struct_size(40) != 0; still 9: MMPngDesc and mm_png_*, struct id 41, an
  * addition, detected by mm_struct_size(41) != 0; still 9: MMJpegModesDesc and mm_jpeg_modes_*, struct id 42, an addition, detected by
- * mm_struct_size(42) != 0, and MMJpegRoundtripDesc.reserved named sampling, where 0, all a caller could pass, keeps its meaning).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_struct_size(42) != 0, and MMJpegRoundtripDesc.reserved named sampling, where 0, all a caller could pass, keeps its meaning; still 9: MMFidInputDesc with
+ * mm_fid_input, struct id 43, and MMFidStatsDesc with mm_fid_stats_query_workspace / mm_fid_stats, struct id 44, additions, detected by
+ * mm_struct_size(43) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
