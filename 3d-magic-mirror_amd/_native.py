@@ -240,6 +240,15 @@ class MMJpegRoundtripDesc(ctypes.Structure):
                 ("params_host", c_p), ("params", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+JPEG_DEC_FILE_INTS, JPEG_DEC_SEGMENT_INTS, JPEG_DEC_SET_INTS, JPEG_TABLE_WORDS = 16, 6, 8, 356      # MM_JPEG_DEC_*_INTS, MM_JPEG_TABLE_WORDS
+JPEG_DEC_MAX_FILES, JPEG_DEC_MAX_BLOCKS, JPEG_DEC_GROUP = 1 << 20, 1 << 24, 16      # MM_JPEG_DEC_MAX_*, MM_JPEG_DEC_GROUP
+
+
+class MMJpegDecodeDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("mode", c_i), ("n_segments", c_i), ("n_qtables", c_i), ("n_htables", c_i), ("n_sets", c_i), ("n_bytes", ctypes.c_int64),
+                ("bytes", c_p), ("tables_host", c_p), ("tables", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 GIF_SEGMENT, GIF_MAX_SEGMENT = 1024, 3838      # MM_GIF_SEGMENT, MM_GIF_MAX_SEGMENT
 
 
@@ -364,6 +373,8 @@ SIGNATURES = {
     "mm_png_query_workspace": (c_z, [P(MMPngDesc)]),
     "mm_png_files_offset": (c_z, [P(MMPngDesc)]),
     "mm_png_encode": (c_int, [P(MMPngDesc), c_p]),
+    "mm_jpeg_decode_query_workspace": (c_z, [P(MMJpegDecodeDesc)]),
+    "mm_jpeg_decode": (c_int, [P(MMJpegDecodeDesc), c_p]),
     "mm_fid_input": (c_int, [P(MMFidInputDesc), c_p]),
     "mm_fid_stats_query_workspace": (c_z, [P(MMFidStatsDesc)]),
     "mm_fid_stats": (c_int, [P(MMFidStatsDesc), c_p]),
@@ -384,7 +395,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
               35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc, 42: MMJpegModesDesc,
-              43: MMFidInputDesc, 44: MMFidStatsDesc}
+              43: MMFidInputDesc, 44: MMFidStatsDesc, 45: MMJpegDecodeDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 

@@ -81,6 +81,40 @@ class ImagePool:
         self.offsets_dev = self.buffer[tables:tables + 8 * (n + 1)].view(torch.int64)
         self.sizes_dev = self.buffer[tables + 8 * (n + 1):].view(torch.int32).view(n, 2)
 
+    @classmethod
+    def from_jpeg(cls, files, segs, device):
+        """The pool of JPEG ``files`` (a list of bytes / paths, or a ``JpegBatch``) decoded on ``device`` by ``decode_jpeg`` straight into
+        the image region of the pool's one buffer: what ``ImagePool([np.asarray(Image.open(f).convert('RGB')) for f in files], segs, device)``
+        holds, without the host decode and the 3 bytes a pixel of upload.  The masks and the two tables go up in one copy, the files' bytes in the
+        decoder's.  ValueError: what ``decode_jpeg`` rejects, masks that do not match the files' sizes, damaged files."""
+        from . import jpeg_decode as JD
+        if device is None:
+            raise ValueError("ImagePool.from_jpeg decodes on a device; on the host, ImagePool(decode_jpeg_host(files)[0], segs)")
+        low = JD.lower_jpeg_decode(files, "RGB")
+        segs = [np.asarray(sg) for sg in segs]
+        n = low["n"]
+        if len(segs) != n:
+            raise ValueError("files and segs must be two non-empty lists of the same length, got %d and %d" % (n, len(segs)))
+        for i, sg in enumerate(segs):
+            if sg.dtype != np.uint8 or sg.shape != tuple(low["sizes"][i]):
+                raise ValueError("image %d: need a uint8 mask %s, got %s %s" % (i, tuple(low["sizes"][i]), sg.dtype, sg.shape))
+        self = cls.__new__(cls)
+        self.sizes, self.offsets, self.device = low["sizes"], low["offsets"], torch.device(device)
+        P = int(self.offsets[-1])
+        tables = (4 * P + 7) // 8 * 8                          # the layout of __init__'s buffer
+        self.buffer = torch.empty(tables + 8 * (n + 1) + 8 * n, dtype=torch.uint8, device=self.device)
+        head = np.zeros(self.buffer.numel() - 3 * P, dtype=np.uint8)          # everything behind the images: masks, padding, offsets, sizes
+        head[:P] = np.concatenate([sg.reshape(-1) for sg in segs])
+        head[tables - 3 * P:tables - 3 * P + 8 * (n + 1)] = self.offsets.view(np.uint8)
+        head[tables - 3 * P + 8 * (n + 1):] = self.sizes.reshape(-1).view(np.uint8)
+        self.images, self.segs = self.buffer[:3 * P], self.buffer[3 * P:4 * P]
+        self.offsets_dev = self.buffer[tables:tables + 8 * (n + 1)].view(torch.int64)
+        self.sizes_dev = self.buffer[tables + 8 * (n + 1):].view(torch.int32).view(n, 2)
+        N.require_device(self.buffer)
+        self.buffer[3 * P:].copy_(torch.from_numpy(head))                   # the masks and the tables: one upload
+        JD.decode_jpeg(low, out=self.images)                                # the files: the decoder's one upload, then straight into the image region
+        return self
+
     def __len__(self):
         return self.sizes.shape[0]
 

@@ -17,8 +17,8 @@ made on the device.
 host side of ``mm_jpeg_roundtrip``.
 
 Out of scope: 4:1:1 and 4:4:0 subsampling, CMYK / RGBA, ``optimize=True``, progressive, restart markers, EXIF / ICC, writing to
-disk beyond ``JpegBatch.write``.  The round trip of our own frames is ``jpeg_roundtrip``; decoding arbitrary files (an entropy decoder)
-stays out of scope.  Device tensors only."""
+disk beyond ``JpegBatch.write``.  The round trip of our own frames is ``jpeg_roundtrip``; decoding arbitrary files (marker parser, the
+file's own tables, an entropy decoder, restart intervals) is ``decode_jpeg`` in jpeg_decode.py.  Device tensors only."""
 import ctypes
 import functools
 

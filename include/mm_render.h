@@ -1260,6 +1260,56 @@ size_t mm_fid_stats_query_workspace(const MMFidStatsDesc* desc);      /* reads N
 int mm_fid_stats(const MMFidStatsDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * JPEG decoding: n baseline JPEG FILES, back to back in device memory, as 8-bit frames -- to the byte what Pillow's
+ * Image.open(file).convert('RGB') gives (mode RGB; a greyscale file replicates its plane) or .convert('L') of a greyscale file (mode L).
+ * csrc/mm_jpeg_decode.hip; the caller parses the markers (jpeg_decode.py: lower_jpeg_decode) and hands over tables of int32 words:
+ *   files     n x MM_JPEG_DEC_FILE_INTS: H, W, layout (0: 4:2:0, 1: 4:2:2, 2: 4:4:4, 3: one component), MCU columns, MCU rows, first block,
+ *             byte offset of its luma plane, byte offset of its chroma planes, quantisation table of components 0, 1, 2; the rest 0.
+ *             Blocks and planes are dense in file order: an MCU has 6, 4, 3 or 1 blocks; the luma plane is MCU rows x MCU columns of
+ *             16 x 16, 16 x 8 (wide x high), 8 x 8 or 8 x 8 bytes, the two chroma planes 8 x 8 bytes per MCU each (none for layout 3).
+ *   offsets   (n + 1) int64 (8-byte aligned in the table): file i's pixels start at pixel offsets[i] of out, H * W pixels, no padding
+ *   segments  n_segments x MM_JPEG_DEC_SEGMENT_INTS: file, first MCU, MCU count, byte begin, byte end, table set.  One lane decodes one
+ *             segment; n_segments is a multiple of MM_JPEG_DEC_GROUP and the MM_JPEG_DEC_GROUP segments of a workgroup share one table set
+ *             (count 0: a filler).
+ *   qtables   n_qtables x 64, natural order, each 1..255
+ *   htables   n_htables x MM_JPEG_TABLE_WORDS = 356 words (csrc/mm_jpeg_entropy.h: look-ahead, maxcode, valoffset, symbols)
+ *   sets      n_sets x MM_JPEG_DEC_SET_INTS: the tables DC 0, DC 1, AC 0, AC 1; bits 2c / 2c + 1: component c's DC / AC table; the rest 0
+ * in this order in one buffer, given twice: tables_host is read (and every record re-checked) before the call returns, tables is the
+ * same on the device.  One memset and three launches whatever n: entropy decode (Huffman, FF 00 stuffing, DC prediction per segment) into
+ * zeroed int16 zigzag blocks, dequantise + islow IDCT into sample planes, fancy upsampling + YCbCr -> RGB + store (the arithmetic of
+ * mm_jpeg_roundtrip).  out may start at any byte.  A damaged stream cannot read or write out of range; its file's status gets
+ * MM_JPEG_ST_* bits (csrc/mm_jpeg_entropy.h) and the coefficients after the damage stay zero.
+ * The workspace is the caller's, mm_jpeg_decode_query_workspace bytes, 16-byte aligned: the coefficients (128 bytes per block), then, on
+ * the next multiple of 256, status (n int32), then the sample planes.
+ * MM_ERR_BAD_SHAPE: a count < 1 (n_segments not a positive multiple of MM_JPEG_DEC_GROUP), an unknown mode, a record that contradicts itself or its
+ * neighbours (sizes, MCU counts, block or plane or pixel offsets not the running sums, a segment's MCU range outside its file or its
+ * bytes outside [0, n_bytes) or not begin <= end, a table index out of range, mixed table sets in a workgroup, a layout other than 3 in
+ * mode L, a quantiser outside 1..255).  MM_ERR_UNSUPPORTED: n > MM_JPEG_DEC_MAX_FILES, a file of more than MM_JPEG_MAX_BLOCKS blocks, more
+ * than MM_JPEG_DEC_MAX_BLOCKS blocks in the call, n_bytes >= 2^31 (the query returns 0 for all of these).  MM_ERR_WORKSPACE: too small or misaligned, or tables not 16-byte aligned.  Every refusal comes before any GPU work.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_JPEG_DEC_FILE_INTS 16
+#define MM_JPEG_DEC_SEGMENT_INTS 6
+#define MM_JPEG_DEC_SET_INTS 8
+#define MM_JPEG_DEC_GROUP 16        /* segments of one workgroup (one wave; the other lanes only help to stage the tables): decoding is bound by
+                                     * the latency of one lane, so few lanes a wave spread a batch over more CUs and wait for fewer stragglers */
+#define MM_JPEG_DEC_MAX_FILES (1 << 20)
+#define MM_JPEG_DEC_MAX_BLOCKS (1 << 24)
+typedef struct MMJpegDecodeDesc {
+    int32_t n;                      /* files */
+    int32_t mode;                   /* MM_JPEG_MODE_RGB: out is 3 bytes a pixel; MM_JPEG_MODE_L: 1, greyscale files only */
+    int32_t n_segments, n_qtables, n_htables, n_sets;
+    int64_t n_bytes;                /* of `bytes` */
+    const uint8_t* bytes;           /* the files, back to back; any alignment */
+    const int32_t* tables_host;     /* files | offsets | segments | qtables | htables | sets */
+    const int32_t* tables;          /* the same on the device, 16-byte aligned */
+    uint8_t* out;                   /* offsets[n] * (3 or 1) bytes, any alignment */
+    void* workspace;
+    size_t workspace_bytes;
+} MMJpegDecodeDesc;
+size_t mm_jpeg_decode_query_workspace(const MMJpegDecodeDesc* desc);      /* reads the counts and tables_host */
+int mm_jpeg_decode(const MMJpegDecodeDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -1285,7 +1335,7 @@ const char* mm_last_error_detail(void);
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
  * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc, 42 MMJpegModesDesc,
- * 43 MMFidInputDesc, 44 MMFidStatsDesc (31, 34 and 36 are unassigned). */
+ * 43 MMFidInputDesc, 44 MMFidStatsDesc, 45 MMJpegDecodeDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1310,7 +1360,8 @@ size_t mm_struct_size(int which);
  * addition, detected by mm_struct_size(41) != 0; still 9: MMJpegModesDesc and mm_jpeg_modes_*, struct id 42, an addition, detected by
  * mm_struct_size(42) != 0, and MMJpegRoundtripDesc.reserved named sampling, where 0, all a caller could pass, keeps its meaning; still 9: MMFidInputDesc with
  * mm_fid_input, struct id 43, and MMFidStatsDesc with mm_fid_stats_query_workspace / mm_fid_stats, struct id 44, additions, detected by
- * mm_struct_size(43) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_struct_size(43) != 0; still 9: MMJpegDecodeDesc with mm_jpeg_decode_query_workspace / mm_jpeg_decode, struct id 45, an addition, detected by
+ * mm_struct_size(45) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
