@@ -1,7 +1,7 @@
 // mm_jpeg.hip -- 8-bit device frames (n,H,W,3) as baseline JPEG files, for gfx950: what the reference's scripts do on the host per image with
 // to_pil_image(X[i, :3].cpu()).save(name, 'JPEG', quality=100) (trainer.py:51, test.py:53, generate_market++.py:55,
 // tool/generate_market_test.py:57, ...).  Every file equals Pillow's (libjpeg-turbo's) byte for byte: baseline, 4:2:0, the standard
-// Huffman tables.  The MCU is a template parameter (JpegMcu below): 4:2:0 is written out here; 4:2:2, 4:4:4 and greyscale -- masks (n,H,W),
+// Huffman tables.  The MCU is a template parameter (JpegMcu of mm_jpeg_idct.h): 4:2:0 is written out here; 4:2:2, 4:4:4 and greyscale -- masks (n,H,W),
 // the files to_pil_image(X[i, 3]).save(...) writes -- differ in the edges, the chroma and the block order alone, as said at JpegMcu.  The host makes the tables and the header; everything after SOS is made here.  Integer arithmetic only (>> is
 // arithmetic), in libjpeg's order:
 //   colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
@@ -43,7 +43,7 @@
 #include <type_traits>
 
 #include "mm_device.h"
-#include "mm_jpeg_idct.h"                                    // JpegMcu, the zigzag order, the inverse DCT, upsampling and colour: shared with mm_jpeg_decode.hip
+#include "mm_jpeg_idct.h"                                    // JpegMcu and the decoder's back half: shared with mm_jpeg_decode.hip
 #include "mm_quant.h"                                         // unquant: the v / 255 of as_float, shared with the exports
 #include "mm_stream.h"                                        // array_scan, Carve: what the encoders share
 
@@ -71,8 +71,6 @@ enum { MM_JPG_DIV = 0, MM_JPG_HUFF = 128, MM_JPG_HEADER = 128 + 1024 };
 // Decoding (the round trip below): the sample planes are Y 8 LV my x 8 LH mx and Cb, Cr 8 my x 8 mx per frame.  4:4:4 is not upsampled;
 // 4:2:2 has real chroma on H x wd, wd = ceil(W / 2): wd > 2, h2v1 fancy, out[2x] = (3 s[x] + s[x-1] + 1) >> 2, out[2x+1] =
 // (3 s[x] + s[x+1] + 2) >> 2, s[-1] := s[0], s[wd] := s[wd-1]; wd <= 2, replication; no vertical neighbour.
-// the same for the host's arithmetic
-struct JpegMcuShape { int blocks, w, h; };
 template <int N = 4, class F>
 __host__ inline void jpeg_by_layout(int layout, F f) {       // f(std::integral_constant<int, layout>): the host's dispatch on the template parameter
     switch (layout) {
@@ -81,11 +79,6 @@ __host__ inline void jpeg_by_layout(int layout, F f) {       // f(std::integral_
         case MM_JPG_444: f(std::integral_constant<int, MM_JPG_444>()); break;
         default: if constexpr (N > MM_JPG_GREY) f(std::integral_constant<int, MM_JPG_GREY>()); break;
     }
-}
-__host__ JpegMcuShape jpeg_mcu_shape(int layout) {
-    JpegMcuShape m = {};
-    jpeg_by_layout(layout, [&](auto L) { using M = JpegMcu<decltype(L)::value>; m = {M::BLOCKS, M::W, M::H}; });
-    return m;
 }
 // mode and sampling as the descriptors carry them -> the layout, or -1 for what is refused (an unknown value; a sampling with mode L)
 int jpeg_layout_of(int mode, int sampling) {
@@ -457,6 +450,7 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_write_kernel(JpegArgs a) {
 //               clamp and crop.  A block stays in registers and LDS from load to store: no greyscale file is ever formed.
 // The colour path reads the int16 zigzag blocks jpeg_transform_kernel wrote, from memory -- its own pass's, or those in mm_jpeg_encode's
 // workspace -- so the decoded frames cannot drift from the files.  Dummy luma blocks lie wholly outside the image and are never read.
+// The arithmetic is mm_jpeg_idct.h's, shared with the file decoder; the kernels here find a lane's block or pixel, pick the divisors, skip the dummies.
 //   idct      eight lanes per block: the block comes from memory into LDS, lane c dequantises column c and runs the column pass, the block
 //             is transposed through LDS, lane r runs the row pass and stores row r as 8 bytes into the padded sample planes in the workspace
 //             (Y 16my x 16mx, Cb and Cr 8my x 8mx per frame: 1.5 bytes per pixel).
@@ -474,6 +468,13 @@ struct JpegDecArgs {
     long long total_blocks, total_pixels;
 };
 
+template <int L>
+__device__ inline JpegPlanes jpeg_frame_planes(const JpegDecArgs& a, int img) {      // the sample planes of frame img
+    const JpegMcuShape m = jpeg_mcu_shape(L);
+    const int mcus = a.my * a.mx;                             // (a frame's blocks are at most MM_JPEG_MAX_BLOCKS: its planes' bytes fit 32 bits)
+    return {a.yp + (size_t)img * (unsigned)JpegPlanes::luma_bytes(m, mcus), a.cp + (size_t)img * (unsigned)JpegPlanes::chroma_bytes(m, mcus), a.mx, a.my};
+}
+
 // ---- idct: coefficients -> the sample planes ----------------------------------------------------------------------------------------
 template <int L>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_idct_kernel(JpegDecArgs a) {
@@ -486,61 +487,32 @@ __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_idct_kernel(JpegDecArgs a) 
     const int img = (int)(gc / a.blocks), rem = (int)(gc % a.blocks);
     const int mcu = rem / M::BLOCKS, j = rem % M::BLOCKS, my = mcu / a.mx, mx = mcu % a.mx;
     const int by = M::LV * my + (j >> M::LH_SHIFT), bx = M::LH * mx + (j & (M::LH - 1));    // (luma)
-    const bool skip = g >= a.total_blocks || (j < M::LUMA && (by >= a.bh || bx >= a.bw));   // a dummy holds no pixel: never read
-    if (!skip) *(uint4*)&zz[lb][r * 8] = *(const uint4*)(a.coef + (size_t)g * 64 + r * 8);
-    __syncthreads();
-    const int* div = a.par + MM_JPG_DIV + (j < M::LUMA ? 0 : 64);
-    int d[8], o[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int nat = k * 8 + r;
-        d[k] = skip ? 0 : (int)zz[lb][jpeg_zigzag_pos[nat]] * (div[nat] >> 3);
-    }
-    jpeg_idct8<11>(d, o);
-    const uint2 row = jpeg_idct_rows(tile, lb, r, o);
-    if (skip) return;
-    if (j < M::LUMA) {
-        const size_t yw = (size_t)a.mx * M::W;
-        *(uint2*)(a.yp + ((size_t)img * a.my * M::H + by * 8 + r) * yw + bx * 8) = row;
-    } else {
-        const size_t cw = (size_t)a.mx * 8;
-        *(uint2*)(a.cp + (((size_t)img * 2 + (j - M::LUMA)) * a.my * 8 + my * 8 + r) * cw + mx * 8) = row;
-    }
+    const bool live = g < a.total_blocks && !(j < M::LUMA && (by >= a.bh || bx >= a.bw));   // a dummy holds no pixel: never read
+    const JpegPlanes pl = jpeg_frame_planes<L>(a, img);
+    const uint2 row = jpeg_block_rows<3>(tile, zz, lb, r, live, a.coef + (size_t)g * 64, [&] { return a.par + MM_JPG_DIV + (j < M::LUMA ? 0 : 64); });
+    if (!live) return;
+    if (j < M::LUMA) *(uint2*)pl.luma(M::W, by * 8 + r, bx * 8) = row;
+    else *(uint2*)pl.chroma(j - M::LUMA, my * 8 + r, mx * 8) = row;
 }
 
 // ---- pixels: upsample, convert, store -----------------------------------------------------------------------------------------------
-// the upsampled chroma sample at (y, x) of one component's plane c (cw bytes a row)
-template <int L>
-__device__ inline int jpeg_chroma_up(const JpegDecArgs& a, const unsigned char* c, size_t cw, int y, int x) {
-    return jpeg_chroma_up_at<L>(c, cw, y, x, a.hd, a.wd);
-}
 // pixel p of the output, over all frames: R | G << 8 | B << 16
 template <int L>
 __device__ inline unsigned jpeg_pixel(const JpegDecArgs& a, long long p, int& img, int& y, int& x) {
-    using M = JpegMcu<L>;
     const int hw = a.H * a.W;
     img = (int)(p / hw);
     const int rem = (int)(p % hw);
     y = rem / a.W; x = rem % a.W;
-    const size_t cw = (size_t)a.mx * 8, cplane = (size_t)a.my * 8 * cw;
-    const int Y = a.yp[((size_t)img * a.my * M::H + y) * (cw * M::LH) + x];
-    const unsigned char* c = a.cp + (size_t)img * 2 * cplane;
-    const int cb = jpeg_chroma_up<L>(a, c, cw, y, x) - 128, cr = jpeg_chroma_up<L>(a, c + cplane, cw, y, x) - 128;
-    return jpeg_ycc_rgb(Y, cb, cr);
+    return jpeg_pixel_at<L>(jpeg_frame_planes<L>(a, img), a.hd, a.wd, y, x);
 }
 
 template <int L>
 __global__ __launch_bounds__(MM_JPG_BLOCK) void jpeg_pixels_u8_kernel(JpegDecArgs a) {
     const long long i = (long long)blockIdx.x * MM_JPG_BLOCK + threadIdx.x, byte0 = 4 * i, bytes = 3 * a.total_pixels;
     if (byte0 >= bytes) return;
-    const long long p = byte0 / 3;
     int img, y, x;
-    unsigned long long seq = jpeg_pixel<L>(a, p, img, y, x);   // the six bytes of pixels p and p + 1
-    if (p + 1 < a.total_pixels) seq |= (unsigned long long)jpeg_pixel<L>(a, p + 1, img, y, x) << 24;
-    const unsigned w = (unsigned)(seq >> (8 * (int)(byte0 - 3 * p)));
-    unsigned char* out = (unsigned char*)a.out + byte0;
-    if (byte0 + 4 <= bytes) *(unsigned*)out = w;
-    else for (int k = 0; k < (int)(bytes - byte0); ++k) out[k] = (unsigned char)(w >> (8 * k));
+    const unsigned w = jpeg_rgb_bytes(byte0, bytes, [&](long long p) { return jpeg_pixel<L>(a, p, img, y, x); });      // (bytes is uniform: pixel p + 1 wherever there is one)
+    jpeg_store_bytes((unsigned char*)a.out, byte0, min(byte0 + 4, bytes), w);
 }
 
 template <int L>
@@ -606,8 +578,8 @@ __host__ JpegRoundtripLayout jpeg_roundtrip_layout(const MMJpegRoundtripDesc* d)
     const size_t n = (size_t)d->n, mcus = (size_t)((d->H + m.h - 1) / m.h) * ((d->W + m.w - 1) / m.w);
     Carve c;
     l.coef = c.take(d->coef ? 0 : n * mcus * m.blocks * 128);
-    l.yp = c.take(n * mcus * m.w * m.h);
-    l.cp = c.take(n * mcus * 128);
+    l.yp = c.take(n * JpegPlanes::luma_bytes(m, mcus));
+    l.cp = c.take(n * JpegPlanes::chroma_bytes(m, mcus));
     l.bytes = c.at;
     return l;
 }

@@ -1,8 +1,8 @@
 // mm_jpeg_decode.hip -- baseline JPEG FILES to 8-bit device frames, for gfx950: what the reference's datasets and evaluation do on the host
 // per file with Image.open(f).convert('RGB') (datasets/market.py, atr.py, bird.py; test.py:430-463, trainer.py:771-836, fid_score.py:71-76).
-// The front half of a decoder; the back half is the round trip's arithmetic (mm_jpeg_idct.h), pinned to Pillow to the byte.  The caller
-// parses the markers (jpeg_decode.py); the tables it hands over are described at MMJpegDecodeDesc in include/mm_render.h, and every record
-// is re-checked here, on the host, before anything is launched (check_jpeg_decode).
+// The front half of a decoder; the back half (block -> row bytes, planes -> pixel, pixels -> output dword) is mm_jpeg_idct.h, shared with the
+// round trip and pinned to Pillow to the byte.  The caller parses the markers (jpeg_decode.py); the tables it hands over are described at
+// MMJpegDecodeDesc in include/mm_render.h, and every record is re-checked here, on the host, before anything is launched (check_jpeg_decode).
 //
 // One memset (coefficients and status, adjacent in the workspace) and three launches, whatever the number of files:
 //   entropy   one lane per SEGMENT -- a file, or one restart interval of it.  A workgroup is one wave; MM_JPEG_DEC_GROUP of its lanes take a
@@ -50,26 +50,16 @@ __host__ JpegDecodeTables jpeg_decode_tables(const MMJpegDecodeDesc* d) {
     return t;
 }
 
-struct JpegDecodeShape { int per, luma, mw, mh; };            // blocks per MCU, luma blocks of them, the MCU in pixels
-__host__ __device__ inline JpegDecodeShape jpeg_decode_shape(int layout) {
-    switch (layout) {
-        case MM_JPG_420: return {6, 4, 16, 16};
-        case MM_JPG_422: return {4, 2, 16, 8};
-        case MM_JPG_444: return {3, 1, 8, 8};
-        default: return {1, 1, 8, 8};
-    }
-}
-
 // totals of a call whose records passed check_jpeg_decode
 struct JpegDecodeTotals { long long blocks, plane_bytes, pixels; };
 __host__ JpegDecodeTotals jpeg_decode_totals(const MMJpegDecodeDesc* d) {
     const JpegDecodeTables t = jpeg_decode_tables(d);
     const int32_t* f = d->tables_host + t.files + (size_t)(d->n - 1) * MM_JPEG_DEC_FILE_INTS;
-    const JpegDecodeShape s = jpeg_decode_shape(f[JD_LAYOUT]);
+    const JpegMcuShape s = jpeg_mcu_shape(f[JD_LAYOUT]);
     const long long mcus = (long long)f[JD_MX] * f[JD_MY];
     JpegDecodeTotals r;
-    r.blocks = f[JD_BLOCK0] + mcus * s.per;
-    r.plane_bytes = f[JD_LAYOUT] == MM_JPG_GREY ? f[JD_YOFF] + mcus * 64 : f[JD_COFF] + mcus * 128;
+    r.blocks = f[JD_BLOCK0] + mcus * s.blocks;
+    r.plane_bytes = f[JD_YOFF] + JpegPlanes::luma_bytes(s, mcus) + JpegPlanes::chroma_bytes(s, mcus);
     long long last;
     std::memcpy(&last, d->tables_host + t.offsets + 2 * (size_t)d->n, 8);
     r.pixels = last;
@@ -105,19 +95,15 @@ int check_jpeg_decode(const MMJpegDecodeDesc* d) {
         const int H = f[JD_H], W = f[JD_W], layout = f[JD_LAYOUT];
         if (H < 1 || W < 1 || H > 65535 || W > 65535 || layout < MM_JPG_420 || layout > MM_JPG_GREY) return MM_ERR_BAD_SHAPE;
         if (d->mode == MM_JPEG_MODE_L && layout != MM_JPG_GREY) return MM_ERR_BAD_SHAPE;
-        const JpegDecodeShape s = jpeg_decode_shape(layout);
-        if (f[JD_MX] != (W + s.mw - 1) / s.mw || f[JD_MY] != (H + s.mh - 1) / s.mh) return MM_ERR_BAD_SHAPE;
+        const JpegMcuShape s = jpeg_mcu_shape(layout);
+        if (f[JD_MX] != (W + s.w - 1) / s.w || f[JD_MY] != (H + s.h - 1) / s.h) return MM_ERR_BAD_SHAPE;
         const long long mcus = (long long)f[JD_MX] * f[JD_MY];
-        if (mcus * s.per > MM_JPEG_MAX_BLOCKS) return MM_ERR_UNSUPPORTED;
+        if (mcus * s.blocks > MM_JPEG_MAX_BLOCKS) return MM_ERR_UNSUPPORTED;
         if (f[JD_BLOCK0] != block0 || f[JD_YOFF] != plane) return MM_ERR_BAD_SHAPE;
-        block0 += mcus * s.per;
-        plane += mcus * s.mw * s.mh;
-        if (layout != MM_JPG_GREY) {
-            if (f[JD_COFF] != plane) return MM_ERR_BAD_SHAPE;
-            plane += mcus * 128;
-        } else if (f[JD_COFF] != 0) {
-            return MM_ERR_BAD_SHAPE;
-        }
+        block0 += mcus * s.blocks;
+        plane += JpegPlanes::luma_bytes(s, mcus);
+        if (f[JD_COFF] != (layout != MM_JPG_GREY ? plane : 0)) return MM_ERR_BAD_SHAPE;
+        plane += JpegPlanes::chroma_bytes(s, mcus);
         if (block0 > MM_JPEG_DEC_MAX_BLOCKS) return MM_ERR_UNSUPPORTED;     // (so the planes, 64 bytes a block, stay below 2^31 too)
         for (int c = 0; c < 3; ++c) if (f[JD_Q0 + c] < 0 || f[JD_Q0 + c] >= d->n_qtables) return MM_ERR_BAD_SHAPE;
         long long at, next;
@@ -150,6 +136,9 @@ struct JpegDecodeArgs {
     int n, channels;
     long long total_blocks, total_bytes;
 };
+__device__ inline JpegPlanes jpeg_decode_planes(const JpegDecodeArgs& a, const int* f) {      // the sample planes of the file whose record is f
+    return {a.planes + (size_t)f[JD_YOFF], a.planes + (size_t)f[JD_COFF], f[JD_MX], f[JD_MY]};
+}
 
 // ---- entropy: segments -> coefficients ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MM_JPGD_WAVE) void jpeg_decode_entropy_kernel(JpegDecodeArgs a) {
@@ -168,9 +157,9 @@ __global__ __launch_bounds__(MM_JPGD_WAVE) void jpeg_decode_entropy_kernel(JpegD
     const int count = s[JS_COUNT];
     if (count == 0) return;                                   // a filler
     const int* f = a.files + (size_t)s[JS_FILE] * MM_JPEG_DEC_FILE_INTS;
-    const JpegDecodeShape m = jpeg_decode_shape(f[JD_LAYOUT]);
-    short* coef = a.coef + ((size_t)f[JD_BLOCK0] + (size_t)s[JS_FIRST] * m.per) * 64;
-    const int st = jpeg_decode_segment(a.bytes, s[JS_BEGIN], s[JS_END], tables, (unsigned)set[4], m.per, m.luma, count, coef);
+    const JpegMcuShape m = jpeg_mcu_shape(f[JD_LAYOUT]);
+    short* coef = a.coef + ((size_t)f[JD_BLOCK0] + (size_t)s[JS_FIRST] * m.blocks) * 64;
+    const int st = jpeg_decode_segment(a.bytes, s[JS_BEGIN], s[JS_END], tables, (unsigned)set[4], m.blocks, m.luma, count, coef);
     if (st) atomicOr(a.status + s[JS_FILE], st);
 }
 
@@ -188,55 +177,31 @@ __global__ __launch_bounds__(MM_JPGD_BLOCK) void jpeg_decode_idct_kernel(JpegDec
         if (a.files[(size_t)mid * MM_JPEG_DEC_FILE_INTS + JD_BLOCK0] <= gc) lo = mid; else hi = mid - 1;
     }
     const int* f = a.files + (size_t)lo * MM_JPEG_DEC_FILE_INTS;
-    const int layout = f[JD_LAYOUT], mxs = f[JD_MX], mys = f[JD_MY];
-    const JpegDecodeShape m = jpeg_decode_shape(layout);
-    const int rem = gc - f[JD_BLOCK0], mcu = rem / m.per, j = rem % m.per, my = mcu / mxs, mx = mcu % mxs;
-    if (live) *(uint4*)&zz[lb][r * 8] = *(const uint4*)(a.coef + (size_t)g * 64 + r * 8);
-    __syncthreads();
-    const int* q = a.qtables + (size_t)f[JD_Q0 + (j < m.luma ? 0 : j - m.luma + 1)] * 64;
-    int d[8], o[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int nat = k * 8 + r;
-        d[k] = live ? (int)zz[lb][jpeg_zigzag_pos[nat]] * q[nat] : 0;
-    }
-    jpeg_idct8<11>(d, o);
-    const uint2 row = jpeg_idct_rows(tile, lb, r, o);
+    const JpegPlanes pl = jpeg_decode_planes(a, f);
+    const JpegMcuShape m = jpeg_mcu_shape(f[JD_LAYOUT]);
+    const int rem = gc - f[JD_BLOCK0], mcu = rem / m.blocks, j = rem % m.blocks, my = mcu / pl.mxs, mx = mcu % pl.mxs;
+    const uint2 row = jpeg_block_rows<0>(tile, zz, lb, r, live, a.coef + (size_t)g * 64,       // the file's own table of the block's component
+                                         [&] { return a.qtables + (size_t)f[JD_Q0 + (j < m.luma ? 0 : j - m.luma + 1)] * 64; });
     if (!live) return;
-    if (j < m.luma) {
-        const int lh = m.mw >> 3;                             // luma blocks across an MCU
-        const int by = (m.mh >> 3) * my + j / lh, bx = lh * mx + j % lh;
-        *(uint2*)(a.planes + (size_t)f[JD_YOFF] + ((size_t)by * 8 + r) * ((size_t)mxs * m.mw) + bx * 8) = row;
-    } else {
-        const size_t cw = (size_t)mxs * 8;
-        *(uint2*)(a.planes + (size_t)f[JD_COFF] + ((size_t)(j - m.luma) * mys * 8 + my * 8 + r) * cw + mx * 8) = row;
-    }
+    const int lh = m.w >> 3;                                  // luma blocks across an MCU
+    if (j < m.luma) *(uint2*)pl.luma(m.w, ((m.h >> 3) * my + j / lh) * 8 + r, (lh * mx + j % lh) * 8) = row;
+    else *(uint2*)pl.chroma(j - m.luma, my * 8 + r, mx * 8) = row;
 }
 
 // ---- pixels: upsample, convert, store -----------------------------------------------------------------------------------------------
-template <int L>
-__device__ inline unsigned jpeg_decode_colour(const unsigned char* yp, const unsigned char* cp, int mxs, int mys, int H, int W, int y, int x) {
-    using M = JpegMcu<L>;
-    const size_t cw = (size_t)mxs * 8, cplane = (size_t)mys * 8 * cw;
-    const int Y = yp[(size_t)y * (cw * M::LH) + x];
-    const int hd = (H + 1) / 2, wd = (W + 1) / 2;
-    const int cb = jpeg_chroma_up_at<L>(cp, cw, y, x, hd, wd) - 128, cr = jpeg_chroma_up_at<L>(cp + cplane, cw, y, x, hd, wd) - 128;
-    return jpeg_ycc_rgb(Y, cb, cr);
-}
 // pixel p of the output (its file is `file` or a later one; `file` is moved on to it): R | G << 8 | B << 16, or the sample for one channel
 __device__ inline unsigned jpeg_decode_pixel(const JpegDecodeArgs& a, long long p, int& file) {
     while (file + 1 < a.n && a.offsets[file + 1] <= p) ++file;                  // (a file has a pixel at least: at most a step per pixel of a dword)
     const int* f = a.files + (size_t)file * MM_JPEG_DEC_FILE_INTS;
-    const int H = f[JD_H], W = f[JD_W], layout = f[JD_LAYOUT], mxs = f[JD_MX], mys = f[JD_MY];
+    const int H = f[JD_H], W = f[JD_W], hd = (H + 1) / 2, wd = (W + 1) / 2;
     const int rem = (int)(p - a.offsets[file]), y = rem / W, x = rem % W;
-    const unsigned char* yp = a.planes + (size_t)f[JD_YOFF];
-    const unsigned char* cp = a.planes + (size_t)f[JD_COFF];
-    switch (layout) {
-        case MM_JPG_420: return jpeg_decode_colour<MM_JPG_420>(yp, cp, mxs, mys, H, W, y, x);
-        case MM_JPG_422: return jpeg_decode_colour<MM_JPG_422>(yp, cp, mxs, mys, H, W, y, x);
-        case MM_JPG_444: return jpeg_decode_colour<MM_JPG_444>(yp, cp, mxs, mys, H, W, y, x);
+    const JpegPlanes pl = jpeg_decode_planes(a, f);
+    switch (f[JD_LAYOUT]) {
+        case MM_JPG_420: return jpeg_pixel_at<MM_JPG_420>(pl, hd, wd, y, x);
+        case MM_JPG_422: return jpeg_pixel_at<MM_JPG_422>(pl, hd, wd, y, x);
+        case MM_JPG_444: return jpeg_pixel_at<MM_JPG_444>(pl, hd, wd, y, x);
         default: {
-            const unsigned v = yp[(size_t)y * ((size_t)mxs * 8) + x];
+            const unsigned v = *pl.luma(JpegMcu<MM_JPG_GREY>::W, y, x);
             return a.channels == 3 ? v * 0x010101u : v;
         }
     }
@@ -247,23 +212,16 @@ __global__ __launch_bounds__(MM_JPGD_BLOCK) void jpeg_decode_pixels_kernel(JpegD
     const long long i = (long long)blockIdx.x * MM_JPGD_BLOCK + threadIdx.x;
     const long long b0 = 4 * i - lead, first = max(b0, 0LL), last = min(b0 + 4, a.total_bytes);      // this lane's bytes [first, last)
     if (first >= last) return;
-    long long p = first / a.channels;
+    const long long p = first / a.channels;
     int lo = 0, hi = a.n - 1;                                 // the file of pixel p: the last whose offset is <= p
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (a.offsets[mid] <= p) lo = mid; else hi = mid - 1;
     }
     unsigned w = 0;
-    if (a.channels == 3) {
-        unsigned long long seq = jpeg_decode_pixel(a, p, lo);                   // the six bytes of pixels p and p + 1
-        if (3 * (p + 1) < last) seq |= (unsigned long long)jpeg_decode_pixel(a, p + 1, lo) << 24;
-        w = (unsigned)(seq >> (8 * (int)(first - 3 * p)));                      // byte `first` at bits 0..7
-    } else {
-        for (long long b = first; b < last; ++b) w |= jpeg_decode_pixel(a, b, lo) << (8 * (int)(b - first));
-    }
-    unsigned char* out = a.out + first;
-    if (last - first == 4) *(unsigned*)out = w;               // (first = b0 here, and out + b0 is a multiple of 4)
-    else for (int k = 0; k < (int)(last - first); ++k) out[k] = (unsigned char)(w >> (8 * k));
+    if (a.channels == 3) w = jpeg_rgb_bytes(first, last, [&](long long q) { return jpeg_decode_pixel(a, q, lo); });
+    else for (long long b = first; b < last; ++b) w |= jpeg_decode_pixel(a, b, lo) << (8 * (int)(b - first));
+    jpeg_store_bytes(a.out, first, last, w);                  // (a whole dword: first = b0, and out + b0 is a multiple of 4)
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
-// mm_jpeg_idct.h -- the back half of libjpeg's baseline decoder, shared by the round trip (mm_jpeg.hip) and the file decoder
-// (mm_jpeg_decode.hip): what an MCU is, the zigzag order, jidctint's islow pass, the clamp to bytes, the transpose between the passes,
-// "fancy" chroma upsampling and the fixed-point YCbCr -> RGB.  Integer arithmetic only (>> is arithmetic); the order of every statement is
-// pinned to Pillow to the byte by tests/test_gpu_jpeg_roundtrip.py and tests/test_gpu_jpeg_modes.py -- see the round trip's header in
-// mm_jpeg.hip for the formulas.
+// mm_jpeg_idct.h -- the back half of libjpeg's baseline decoder, stated once for the round trip (mm_jpeg.hip) and the file decoder
+// (mm_jpeg_decode.hip): what an MCU is, where one image's sample planes lie, the zigzag order, a block to its row bytes (dequantise, jidctint's
+// islow passes, the clamp), a pixel from the planes ("fancy" chroma upsampling, fixed-point YCbCr -> RGB), an output dword from its pixels.
+// Their kernels keep what differs: how a lane finds its block, image and quantiser, and where the planes are.  Integer arithmetic only (>> is
+// arithmetic); the order of every statement is pinned to Pillow to the byte by tests/test_gpu_jpeg_roundtrip.py, tests/test_gpu_jpeg_modes.py
+// and tests/test_gpu_jpeg_decode.py -- see the round trip's header in mm_jpeg.hip for the formulas.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,31 @@ struct JpegMcu {
     static constexpr int LUMA = LH * LV, BLOCKS = L == MM_JPG_GREY ? 1 : LUMA + 2;
     static constexpr int W = 8 * LH, H = 8 * LV;              // the MCU in pixels
     static constexpr int CHANNELS = L == MM_JPG_GREY ? 1 : 3; // bytes a pixel of the input
+};
+// the same at run time: blocks per MCU, luma blocks of them, the MCU in pixels
+struct JpegMcuShape { int blocks, luma, w, h; };
+template <int L>
+__host__ __device__ constexpr JpegMcuShape jpeg_mcu_shape_of() { return {JpegMcu<L>::BLOCKS, JpegMcu<L>::LUMA, JpegMcu<L>::W, JpegMcu<L>::H}; }
+__host__ __device__ inline JpegMcuShape jpeg_mcu_shape(int layout) {
+    switch (layout) {
+        case MM_JPG_420: return jpeg_mcu_shape_of<MM_JPG_420>();
+        case MM_JPG_422: return jpeg_mcu_shape_of<MM_JPG_422>();
+        case MM_JPG_444: return jpeg_mcu_shape_of<MM_JPG_444>();
+        default: return jpeg_mcu_shape_of<MM_JPG_GREY>();
+    }
+}
+
+// The padded sample planes of ONE image of mys x mxs MCUs: Y, 8 LV mys rows of 8 LH mxs bytes, at y; Cb then Cr, 8 mys rows of 8 mxs bytes each,
+// at c (a greyscale image has none).  The IDCT kernels store through it, the pixel passes read through it.  An image has at most
+// MM_JPEG_MAX_BLOCKS = 2^20 blocks (both callers' descriptors are refused beyond), so an offset inside its planes fits 32 bits.
+struct JpegPlanes {
+    unsigned char* y; unsigned char* c;
+    int mxs, mys;
+    __host__ __device__ static long long luma_bytes(const JpegMcuShape& m, long long mcus) { return mcus * m.w * m.h; }
+    __host__ __device__ static long long chroma_bytes(const JpegMcuShape& m, long long mcus) { return m.blocks > m.luma ? mcus * 128 : 0; }
+    // byte x of luma row `row`, in planes of MCUs mw pixels wide; of row `row` of chroma component comp (0: Cb, 1: Cr)
+    __device__ unsigned char* luma(int mw, int row, int x) const { return y + ((unsigned)row * (unsigned)(mxs * mw) + x); }
+    __device__ unsigned char* chroma(int comp, int row, int x) const { return c + ((unsigned)(comp * mys * 8 + row) * (unsigned)(mxs * 8) + x); }
 };
 
 // natural index -> position in zigzag order
@@ -67,6 +93,24 @@ __device__ inline uint2 jpeg_idct_rows(int (*tile)[65], int lb, int r, int (&o)[
     return jpeg_row_bytes(o);
 }
 
+// A block to its row bytes: the eight lanes of block lb bring the 64 int16 zigzag coefficients at coef into zz, lane r dequantises column r
+// by table()[nat] >> SHIFT (the table in natural order; the round trip's holds 8 q) and runs the column pass, then jpeg_idct_rows.  Every
+// lane of the workgroup calls it; a lane that is not live reads nothing and transforms zeros.
+template <int SHIFT, class T>
+__device__ inline uint2 jpeg_block_rows(int (*tile)[65], short (*zz)[64], int lb, int r, bool live, const short* coef, T table) {
+    if (live) *(uint4*)&zz[lb][r * 8] = *(const uint4*)(coef + r * 8);
+    __syncthreads();
+    const int* q = table();
+    int d[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int nat = k * 8 + r;
+        d[k] = live ? (int)zz[lb][jpeg_zigzag_pos[nat]] * (q[nat] >> SHIFT) : 0;
+    }
+    jpeg_idct8<11>(d, o);
+    return jpeg_idct_rows(tile, lb, r, o);
+}
+
 // the upsampled chroma sample at (y, x) of one component's plane c (cw bytes a row), real on hd rows by wd columns
 template <int L>
 __device__ inline int jpeg_chroma_up_at(const unsigned char* c, size_t cw, int y, int x, int hd, int wd) {
@@ -93,6 +137,31 @@ __device__ inline unsigned jpeg_ycc_rgb(int Y, int cb, int cr) {
     const int G = min(max(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0), 255);
     const int B = min(max(Y + ((116130 * cb + 32768) >> 16), 0), 255);
     return (unsigned)R | (unsigned)G << 8 | (unsigned)B << 16;
+}
+
+// the pixel at (y, x) of the image whose planes are pl, its chroma real on hd rows by wd columns: R | G << 8 | B << 16
+template <int L>
+__device__ inline unsigned jpeg_pixel_at(const JpegPlanes& pl, int hd, int wd, int y, int x) {
+    const size_t cw = (size_t)pl.mxs * 8;
+    const int Y = *pl.luma(JpegMcu<L>::W, y, x);
+    const int cb = jpeg_chroma_up_at<L>(pl.chroma(0, 0, 0), cw, y, x, hd, wd) - 128, cr = jpeg_chroma_up_at<L>(pl.chroma(1, 0, 0), cw, y, x, hd, wd) - 128;
+    return jpeg_ycc_rgb(Y, cb, cr);
+}
+
+// bytes [first, last) of a dense output, at most the four of one aligned dword, out of w (byte `first` at bits 0..7): one 4-byte store, or
+// the byte tail at the output's two ends
+__device__ inline void jpeg_store_bytes(unsigned char* out, long long first, long long last, unsigned w) {
+    out += first;
+    if (last - first == 4) *(unsigned*)out = w;
+    else for (int k = 0; k < (int)(last - first); ++k) out[k] = (unsigned char)(w >> (8 * k));
+}
+// that w for bytes [first, last) of an RGB output, pixel(p) giving its pixel p as R | G << 8 | B << 16: the six bytes of pixels p and p + 1, shifted to `first`
+template <class P>
+__device__ inline unsigned jpeg_rgb_bytes(long long first, long long last, P pixel) {
+    const long long p = first / 3;
+    unsigned long long seq = pixel(p);
+    if (3 * (p + 1) < last) seq |= (unsigned long long)pixel(p + 1) << 24;
+    return (unsigned)(seq >> (8 * (int)(first - 3 * p)));
 }
 
 }  // namespace mm

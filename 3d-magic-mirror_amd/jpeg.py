@@ -88,8 +88,16 @@ def _segment(marker, body):
 
 
 SUBSAMPLINGS = ("4:4:4", "4:2:2", "4:2:0")        # Pillow's ints 0, 1, 2 in this order
-# what an MCU is, per layout: (blocks, luma blocks across, luma blocks down, Y's sampling byte in SOF0); JpegMcu in csrc/mm_jpeg.hip
+# what an MCU is, per layout: (blocks, luma blocks across and down, of 8 x 8 pixels, Y's sampling byte in SOF0); JpegMcu in csrc/mm_jpeg_idct.h
 MCU = {"4:2:0": (6, 2, 2, 0x22), "4:2:2": (4, 2, 1, 0x21), "4:4:4": (3, 1, 1, 0x11), "L": (1, 1, 1, 0x11)}
+MODES = {"RGB": N.JPEG_MODE_RGB, "L": N.JPEG_MODE_L}
+SAMPLINGS = {"4:2:0": N.JPEG_SAMPLING_420, "4:2:2": N.JPEG_SAMPLING_422, "4:4:4": N.JPEG_SAMPLING_444, "L": 0}      # by layout: MM_JPEG_SAMPLING_*
+
+
+def plane_bytes(layout, mcus):
+    """the bytes of the padded sample planes of one image of ``mcus`` MCUs, (Y, Cb and Cr together): JpegPlanes in csrc/mm_jpeg_idct.h"""
+    per, lh, lv, _ = MCU[layout]
+    return mcus * 64 * lh * lv, mcus * 64 * (per - lh * lv)
 
 
 def check_layout(mode, subsampling="4:2:0"):
@@ -166,7 +174,7 @@ def _lower(H, W, quality, layout):
             return 256
         if layout == "L":
             raise ValueError("a greyscale layout has no colour round trip")
-        return (up(n * blocks * 128) if own_coef else 0) + up(n * my * mx * 64 * lv * lh) + up(n * my * mx * 128)
+        return (up(n * blocks * 128) if own_coef else 0) + sum(up(n * b) for b in plane_bytes(layout, my * mx))
 
     low["roundtrip_workspace_bytes"] = roundtrip_workspace_bytes
     low["workspace_bytes"] = lambda n: (up((n + 1) * 8) + up(n * low["file_capacity"]) + up(n * blocks * 128) + up(n * blocks * 4) + up(n * 4)
@@ -287,10 +295,6 @@ def _collect(ws, n, low, lead):
     """the files out of ``mm_jpeg_modes_encode``'s workspace: a ``JpegBatch`` after two blocking copies, the n + 1 offsets and the bytes used"""
     off, buf = N.read_back(ws, n + 1, low["files_offset"](n))
     return JpegBatch(buf, off, lead)
-
-
-MODES = {"RGB": N.JPEG_MODE_RGB, "L": N.JPEG_MODE_L}
-SAMPLINGS = {"4:2:0": N.JPEG_SAMPLING_420, "4:2:2": N.JPEG_SAMPLING_422, "4:4:4": N.JPEG_SAMPLING_444, "L": 0}      # by layout: MM_JPEG_SAMPLING_*
 
 
 def check_roundtrip(frames, quality, mode, files, subsampling="4:2:0"):

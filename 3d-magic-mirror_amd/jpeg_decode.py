@@ -31,17 +31,16 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .jpeg import MAX_BLOCKS, ZIGZAG, JpegBatch
+from .jpeg import MAX_BLOCKS, MCU, MODES, ZIGZAG, JpegBatch, plane_bytes
 
 ST_OVERRUN, ST_BAD_CODE, ST_BAD_RUN, ST_BAD_SIZE = 1, 2, 4, 8      # MM_JPEG_ST_* (csrc/mm_jpeg_entropy.h)
 STATUS_NAMES = ((ST_OVERRUN, "OVERRUN"), (ST_BAD_CODE, "BAD_CODE"), (ST_BAD_RUN, "BAD_RUN"), (ST_BAD_SIZE, "BAD_SIZE"))
 LAYOUTS = ("4:2:0", "4:2:2", "4:4:4", "L")                          # a file record's layout word indexes this
-SHAPES = ((6, 4, 16, 16), (4, 2, 16, 8), (3, 1, 8, 8), (1, 1, 8, 8))      # per layout: blocks per MCU, luma blocks of them, MCU width, MCU height
+SHAPES = tuple((per, lh * lv, 8 * lh, 8 * lv) for per, lh, lv, _ in (MCU[k] for k in LAYOUTS))      # per layout: blocks per MCU, luma blocks of them, MCU width, MCU height
 FILE_INTS, SEGMENT_INTS, SET_INTS, TABLE_WORDS = N.JPEG_DEC_FILE_INTS, N.JPEG_DEC_SEGMENT_INTS, N.JPEG_DEC_SET_INTS, N.JPEG_TABLE_WORDS
 (F_H, F_W, F_LAYOUT, F_MX, F_MY, F_BLOCK0, F_YOFF, F_COFF, F_Q0) = range(9)
 (S_FILE, S_FIRST, S_COUNT, S_BEGIN, S_END, S_SET) = range(6)
 GROUP = N.JPEG_DEC_GROUP                                            # segments of one workgroup: they share a table set
-MODES = {"RGB": N.JPEG_MODE_RGB, "L": N.JPEG_MODE_L}
 
 
 def _fail(i, why):
@@ -268,7 +267,6 @@ def lower_jpeg_decode(files, mode="RGB"):
         if head is None or b - a < len(head) or view[a:a + len(head)] != head:   # (a dataset repeats one header: the same bytes parse to the same dict)
             h = parse_header(view[a:b], i)
             head = bytes(view[a:a + h["scan"]])
-        per, _, mw, mh = SHAPES[h["layout"]]
         if mode == "L" and h["layout"] != 3:
             _fail(i, "a colour file with mode 'L' (mode 'L' decodes greyscale files only; Pillow's RGB -> L formula is not part of this)")
         mcus = h["mx"] * h["my"]
@@ -292,12 +290,9 @@ def lower_jpeg_decode(files, mode="RGB"):
         s = sindex.setdefault(key, len(sindex))
         segments.extend((s, i) + r for r in rows)
         q = [qindex.setdefault(t, len(qindex)) for t in h["qtables"]]
-        recs[i, :F_Q0 + 3] = (h["H"], h["W"], h["layout"], h["mx"], h["my"], block0, plane, 0, q[0], q[1], q[2])
-        block0 += mcus * per
-        plane += mcus * mw * mh
-        if h["layout"] != 3:
-            recs[i, F_COFF] = plane
-            plane += mcus * 128
+        luma, chroma = plane_bytes(LAYOUTS[h["layout"]], mcus)
+        recs[i, :F_Q0 + 3] = (h["H"], h["W"], h["layout"], h["mx"], h["my"], block0, plane, plane + luma if chroma else 0, q[0], q[1], q[2])
+        block0, plane = block0 + mcus * SHAPES[h["layout"]][0], plane + luma + chroma
         if block0 > N.JPEG_DEC_MAX_BLOCKS:
             raise ValueError("files 0..%d have %d blocks, more than %d in a call" % (i, block0, N.JPEG_DEC_MAX_BLOCKS))
     sizes = recs[:, :2].copy()
