@@ -490,13 +490,22 @@ def as_f32(t, dev):
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
-def upload_int32(values, device):
+def upload_int32(values, device, wait=False):
     """int32 ``values`` (a tensor, or an array that is cast) to ``device`` through pinned host memory, without waiting: (host, dev).  A
-    descriptor may name the pinned copy as its host table; it is read before the call returns."""
+    descriptor may name the pinned copy as its host table; it is read before the call returns.
+
+    The copy is queued on the device's current stream, so the device tensor is ordered only against work queued there after it: right for a
+    table that one call uploads and the same call's kernels read.  wait=True is for a table that is cached and shared: the host waits for
+    that copy (an event behind it, not the whole device), so the table is finished on return and a later call on any stream may read it."""
     src = values if torch.is_tensor(values) else torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32))
     host = torch.empty(src.shape, dtype=torch.int32, pin_memory=True)
     host.copy_(src)
-    return host, host.to(device, non_blocking=True)
+    dev = host.to(device, non_blocking=True)
+    if wait and dev.is_cuda:
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev.device))
+        done.synchronize()
+    return host, dev
 
 
 def ptr(t):

@@ -164,6 +164,9 @@ class DiffRender(object):
 
     # ---- device-resident static template data (the reference re-uploads faces/face_uvs on every call, :272-273) ----
     def _static(self, device):
+        """The template's faces, face uvs and vertex-corner table on ``device``, made once per device.  Resident: each upload is a blocking
+        copy from pageable memory that has finished when this returns, and the tensors are only read afterwards, so calls on any stream
+        may share them."""
         key = str(device)
         st = self._static_cache.get(key)
         if st is None:

@@ -43,7 +43,8 @@ def lpl_tables(lpl, device):
     """The column table (neighbor[u] = sum_k local[idx[k,u]] * val[k,u]) and the row table (the same for lpl^T, the backward's
     gather) of ``lpl`` on ``device``: (col_idx, col_val, row_idx, row_val).  Built once per (tensor, data_ptr, _version, shape,
     strides) -- an in-place edit, a ``.data`` reassignment or a new tensor is picked up -- with one device-to-host copy when
-    ``lpl`` lives on the device."""
+    ``lpl`` lives on the device.  Resident: the four uploads are blocking copies from pageable memory that have finished when this returns,
+    and the tables are only read afterwards, so calls on any stream may share them."""
     key = (lpl.data_ptr(), lpl._version, tuple(lpl.shape), tuple(lpl.stride()), lpl.dtype, str(lpl.device), str(device))
     hit = _LPL_CACHE.get(key)
     if hit is not None and hit[0]() is lpl:

@@ -31,7 +31,9 @@ FID_SUM_ROWS = N.FID_SUM_ROWS        # rows of one column-sum chunk (MM_FID_SUM_
 FID_TILE = 64                        # the Gram matrix's macro-tile (MM_FID_TILE): only tiles on or above the diagonal are computed
 FID_MAX_SIDE = N.FID_MAX_SIDE
 
-_TABLES = {}                         # (H, W, size, device) -> (Ho, Wo, pinned host rows, device rows)
+# (H, W, size, device) -> (Ho, Wo, pinned host rows, device rows).  Resident: the device rows' upload has finished when the call that
+# made the entry returns, nothing writes them afterwards, so calls on any stream may share them (one host wait per new key, none after).
+_TABLES = {}
 
 
 def _axis_rows(n_in, n_out):
@@ -103,8 +105,9 @@ def inception_input(frames, size=299, normalize=True, out=None):
     normalize  False skips ``2 x - 1``; with size=None that is the [0,1] batch a default-flag ``InceptionV3`` expects
     out        a float32 contiguous device tensor of the result's shape to write into
 
-    Any byte alignment; other strides go through ``.contiguous()``.  Float input is refused: ``export_images`` makes the bytes.  One launch,
-    nothing synchronises.  H and W in 1..1024."""
+    Any byte alignment; other strides go through ``.contiguous()``.  Float input is refused: ``export_images`` makes the bytes.  One launch on
+    the current stream; nothing synchronises, except that the first call of an (H, W, size, device) waits once for its table's upload
+    (``_TABLES``: finished on return, read-only afterwards, shared by calls on any stream).  H and W in 1..1024."""
     _check_frames(frames)
     H, W = frames.shape[-3], frames.shape[-2]
     _check_sizes(H, W, size)
@@ -116,7 +119,7 @@ def inception_input(frames, size=299, normalize=True, out=None):
         Ho, Wo, rows = lower_inception_input(H, W, size)
         if len(_TABLES) >= 64:
             _TABLES.clear()
-        tables = _TABLES[key] = (Ho, Wo) + N.upload_int32(rows, dev)
+        tables = _TABLES[key] = (Ho, Wo) + N.upload_int32(rows, dev, wait=True)      # resident: finished before any stream may share it
     Ho, Wo = tables[:2]
     frames = frames.detach().contiguous()
     n = 1 if frames.dim() == 3 else frames.shape[0]

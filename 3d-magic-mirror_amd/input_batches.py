@@ -86,7 +86,8 @@ class ImagePool:
         """The pool of JPEG ``files`` (a list of bytes / paths, or a ``JpegBatch``) decoded on ``device`` by ``decode_jpeg`` straight into
         the image region of the pool's one buffer: what ``ImagePool([np.asarray(Image.open(f).convert('RGB')) for f in files], segs, device)``
         holds, without the host decode and the 3 bytes a pixel of upload.  The masks and the two tables go up in one copy, the files' bytes in the
-        decoder's.  ValueError: what ``decode_jpeg`` rejects, masks that do not match the files' sizes, damaged files."""
+        decoder's, both from pinned memory on the current stream without waiting.  ValueError: what ``decode_jpeg`` rejects, masks that do not
+        match the files' sizes, damaged files -- the one host wait of the call, ``decode_jpeg``'s strict wait for the status."""
         from . import jpeg_decode as JD
         if device is None:
             raise ValueError("ImagePool.from_jpeg decodes on a device; on the host, ImagePool(decode_jpeg_host(files)[0], segs)")
@@ -111,7 +112,7 @@ class ImagePool:
         self.offsets_dev = self.buffer[tables:tables + 8 * (n + 1)].view(torch.int64)
         self.sizes_dev = self.buffer[tables + 8 * (n + 1):].view(torch.int32).view(n, 2)
         N.require_device(self.buffer)
-        self.buffer[3 * P:].copy_(torch.from_numpy(head))                   # the masks and the tables: one upload
+        self.buffer[3 * P:].copy_(torch.from_numpy(head).pin_memory(), non_blocking=True)      # the masks and the tables: one upload, not waited for
         JD.decode_jpeg(low, out=self.images)                                # the files: the decoder's one upload, then straight into the image region
         return self
 

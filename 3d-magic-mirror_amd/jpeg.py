@@ -240,8 +240,9 @@ def check_frames(frames, quality, layout="(...,H,W,3)"):
 
 @functools.lru_cache(maxsize=16)
 def _resident_params(device, H, W, quality, layout="4:2:0"):
-    """``lower_jpeg``'s table in the device's memory, kept between calls (a run repeats one size, quality and layout): uploaded once, by a
-    copy that has finished when this returns, and only read afterwards, so calls on any stream may share it"""
+    """``lower_jpeg``'s table in the device's memory, kept between calls (a run repeats one size, quality and layout).
+    Resident: uploaded once, by a blocking copy from pageable memory that has finished when this returns, and only read afterwards, so calls
+    on any stream may share it (tests/test_gpu_stream_order.py holds the copy to that)"""
     return _lower(H, W, quality, layout)["params"].to(device)
 
 

@@ -19,7 +19,9 @@ def _csr(keys, items, n):
 
 
 def build_tables(dr, device):
-    """Static tables of a template, on ``device`` (cached by the caller)."""
+    """Static tables of a template, on ``device`` (cached by the caller, ``DiffRender._reg_tables``).  Resident: every upload is a blocking
+    copy from pageable memory that has finished when this returns, and the tables are only read afterwards, so calls on any stream may
+    share them."""
     V, F = dr.num_vertices, dr.num_faces
     Lm = dr.vertices_laplacian_matrix.detach().cpu().to(torch.float32).numpy()
     t = {}

@@ -18,7 +18,8 @@ def camera_transform(distances, elevations, azimuths, biases):
     e, a = elevations * (math.pi / 180.0), azimuths * (math.pi / 180.0)
     cam = torch.stack([distances * torch.cos(e) * torch.sin(a), distances * torch.sin(e), distances * torch.cos(e) * torch.cos(a)], dim=-1)
     at = torch.cat([biases, torch.zeros_like(biases[:, :1])], dim=1)
-    up = torch.tensor([[0.0, 1.0, 0.0]], device=cam.device, dtype=cam.dtype).expand_as(cam)
+    up = torch.zeros_like(cam)                                   # +y, filled on the device: torch.tensor(..., device=) is a blocking upload
+    up[:, 1] = 1.0
     z = torch.nn.functional.normalize(cam - at, dim=1, eps=1e-5)
     x = torch.nn.functional.normalize(torch.cross(up, z, dim=1), dim=1, eps=1e-5)
     y = torch.cross(z, x, dim=1)

@@ -171,7 +171,8 @@ def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, wi
 
 
 def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, win=None, weights=None, K=(0.01, 0.03)):
-    """pytorch_msssim.ms_ssim (R9), composed from the SSIM op's per-channel ssim and cs and F.avg_pool2d."""
+    """pytorch_msssim.ms_ssim (R9), composed from the SSIM op's per-channel ssim and cs and F.avg_pool2d.  With device inputs nothing waits
+    on the host, forward or backward: the weights go up from pinned memory, and the product over the levels is ``_prod_rows``."""
     X, Y, taps, win_size = _prepare(X, Y, win_size, win_sigma, win)
     smaller_side = min(X.shape[-2:])
     assert smaller_side > (win_size - 1) * (2 ** 4), \
@@ -179,7 +180,11 @@ def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5,
     X, Y, out_dev = _on_device(X, Y)
     if weights is None:
         weights = MS_WEIGHTS
-    weights_tensor = X.new_tensor(weights)
+    weights_tensor = torch.as_tensor(weights, dtype=X.dtype).detach()
+    if weights_tensor.is_cuda:
+        weights_tensor = weights_tensor.to(X.device)
+    else:                                                # through pinned memory, without waiting: new_tensor's copy from pageable memory blocks
+        weights_tensor = weights_tensor.pin_memory().to(X.device, non_blocking=True)      # the host until the caller's stream has drained
     C1, C2 = _constants(data_range, K)
     levels = weights_tensor.shape[0]
     mcs = []
@@ -192,8 +197,23 @@ def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5,
             Y = F.avg_pool2d(Y, kernel_size=2, padding=padding)
     ssim_per_channel = torch.relu(ssim_per_channel)
     mcs_and_ssim = torch.stack(mcs + [ssim_per_channel], dim=0)
-    ms_ssim_val = torch.prod(mcs_and_ssim ** weights_tensor.view(-1, 1, 1), dim=0)
+    ms_ssim_val = _prod_rows(mcs_and_ssim ** weights_tensor.view(-1, 1, 1))
     return (ms_ssim_val.mean() if size_average else ms_ssim_val.mean(1)).to(out_dev)
+
+
+def _prod_rows(t):
+    """``torch.prod(t, dim=0)`` written out as multiplies, in the order its device kernel takes the rows in (four running products, row i into
+    product i % 4, then the four combined in ascending order).  That the bits equal ``torch.prod``'s is measured on this stack (tests/test_gpu_ssim.py), not
+    a contract: another torch build or another inner size may reduce in another order, and nothing here promises ``prod``'s bits.  Written out because ``prod``'s backward counts the zeros of
+    its input on the host -- a wait for the caller's stream in every MS-SSIM backward; the chain's backward is plain multiplies, and a zero
+    factor (a clamped level) needs no special case."""
+    acc = [t[i] for i in range(min(4, t.shape[0]))]
+    for i in range(4, t.shape[0]):
+        acc[i % 4] = acc[i % 4] * t[i]
+    out = acc[0]
+    for a in acc[1:]:
+        out = out * a
+    return out
 
 
 class SSIM(torch.nn.Module):

@@ -228,3 +228,16 @@ def test_matches_real_pytorch_msssim_fixture(S):
         assert np.abs(v.detach().cpu().numpy() - z[case + "_val"]).max() <= 1e-5, case
         v.sum().backward()
         grad_close(Xd.grad, z[case + "_gX"], what=case + " dX"), grad_close(Yd.grad, z[case + "_gY"], what=case + " dY")
+
+
+@pytest.mark.parametrize("rows", (1, 3, 4, 5, 6, 9))
+def test_the_written_out_level_product_has_torch_prods_bits(S, rows):
+    """ms_ssim multiplies its levels with ssim._prod_rows (torch.prod's backward waits on the host): the forward's bits are torch.prod's,
+    on values like the clamped levels raised to their weights, a zero among them; the backward is the product rule, zero factor included"""
+    t = torch.rand((rows, 7, 3), generator=torch.Generator().manual_seed(rows)).to(DEV) ** 0.3
+    t[rows // 2, 2, 1] = 0.0
+    assert (bits(S._prod_rows(t)) == bits(torch.prod(t, dim=0))).all()
+    a, b = t.clone().requires_grad_(True), t.double().requires_grad_(True)
+    S._prod_rows(a).sum().backward()
+    torch.prod(b, dim=0).sum().backward()
+    grad_close(a.grad, b.grad, what="product over %d levels" % rows)
