@@ -12,7 +12,7 @@
 //      to the record list of every 32x32-texel tile under its bilinear footprint.  Its first workgroups plan the face sweep (sweep items).
 //   2. gather_bwd (this file), one launch, two kinds of workgroup:
 //      a. texture tiles   one workgroup per (image, tile): streams the tile's record list into INT32 fixed-point LDS accumulators (per-tile
-//         power-of-two scale) and writes the tile once with plain stores: no zero-fill pass over grad_textures.
+//         power-of-two scale) and writes the tile once (store_once, mm_device.h): no zero-fill pass over grad_textures.
 //      b. face sweep      8 lanes per sweep item (a 128-pixel chunk of a face's inflated screen box; an image's items are dealt to its waves
 //         round-robin): pixels the face owns give K2 (add the pixel pass's numbers), uncovered pixels that hold the face among their first
 //         knum silhouette faces give K4; hits are ballot-compacted over the wave and finished by all 64 lanes into INT64 fixed-point per-item
@@ -247,8 +247,8 @@ __device__ inline void texture_tile_store(const BwdArgs& a, int b, int T, int tx
             const int x = tx0 + lx, y = ty0 + ly;
             if (x < a.Wt && y < a.Ht) {
                 const int4 v = *(const int4*)&s_acc[c][ly * MM_TS + lx];
-                *(float4*)(a.grad_textures + (((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x) =
-                    make_float4((float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv);
+                store_once((float4*)(a.grad_textures + (((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x),
+                                    make_float4((float)v.x * inv, (float)v.y * inv, (float)v.z * inv, (float)v.w * inv));
             }
         }
     } else {
@@ -256,7 +256,7 @@ __device__ inline void texture_tile_store(const BwdArgs& a, int b, int T, int tx
             const int c = i / (MM_TS * MM_TS), r = i - c * (MM_TS * MM_TS);
             const int ly = r / MM_TS, lx = r - ly * MM_TS;
             const int x = tx0 + lx, y = ty0 + ly;
-            if (x < a.Wt && y < a.Ht) a.grad_textures[(((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x] = (float)s_acc[c][r] * inv;
+            if (x < a.Wt && y < a.Ht) store_once(a.grad_textures + (((size_t)b * 3 + c) * a.Ht + y) * a.Wt + x, (float)s_acc[c][r] * inv);
         }
     }
 }

@@ -733,4 +733,34 @@ __device__ inline bool last_workgroup(unsigned* ticket, unsigned arrivals, bool 
     return s_last != 0;
 }
 
+// ---- store policy of the arrays a kernel writes ONCE and nothing in the step reads again (image, normals image, dL/dbg, dL/dtextures) -----
+// A plain store leaves its line dirty in the storing XCD's write-back L2; what is still dirty when the kernel ends is written back at its
+// end, in front of the next launch: 3.0 us behind 32 MB on this chip (profiles/tools/dirty_boundary.hip; profiles/store_policy_ab.md).
+//   store_once()     the policy those arrays get: NON-TEMPORAL (nt: still write-back, but first in line for eviction, so most lines have left
+//                    L2 by the kernel's end).  -1.5 us per step at config 2, stores where they always were.
+//   store_through()  WRITE-THROUGH (sc1: the bytes go to the memory side at once, the line is dropped).  Removes the boundary cost almost
+//                    entirely in the probe and LOSES in the step (+0.6 us in place, +1.2 ... +2.2 us moved behind the record atomics): the
+//                    kernels' waves end on these stores, and a write-through store's acknowledgement is a full trip to the memory side.  Kept
+//                    for a caller whose stores sit well in front of its end.
+// Neither form gets L2's write combining for free, so one wave instruction should cover whole 32-byte sectors: 4, 8, 12 or 16 bytes per lane
+// at consecutive addresses.  The 12- and 16-byte write-through forms are spelled as instructions (no builtin carries sc1 at that width); the
+// s_nop is the wait state a VALU write of the data registers needs behind a store of more than 8 bytes, which the compiler cannot insert
+// into an asm.  Vector stores only.
+typedef float mm_f3v __attribute__((ext_vector_type(3)));
+typedef float mm_f4v __attribute__((ext_vector_type(4)));
+__device__ inline void store_once(float* p, float v) { __builtin_nontemporal_store(v, p); }
+__device__ inline void store_once(Packed3* p, float x, float y, float z) { __builtin_nontemporal_store(mm_f3v{x, y, z}, (mm_f3v*)p); }
+__device__ inline void store_once(float4* p, float4 v) { __builtin_nontemporal_store(mm_f4v{v.x, v.y, v.z, v.w}, (mm_f4v*)p); }
+__device__ inline void store_through(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void store_through(float2* p, float2 v) {
+    __hip_atomic_store((unsigned long long*)p, ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline void store_through(Packed3* p, float x, float y, float z) {
+    asm volatile("global_store_dwordx3 %0, %1, off sc1\n\ts_nop 0" ::"v"(p), "v"(mm_f3v{x, y, z}));
+}
+__device__ inline void store_through(float4* p, float4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" ::"v"(p), "v"(mm_f4v{v.x, v.y, v.z, v.w}));
+}
+
 }  // namespace mm
+

@@ -464,7 +464,7 @@ __device__ inline void step_pixel_pass(const RasterArgs& a, const TileCtx& t, in
             float gbg[3];
             dcs = pixel_pass_background<false>(pl, true, bgv, coef, gbg);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a.grad_bg[((size_t)t.b * 3 + c) * hw + pin] = gbg[c];
+            for (int c = 0; c < 3; ++c) store_once(a.grad_bg + ((size_t)t.b * 3 + c) * hw + pin, gbg[c]);
         }
     } else if (t.in_img && (hf >= 0 || kNoMask)) {
         PixelShade sh = shw;
@@ -472,7 +472,7 @@ __device__ inline void step_pixel_pass(const RasterArgs& a, const TileCtx& t, in
         pixel_pass_shaded<kNoMask, false>(pl, true, sh, s, tq, L, bgv, a.Ht, a.Wt, a.ntx_tex, a.mult, pg);
         if (kNoMask) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a.grad_bg[((size_t)t.b * 3 + c) * hw + pin] = pg.gbg[c];
+            for (int c = 0; c < 3; ++c) store_once(a.grad_bg + ((size_t)t.b * 3 + c) * hw + pin, pg.gbg[c]);
         }
         dcs = pg.dcs; snx = sh.nx; sny = sh.ny; snz = sh.nz;
         if (hf >= 0) { a.gp[pix * 2 + 0] = pg.k0; a.gp[pix * 2 + 1] = pg.k1; a.gp2[pix] = pg.k2; m2 = pg.m2; }
@@ -648,11 +648,11 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
         h.f = -1;
     }
     if (t.in_img) {
-        *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], out[3]);
+        store_once((float4*)(a.rgba + pix * 4), make_float4(out[0], out[1], out[2], out[3]));   // (written once, read by nobody in the step: mm_device.h)
         a.face_idx[pix] = h.f;
         if (h.f >= 0 && a.fflag) a.fflag[((size_t)t.b * a.F + h.f) * 2] = 1;     // "owns a pixel" (idempotent plain store: the backward sweeps this face)
         a.soft[pix] = make_float2((h.f >= 0 || ss.zeros >= 2) ? 0.f : (ss.zeros == 1 ? -ss.qnz : ss.qnz), __int_as_float(ss.lastf));
-        if (a.imnormal) { a.imnormal[pix * 3] = nx; a.imnormal[pix * 3 + 1] = ny; a.imnormal[pix * 3 + 2] = nz; }
+        if (a.imnormal) store_once((Packed3*)(a.imnormal + pix * 3), nx, ny, nz);            // (one 12-byte store per lane: 96 contiguous bytes per tile row)
     }
     if (a.gt) {                                                  // recon_data terms of this tile (networks.py:370-377)
         float l1 = 0.f, up = 0.f, down = 0.f, cs = 0.f;
@@ -751,7 +751,7 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
                 float gbg[3];
                 dcs = pixel_pass_background<false>(pl, true, bgv[q], coef, gbg);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) a.grad_bg[((size_t)b * 3 + c) * hw + pin[q]] = gbg[c];
+                for (int c = 0; c < 3; ++c) store_once(a.grad_bg + ((size_t)b * 3 + c) * hw + pin[q], gbg[c]);
             }
             float dl[9];
             wave_light_sums(false, dcs, 0.f, 0.f, 0.f, a.options, dl);
@@ -759,11 +759,11 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
         }
         if (!in[q]) continue;
         const size_t pix = (size_t)b * hw + pin[q];
-        if (kIndexed && bad) { const float nan = __uint_as_float(0x7FC00000u); *(float4*)(a.rgba + pix * 4) = make_float4(nan, nan, nan, nan); }
-        else *(float4*)(a.rgba + pix * 4) = make_float4(out[0], out[1], out[2], 1.f - 1.f);
+        if (kIndexed && bad) { const float nan = __uint_as_float(0x7FC00000u); store_once((float4*)(a.rgba + pix * 4), make_float4(nan, nan, nan, nan)); }
+        else store_once((float4*)(a.rgba + pix * 4), make_float4(out[0], out[1], out[2], 1.f - 1.f));
         a.face_idx[pix] = -1;
         a.soft[pix] = make_float2(1.f, __int_as_float(0x7FFFFFFF));
-        if (a.imnormal) { a.imnormal[pix * 3] = 0.f; a.imnormal[pix * 3 + 1] = 0.f; a.imnormal[pix * 3 + 2] = 0.f; }
+        if (a.imnormal) store_once((Packed3*)(a.imnormal + pix * 3), 0.f, 0.f, 0.f);
         if (a.gt) {
             const float gm = gtv[q][3];
 #pragma unroll
