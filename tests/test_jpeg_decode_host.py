@@ -390,9 +390,10 @@ def sanitized(tmp_path_factory):
     return exe
 
 
-def run_forms(exe, tmp, name, forms):
-    """one fixture file's forms through the sanitized program and through ``entropy_decode_host``: [(form, statuses, status of the file)]"""
-    data = file_of(name)
+def run_forms(exe, tmp, name, forms, data=None):
+    """one fixture file's forms (or those of ``data``, a clean file, under ``name``) through the sanitized program and through
+    ``entropy_decode_host``: [(form, statuses, status of the file)]"""
+    data = file_of(name) if data is None else data
     h = JD.parse_header(data)
     per, luma = JD.SHAPES[h["layout"]][:2]
     mcus, blocks = h["mx"] * h["my"], h["mx"] * h["my"] * per
