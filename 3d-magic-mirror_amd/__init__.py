@@ -13,6 +13,7 @@ from .pyramid import lower_pyramid, pyramid_frames  # noqa: F401
 from .poisson import lower_poisson, poisson_frames  # noqa: F401
 from .jpeg import JpegBatch, encode_jpeg, jpeg_roundtrip, lower_jpeg  # noqa: F401
 from .jpeg_decode import DecodedFrames, decode_jpeg, decode_jpeg_host, lower_jpeg_decode  # noqa: F401
+from .png_decode import decode_png, decode_png_host, lower_png_decode  # noqa: F401
 from .gif import GIF_SEGMENT, GifFile, encode_gif, quantize_frames  # noqa: F401
 from .png import PNG_MAX_SEGMENT, PNG_SEGMENT, PngBatch, encode_png, lower_png  # noqa: F401
 from .fid import FID_SPLIT, FidStatistics, fid_score, frechet_distance, inception_input  # noqa: F401

@@ -249,6 +249,15 @@ class MMJpegDecodeDesc(ctypes.Structure):
                 ("bytes", c_p), ("tables_host", c_p), ("tables", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+PNG_DEC_FILE_INTS, PNG_DEC_MAX_FILES, PNG_DEC_MAX_BYTES, PNG_DEC_MAX_PIXELS = 16, 1 << 20, 1 << 30, 1 << 36      # MM_PNG_DEC_*
+PNG_POST_THRESHOLD, PNG_POST_ALPHA = 1, 2      # MM_PNG_POST_*
+
+
+class MMPngDecodeDesc(ctypes.Structure):
+    _fields_ = [("n", c_i), ("channels", c_i), ("n_tables", c_i), ("post", c_i), ("n_bytes", ctypes.c_int64),
+                ("bytes", c_p), ("tables_host", c_p), ("tables", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 GIF_SEGMENT, GIF_MAX_SEGMENT = 1024, 3838      # MM_GIF_SEGMENT, MM_GIF_MAX_SEGMENT
 
 
@@ -375,6 +384,8 @@ SIGNATURES = {
     "mm_png_encode": (c_int, [P(MMPngDesc), c_p]),
     "mm_jpeg_decode_query_workspace": (c_z, [P(MMJpegDecodeDesc)]),
     "mm_jpeg_decode": (c_int, [P(MMJpegDecodeDesc), c_p]),
+    "mm_png_decode_query_workspace": (c_z, [P(MMPngDecodeDesc)]),
+    "mm_png_decode": (c_int, [P(MMPngDecodeDesc), c_p]),
     "mm_fid_input": (c_int, [P(MMFidInputDesc), c_p]),
     "mm_fid_stats_query_workspace": (c_z, [P(MMFidStatsDesc)]),
     "mm_fid_stats": (c_int, [P(MMFidStatsDesc), c_p]),
@@ -395,7 +406,7 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
               35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc, 42: MMJpegModesDesc,
-              43: MMFidInputDesc, 44: MMFidStatsDesc, 45: MMJpegDecodeDesc}
+              43: MMFidInputDesc, 44: MMFidStatsDesc, 45: MMJpegDecodeDesc, 46: MMPngDecodeDesc}
 
 _FN = {}          # export name -> bound function, filled by lib()
 

@@ -28,8 +28,8 @@ FP_ATOMICS = ["-munsafe-fp-atomics"]     # mm_dibr.hip (features of more than 8 
 SOURCES = {"mm_abi.hip": EXACT, "mm_reg.hip": EXACT, "mm_texflow.hip": EXACT + FP_ATOMICS, "mm_attloss.hip": EXACT, "mm_vertex.hip": EXACT, "mm_raster.hip": EXACT,
            "mm_backward.hip": RELAXED, "mm_pixel_bwd.hip": EXACT, "mm_loss.hip": EXACT, "mm_nn.hip": EXACT, "mm_dibr.hip": EXACT + FP_ATOMICS, "mm_ops.hip": EXACT + FP_ATOMICS,
            "mm_ssim.hip": EXACT, "mm_encfeat.hip": EXACT, "mm_interp.hip": EXACT, "mm_views.hip": EXACT, "mm_vertex_views.hip": EXACT, "mm_indexed.hip": EXACT, "mm_vertex_indexed.hip": EXACT,
-           "mm_critic.hip": EXACT, "mm_export.hip": EXACT, "mm_batch.hip": EXACT, "mm_composite.hip": EXACT, "mm_pyramid.hip": EXACT, "mm_poisson.hip": EXACT, "mm_jpeg.hip": EXACT, "mm_jpeg_decode.hip": EXACT, "mm_gif.hip": EXACT, "mm_png.hip": EXACT, "mm_fid.hip": EXACT}
-HEADERS = ["mm_device.h", "mm_raster_common.h", "mm_raster_walk.h", "mm_backward.h", "mm_order.h", "mm_pixel_pass.h", "mm_plan.h", "mm_quant.h", "mm_frame.h", "mm_row_sum.h", "mm_stream.h", "mm_jpeg_idct.h", "mm_jpeg_entropy.h", os.path.join("..", "..", "include", "mm_render.h")]
+           "mm_critic.hip": EXACT, "mm_export.hip": EXACT, "mm_batch.hip": EXACT, "mm_composite.hip": EXACT, "mm_pyramid.hip": EXACT, "mm_poisson.hip": EXACT, "mm_jpeg.hip": EXACT, "mm_jpeg_decode.hip": EXACT, "mm_gif.hip": EXACT, "mm_png.hip": EXACT, "mm_png_decode.hip": EXACT, "mm_fid.hip": EXACT}
+HEADERS = ["mm_device.h", "mm_raster_common.h", "mm_raster_walk.h", "mm_backward.h", "mm_order.h", "mm_pixel_pass.h", "mm_plan.h", "mm_quant.h", "mm_frame.h", "mm_row_sum.h", "mm_stream.h", "mm_jpeg_idct.h", "mm_jpeg_entropy.h", "mm_inflate.h", os.path.join("..", "..", "include", "mm_render.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

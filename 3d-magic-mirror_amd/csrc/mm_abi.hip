@@ -82,6 +82,9 @@ int launch_png(const MMPngDesc*, hipStream_t);
 int check_jpeg_decode(const MMJpegDecodeDesc*);
 size_t jpeg_decode_workspace_bytes(const MMJpegDecodeDesc*);
 int launch_jpeg_decode(const MMJpegDecodeDesc*, hipStream_t);
+int check_png_decode(const MMPngDecodeDesc*);
+size_t png_decode_workspace_bytes(const MMPngDecodeDesc*);
+int launch_png_decode(const MMPngDecodeDesc*, hipStream_t);
 int launch_fid_input(const MMFidInputDesc*, hipStream_t);
 size_t fid_stats_workspace_bytes(const MMFidStatsDesc*);
 int launch_fid_stats(const MMFidStatsDesc*, hipStream_t);
@@ -1024,6 +1027,19 @@ int mm_jpeg_decode(const MMJpegDecodeDesc* d, mm_stream_t stream) {
     return mm::launch_jpeg_decode(d, (hipStream_t)stream);
 }
 
+size_t mm_png_decode_query_workspace(const MMPngDecodeDesc* d) {
+    return mm::check_png_decode(d) == MM_OK ? mm::png_decode_workspace_bytes(d) : 0;
+}
+
+int mm_png_decode(const MMPngDecodeDesc* d, mm_stream_t stream) {
+    const int shape = mm::check_png_decode(d);                    // (every record of tables_host: csrc/mm_png_decode.hip)
+    if (shape != MM_OK) return shape;
+    if (!d->bytes || !d->tables || !d->out || !d->workspace) return MM_ERR_NULL_POINTER;
+    if (d->workspace_bytes < mm::png_decode_workspace_bytes(d) || ((uintptr_t)d->workspace & 15) || ((uintptr_t)d->tables & 15)) return MM_ERR_WORKSPACE;
+    mm::clear_stale_error();
+    return mm::launch_png_decode(d, (hipStream_t)stream);
+}
+
 int mm_fid_input(const MMFidInputDesc* d, mm_stream_t stream) {
     if (!d) return MM_ERR_NULL_POINTER;
     if (d->n <= 0 || d->H < 1 || d->W < 1 || d->Ho < 1 || d->Wo < 1) return MM_ERR_BAD_SHAPE;
@@ -1137,7 +1153,7 @@ size_t mm_struct_size(int which) {
         case 37: return sizeof(MMJpegDesc);     case 38: return sizeof(MMJpegRoundtripDesc);    // (36: unassigned)
         case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc); case 41: return sizeof(MMPngDesc);
         case 42: return sizeof(MMJpegModesDesc); case 43: return sizeof(MMFidInputDesc); case 44: return sizeof(MMFidStatsDesc);
-        case 45: return sizeof(MMJpegDecodeDesc);
+        case 45: return sizeof(MMJpegDecodeDesc); case 46: return sizeof(MMPngDecodeDesc);
         default: return 0;
     }
 }

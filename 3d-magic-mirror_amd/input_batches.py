@@ -116,6 +116,45 @@ class ImagePool:
         JD.decode_jpeg(low, out=self.images)                                # the files: the decoder's one upload, then straight into the image region
         return self
 
+    @classmethod
+    def from_files(cls, jpeg_files, png_masks, device, mask=None):
+        """The pool of a dataset directory's two files per sample: the photos, JPEG ``jpeg_files``, through ``decode_jpeg`` and the masks, PNG
+        ``png_masks``, through ``decode_png``, both straight into the pool's one buffer (each a list of bytes / paths, or a ``JpegBatch`` /
+        ``PngBatch``).  Beside the files' bytes only the two small tables are uploaded.  mask: None keeps what ``Image.open(m).convert('L')``
+        gives (bird.py, atr.py: the threshold after the resize follows); "market" maps every byte that is not 0 to 255 on the device
+        (market.py's ``point(lambda p: p > 0 and 255)``); "alpha" decodes as ``.convert('RGBA')`` and keeps the alpha plane, not 0 as 255
+        (thuman2.py).  What ``ImagePool(images, segs, device)`` holds for the same arrays, byte for byte.  ValueError: what the two decoders
+        reject, masks whose sizes do not match the photos', damaged files (the decoders' strict waits for the status)."""
+        from . import jpeg_decode as JD
+        from . import png_decode as PD
+        if device is None:
+            raise ValueError("ImagePool.from_files decodes on a device")
+        if mask not in (None, "market", "alpha"):
+            raise ValueError("mask must be None, 'market' or 'alpha', got %r" % (mask,))
+        low = JD.lower_jpeg_decode(jpeg_files, "RGB")
+        lowm = PD.lower_png_decode(png_masks, "RGBA" if mask == "alpha" else "L")
+        n = low["n"]
+        if lowm["n"] != n:
+            raise ValueError("jpeg_files and png_masks must be two non-empty lists of the same length, got %d and %d" % (n, lowm["n"]))
+        for i in range(n):
+            if tuple(lowm["sizes"][i]) != tuple(low["sizes"][i]):
+                raise ValueError("image %d: the photo is %d x %d, its mask %d x %d" % ((i,) + tuple(low["sizes"][i]) + tuple(lowm["sizes"][i])))
+        self = cls.__new__(cls)
+        self.sizes, self.offsets, self.device = low["sizes"], low["offsets"], torch.device(device)
+        P = int(self.offsets[-1])
+        tables = (4 * P + 7) // 8 * 8                          # the layout of __init__'s buffer
+        self.buffer = torch.zeros(tables + 8 * (n + 1) + 8 * n, dtype=torch.uint8, device=self.device)
+        self.images, self.segs = self.buffer[:3 * P], self.buffer[3 * P:4 * P]
+        self.offsets_dev = self.buffer[tables:tables + 8 * (n + 1)].view(torch.int64)
+        self.sizes_dev = self.buffer[tables + 8 * (n + 1):].view(torch.int32).view(n, 2)
+        N.require_device(self.buffer)
+        tail = np.concatenate([self.offsets.view(np.uint8), self.sizes.reshape(-1).view(np.uint8)])
+        self.buffer[tables:].copy_(torch.from_numpy(tail).pin_memory(), non_blocking=True)      # the two tables: one upload, not waited for
+        JD.decode_jpeg(low, out=self.images)
+        post = {None: 0, "market": N.PNG_POST_THRESHOLD, "alpha": N.PNG_POST_THRESHOLD | N.PNG_POST_ALPHA}[mask]
+        PD._decode_into(lowm, self.segs, True, post=post)
+        return self
+
     def __len__(self):
         return self.sizes.shape[0]
 

@@ -22,8 +22,8 @@ Damaged entropy-coded data is not an error of the parser: the kernel cannot read
 stops at the damage with the rest of its coefficients zero, and the file's ``status`` gets ST_OVERRUN / ST_BAD_CODE / ST_BAD_RUN /
 ST_BAD_SIZE.  Such a file's pixels are defined by ``decode_jpeg_host``, not by Pillow (which raises, or conceals differently).
 
-Out of scope: progressive and arithmetic coding, 12-bit, CMYK / YCCK, non-interleaved scans, 4:1:1 and 4:4:0, PNG, reading directories,
-anything differentiable."""
+Out of scope: progressive and arithmetic coding, 12-bit, CMYK / YCCK, non-interleaved scans, 4:1:1 and 4:4:0, reading directories,
+anything differentiable.  PNG files (the datasets' masks) are ``decode_png``'s, in png_decode.py."""
 import os
 import re
 
@@ -527,8 +527,8 @@ class DecodedFrames:
 
     def __init__(self, images, offsets, sizes, status, mode):
         self.images, self.offsets, self.sizes, self.status, self.mode = images, offsets, sizes, status, mode
-        ch = 3 if mode == "RGB" else 1
-        self.frames = [images[ch * int(offsets[i]):ch * int(offsets[i + 1])].view((int(h), int(w), 3) if ch == 3 else (int(h), int(w)))
+        ch = {"RGB": 3, "RGBA": 4}.get(mode, 1)                           # ("RGBA": decode_png's)
+        self.frames = [images[ch * int(offsets[i]):ch * int(offsets[i + 1])].view((int(h), int(w), ch) if ch > 1 else (int(h), int(w)))
                        for i, (h, w) in enumerate(sizes.tolist())]
 
     def __len__(self):

@@ -14,7 +14,8 @@ of ``PNG_SEGMENT`` bytes, and each segment is one deflate block with the fixed H
 point anywhere; the order is in DESIGN.md and in the kernel's header.
 
 Out of scope: dynamic Huffman codes and stored blocks, matches across segments, lazy matching, interlacing, palettes, 16-bit depth,
-ancillary chunks, APNG, Pillow's or libpng's own bytes, decoding, ``save_image(normalize=True)``'s min-max stretch, ``bench.py``.
+ancillary chunks, APNG, Pillow's or libpng's own bytes, ``save_image(normalize=True)``'s min-max stretch, ``bench.py``.  Decoding -- these
+files and other encoders' -- is ``decode_png`` in png_decode.py.
 Device tensors only."""
 import functools
 

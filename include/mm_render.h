@@ -1310,6 +1310,59 @@ size_t mm_jpeg_decode_query_workspace(const MMJpegDecodeDesc* desc);      /* rea
 int mm_jpeg_decode(const MMJpegDecodeDesc* desc, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * PNG decoding: n PNG FILES' IDAT data, back to back in device memory, as 8-bit frames -- to the byte what Pillow's
+ * Image.open(file).convert(mode) gives for mode L (channels 1), RGB (3) or RGBA (4).  csrc/mm_png_decode.hip; the caller walks the
+ * chunks, checks their CRCs and the zlib header (png_decode.py: lower_png_decode) and hands over tables of int32 words:
+ *   files     n x MM_PNG_DEC_FILE_INTS: H, W, colour type (0, 2, 3, 4, 6), bit depth (8; 1, 2, 4 for types 0 and 3), bpp (the filters'
+ *             distance: 1 below 8 bits, else the file's channels), row_bytes (ceil(W * channels * depth / 8), without the filter byte),
+ *             conversion table (types 0 and 3; -1 for the others), byte begin and byte end of the file's raw deflate stream in `bytes`
+ *             (its concatenated IDAT data behind the two zlib header bytes), byte offset of its inflated stream S in the workspace
+ *             (H * (1 + row_bytes) bytes, dense in file order); the rest 0
+ *   offsets   (n + 1) int64 (8-byte aligned in the table): file i's pixels start at pixel offsets[i] of out, H * W pixels, no padding
+ *   conv      n_tables x 256 words: for a sample or palette index v the output pixel, channel c in byte c (mode L: byte 0)
+ * in this order in one buffer, given twice: tables_host is read (and every record re-checked) before the call returns, tables is the
+ * same on the device.  One memset and three launches whatever n: inflate (one wave per file; csrc/mm_inflate.h) into the zeroed S,
+ * unfilter in place (filters 0-4), unpack + convert + store.  out may start at any byte.  A damaged stream cannot read or write out of
+ * range or spin; its file's status gets MM_PNG_ST_* bits, the bytes of S it did not produce stay zero and the other passes still run.
+ * The workspace is the caller's, mm_png_decode_query_workspace bytes, 16-byte aligned: the streams S, then, on the next multiple of
+ * 256, status (n int32).
+ * MM_ERR_BAD_SHAPE: a count < 1, channels not 1 / 3 / 4, post outside 0..3 or MM_PNG_POST_ALPHA without channels 4, a record that contradicts itself or its neighbours (a size below 1, an unknown
+ * colour type, a depth the type does not allow, bpp or row_bytes not what the type, depth and W give, a table index out of range or
+ * not -1 where there is none, bytes outside [0, n_bytes] or not begin <= end, stream or pixel offsets not the running sums).
+ * MM_ERR_UNSUPPORTED: 16-bit depth, H or W above 65535, n > MM_PNG_DEC_MAX_FILES, n_bytes or the streams above MM_PNG_DEC_MAX_BYTES, more than
+ * MM_PNG_DEC_MAX_PIXELS pixels (the query returns 0 for all of these).  MM_ERR_WORKSPACE: too small or misaligned, or tables not 16-byte
+ * aligned.  Every refusal comes before any GPU work.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define MM_PNG_DEC_FILE_INTS 16
+#define MM_PNG_DEC_MAX_FILES (1 << 20)
+#define MM_PNG_DEC_MAX_BYTES (1 << 30)
+#define MM_PNG_DEC_MAX_PIXELS (1LL << 36)
+#define MM_PNG_POST_THRESHOLD 1     /* every output byte that is not 0 becomes 255 (datasets/market.py's seg_loader: point(lambda p: p > 0 and 255)) */
+#define MM_PNG_POST_ALPHA 2         /* channels 4 only: out gets the alpha plane alone, one byte a pixel (datasets/thuman2.py's seg_loader) */
+#define MM_PNG_ST_OVERRUN 1         /* bits wanted past the stream's end: the reader supplied zeros and the decode stopped at that symbol */
+#define MM_PNG_ST_BAD_BLOCK 2       /* BTYPE 3, or a stored block whose LEN and NLEN disagree */
+#define MM_PNG_ST_BAD_TABLE 4       /* a dynamic header zlib refuses */
+#define MM_PNG_ST_BAD_CODE 8        /* bits that match no code, literal/length symbols 286 / 287, distance symbols 30 / 31 */
+#define MM_PNG_ST_BAD_DISTANCE 16   /* a distance that reaches before the first byte produced */
+#define MM_PNG_ST_SHORT 32          /* the final block ends before S bytes */
+#define MM_PNG_ST_BAD_FILTER 64     /* a filter byte above 4: the row is taken as filter 0 */
+typedef struct MMPngDecodeDesc {
+    int32_t n;                      /* files */
+    int32_t channels;               /* of out: 1 (L), 3 (RGB), 4 (RGBA) */
+    int32_t n_tables;               /* conversion tables (0 if no file is grey or palette) */
+    int32_t post;                   /* MM_PNG_POST_* bits, 0: the pixels as they are */
+    int64_t n_bytes;                /* of `bytes` */
+    const uint8_t* bytes;           /* the files' deflate streams, back to back; any alignment */
+    const int32_t* tables_host;     /* files | offsets | conv */
+    const int32_t* tables;          /* the same on the device, 16-byte aligned */
+    uint8_t* out;                   /* offsets[n] * channels bytes (offsets[n] with MM_PNG_POST_ALPHA), any alignment */
+    void* workspace;
+    size_t workspace_bytes;
+} MMPngDecodeDesc;
+size_t mm_png_decode_query_workspace(const MMPngDecodeDesc* desc);      /* reads the counts and tables_host */
+int mm_png_decode(const MMPngDecodeDesc* desc, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Host helpers (no GPU involved)
  * ------------------------------------------------------------------------------------------------------------------ */
 /* Build the vertex -> corner CSR from HOST faces (F,3).  offsets: (V+1), items: (3F).  Returns MM_OK or an error. */
@@ -1335,7 +1388,7 @@ const char* mm_last_error_detail(void);
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
  * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc, 42 MMJpegModesDesc,
- * 43 MMFidInputDesc, 44 MMFidStatsDesc, 45 MMJpegDecodeDesc (31, 34 and 36 are unassigned). */
+ * 43 MMFidInputDesc, 44 MMFidStatsDesc, 45 MMJpegDecodeDesc, 46 MMPngDecodeDesc (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1361,7 +1414,8 @@ size_t mm_struct_size(int which);
  * mm_struct_size(42) != 0, and MMJpegRoundtripDesc.reserved named sampling, where 0, all a caller could pass, keeps its meaning; still 9: MMFidInputDesc with
  * mm_fid_input, struct id 43, and MMFidStatsDesc with mm_fid_stats_query_workspace / mm_fid_stats, struct id 44, additions, detected by
  * mm_struct_size(43) != 0; still 9: MMJpegDecodeDesc with mm_jpeg_decode_query_workspace / mm_jpeg_decode, struct id 45, an addition, detected by
- * mm_struct_size(45) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_struct_size(45) != 0; still 9: MMPngDecodeDesc with mm_png_decode_query_workspace / mm_png_decode, struct id 46, an addition, detected by
+ * mm_struct_size(46) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
