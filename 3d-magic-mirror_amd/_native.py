@@ -293,6 +293,7 @@ OPT_CULL_STRICT, OPT_SOFT_SKIP_CULLED, OPT_BBOX_HALF_OPEN, OPT_BARY_ONE_MINUS, O
 OPT_BBOX_MIN_CLOSED_MAX_OPEN = 1 << 9
 OPT_WALK_QUEUE, OPT_WALK_BATCH = 1 << 10, 1 << 11
 OPT_MANY_IN_FLIGHT = 1 << 12          # hint: several independent calls in flight (identical results; include/mm_render.h)
+OPT_ORDER_LAUNCH = 1 << 13            # tuning / tests: the tile sort in a launch of its own, also where the vertex launch would do it (identical results)
 PROF_RECON = ("recon_partial", "recon_final", "recon_bwd", "recon_contour")
 
 

@@ -71,6 +71,18 @@ inline bool walk_queue_mode(int options, int bin_shift) {
 // does the forward walk of this shape leave face flags (Workspace::fflag) for the backward's sweep plan?  Only the compacting walk: flags from
 // the per-batch walk cost raster_fwd 2.5-3 us to save gather_bwd 1.4 us at 128x128 (r06, profiles/r06_batch_walk_flags_ab.md)
 inline bool walk_flags_mode(int options, int bin_shift) { return walk_queue_mode(options, bin_shift); }
+// Does the vertex launch sort this shape's tiles itself?  (Order workgroups beside the record workgroups, counting from boxes they recompute:
+// mm_vertex.hip.)  Exactly the shapes whose tile counts the order kernel would popcount from the bin masks itself (at most 1024 tile slots,
+// mask rows of at most 64 words: launch_order, mm_raster.hip), with 8-pixel bins: the bin is then the tile, and blocks are not sorted as
+// units (walk_block_sort wants bins of 16 pixels).  bin_shift_for gives 8-pixel bins for every such shape whose screen is not a strip: with
+// nb <= ceil(W/8) ceil(H/8) bins its test reads 128 nb words <= 140 F + 128 H W, and words <= F / 64 + 1, nb <= H W / 64 + (W + H) / 8 + 1
+// leave it true unless W + H is of the order of W H / 64 -- a screen a few pixels wide and thousands high (1 x 4096 with 4 096 faces gets
+// 32-pixel bins).  Hence the bin size is asked here and not assumed.  One answer for the vertex launch and for launch_order; the callers
+// add what only they know (one view, no index table, a screen pass at all).  MM_OPT_ORDER_LAUNCH forces the launch of its own.
+inline bool order_in_vertex(int options, int blocks_per_image, int words, int bin_shift) {
+    if (options & MM_OPT_ORDER_LAUNCH) return false;
+    return 4 * blocks_per_image <= 1024 && words <= 64 && bin_shift == 3;
+}
 
 // ---- workspace carving (all offsets multiples of 256 bytes) ---------------------------------------------------------
 struct Workspace {

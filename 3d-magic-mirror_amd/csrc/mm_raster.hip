@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void bincount_kernel(const uint64_t* binmask, 
 // Orders the tile slots (16x16 block * 4 + quadrant) of every image by their soft-mask candidate count, descending: a counting
 // sort in LDS (keys clipped to 1023; slots per image <= MM_ORDER_MAX_SLOTS), linear in the slots.  Only the launch ORDER of raster_fwd
 // depends on it -- slots with equal counts may come out in any order, no result does.  Bit 15 of an entry marks a tile that no
-// face can touch (count 0), which raster_fwd then never walks.
+// face can touch (count 0), which raster_fwd then never walks.  (Not launched where the vertex launch's order workgroups sort: launch_order.)
 #define MM_ORDER_MAX_SLOTS 16384      // 1024x1024 pixels; bigger screens are walked in natural order
 __global__ __launch_bounds__(256) void order_kernel(RasterArgs a, unsigned short* order, int* nheavy) {
     __shared__ unsigned short s_key[MM_ORDER_MAX_SLOTS];
@@ -216,12 +216,15 @@ bool render_step_mode(const MMRenderDesc* d, const Workspace& w) {
     return a.bin_shift == 3 && walk_block_mode(a) && !walk_queue_mode(a);
 }
 
-const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nheavy, int* bincount, int B, void** prof_events, hipStream_t s) {
+const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nheavy, int* bincount, int B, void** prof_events, hipStream_t s,
+                                   bool sorted_by_vertex) {
     const int nslot = 4 * a.blocks_per_image;
     a.order = nullptr; a.bincount = nullptr;
     a.block_sort = walk_block_sort(a) ? 1 : 0;
     if (nslot > MM_ORDER_MAX_SLOTS || nslot > 0x7FFF) return nullptr;          // (entries are 15 bits + the empty flag)
     ProfScope po(prof_events, MM_PROF_ORDER, s);
+    // the vertex launch's order workgroups have sorted the tiles already (mm_vertex.hip): nothing to launch, the slot reads as empty
+    if (sorted_by_vertex && order_in_vertex(a.options, a.blocks_per_image, a.words, a.bin_shift)) return order;
     if (nslot > 1024 || a.words > 64) {                          // big screen / mesh: the bins' candidate counts by a parallel kernel first
         const int nrows = B * a.nbx * a.nby;
         hipLaunchKernelGGL(bincount_kernel, dim3((nrows + 3) / 4), dim3(256), 0, s, a.binmask, bincount, nrows, a.words);
@@ -235,7 +238,7 @@ int launch_raster_fwd(const MMRenderDesc* d, const Workspace& w, hipStream_t s, 
     RasterArgs a = make_raster_args(d, w);
     a.views = views;
     if (index_table) a.ltot = reinterpret_cast<long long*>(const_cast<int*>(index_table));   // (indexed calls: see indexed_table; views == 1, no fused loss)
-    a.order = launch_order(a, w.order, w.nheavy, w.bincount, d->B, d->prof_events, s);     // heavy-first launch order
+    a.order = launch_order(a, w.order, w.nheavy, w.bincount, d->B, d->prof_events, s, views == 1 && !index_table);     // heavy-first launch order
     a.spread = walk_spread(a);
     a.nheavy = w.nheavy;
     const bool block = walk_block_mode(a);

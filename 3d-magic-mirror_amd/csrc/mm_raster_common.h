@@ -801,8 +801,11 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
 RasterArgs make_raster_args(const MMRenderDesc* d, const Workspace& w);
 // plan kernel (mm_raster.hip), one workgroup per image between the vertex stage and the walk: (a) heavy-first tile order for the
 // walk kernels, (b) the sweep items (face, box chunk) of the backward.  Returns the order buffer to put in
-// RasterArgs::order, or nullptr where the sort does not pay (then the natural order is used).
-const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nheavy, int* bincount, int B, void** prof_events, hipStream_t s);
+// RasterArgs::order, or nullptr where the sort does not pay (then the natural order is used).  sorted_by_vertex: the caller's vertex launch
+// was mm_render_forward's (one view, no index table) -- where order_in_vertex (mm_device.h) holds it has written order / nheavy already and
+// nothing is launched here (the MM_PROF_ORDER bracket stays, empty).
+const unsigned short* launch_order(RasterArgs& a, unsigned short* order, int* nheavy, int* bincount, int B, void** prof_events, hipStream_t s,
+                                   bool sorted_by_vertex = false);
 // The walk kernels come in two workgroup shapes with identical results: 256 threads (four tiles per workgroup, heavy tiles walked by
 // the four waves together) and 64 threads (one tile per workgroup).  Measured (profiles/r02_walk_shapes.md), raster_fwd us, block /
 // wave: 128x128 1280 faces 45.6 / 55.3; 128x64 38.4 / 51.5; 512x512 13 776 faces (no tile sort: a workgroup = the 2x2 tiles of a

@@ -5,6 +5,7 @@
 //   divide, x multiplier, inflated pixel box, unit normal.  Writes the packed face records the pixel stage streams plus
 //   attributes['face_normals'], and -- the 64 faces of a wave being exactly one word of the screen-bin candidate mask --
 //   that mask: per block of 8x8 bins one wave transpose of the lanes' coverage bits (no separate binning pass).
+//   Small screens and meshes: one more workgroup per image sorts the image's tiles for the walk, from boxes it forms itself (order_workgroup).
 // Backward (reverse of the above): one workgroup per image walks the static vertex->corner CSR, so per-vertex
 //   gradients are gathered in a fixed order (no atomics), reduces dT in LDS and finishes with the camera chain.
 //
@@ -16,6 +17,10 @@
 // image b reads the vertices of row vrow[b], the plan's sanitised table (indexed calls, mm_render_indexed_*); only that compilation's argument
 // structs carry the table's pointer, and its launchers take it in the place of the view count.
 #include "mm_device.h"
+#if !defined(MM_VERTEX_INDEXED) && !defined(MM_VERTEX_VIEWS)
+#include "mm_order.h"
+#define MM_VX_ORDER 1         // this compilation's forward kernel carries the order workgroups (below); the other two keep their code
+#endif
 
 #if defined(MM_VERTEX_INDEXED)
 #define MM_VX(name) name##_indexed
@@ -59,6 +64,12 @@ struct VertexFwdArgs {
 #ifdef MM_VERTEX_INDEXED
     const int* vrow;         // (B) the row of `vertices` every image reads
 #endif
+#ifdef MM_VX_ORDER
+    // the order workgroups (order_rows > 0: the grid's first order_rows rows, gridDim.x images each): the images' tile orders
+    unsigned short* order;   // (B,4*blocks_per_image)
+    int* nheavy;             // (B,4)
+    int order_rows, blocks_x, blocks_per_image;
+#endif
 };
 
 __device__ inline void block_camera(const float* azim, const float* elev, const float* dist, const float* bias, int b,
@@ -74,18 +85,31 @@ __device__ inline void block_camera(const float* azim, const float* elev, const 
     __syncthreads();
 }
 
-// one face: camera transform of its three vertices, perspective divide, x multiplier, unit normal, inflated pixel box -> the packed
-// record the pixel stage streams (geo), attributes['face_normals'], cleared face flags.  The expressions of SURVEY 8(a)-a5, in their order.
+// one face's positions: camera transform of its three vertices, perspective divide, x multiplier -> its screen corners, and their pixel box
+// inflated by the soft-mask margin.  ONE text for the record path and for the order workgroups, which repeat it to count the tiles' candidates:
+// compiled with contraction off, both get the same integers.  The expressions of SURVEY 8(a)-a5, in their order.
+struct FacePos { Float3 A, Bv, C; float ax, ay, bx, by, cx, cy; int bx0, by0, bw, bh; unsigned org, ext; };
+__device__ inline FacePos face_position(const VertexFwdArgs& a, const float* pa, const float* pb, const float* pc, const float* T) {
+    FacePos p;
+    p.A = to_camera(pa, T);
+    p.Bv = to_camera(pb, T);
+    p.C = to_camera(pc, T);
+    // perspective_camera: (x*px)/(z*pz), then x multiplier (kaolin rasterises in multiplier units)
+    const float apz = p.A.z * a.proj2, bpz = p.Bv.z * a.proj2, cpz = p.C.z * a.proj2;
+    p.ax = ((p.A.x * a.proj0) / apz) * a.mult; p.ay = ((p.A.y * a.proj1) / apz) * a.mult;
+    p.bx = ((p.Bv.x * a.proj0) / bpz) * a.mult; p.by = ((p.Bv.y * a.proj1) / bpz) * a.mult;
+    p.cx = ((p.C.x * a.proj0) / cpz) * a.mult; p.cy = ((p.C.y * a.proj1) / cpz) * a.mult;
+    // the pixel box of the face inflated by the soft-mask margin (conservative, see pixel_range), packed for the backward's
+    // face sweep: x = px0 | py0 << 16, y = width | height << 16 (0 x 0 if it misses the image)
+    face_pixel_box(p.ax, p.ay, p.bx, p.by, p.cx, p.cy, a.infl, a.mult, a.W, a.H, p.bx0, p.by0, p.bw, p.bh, p.org, p.ext);
+    return p;
+}
+
+// one face: its positions (above), unit normal -> the packed record the pixel stage streams (geo), attributes['face_normals'], cleared face flags
 __device__ inline void face_record(const VertexFwdArgs& a, int b, int f, const float* pa, const float* pb, const float* pc, const float* T,
                                    int& bx0, int& by0, int& bw, int& bh) {
-    const Float3 A = to_camera(pa, T);
-    const Float3 Bv = to_camera(pb, T);
-    const Float3 C = to_camera(pc, T);
-    // perspective_camera: (x*px)/(z*pz), then x multiplier (kaolin rasterises in multiplier units)
-    const float apz = A.z * a.proj2, bpz = Bv.z * a.proj2, cpz = C.z * a.proj2;
-    const float ax = ((A.x * a.proj0) / apz) * a.mult, ay = ((A.y * a.proj1) / apz) * a.mult;
-    const float bx = ((Bv.x * a.proj0) / bpz) * a.mult, by = ((Bv.y * a.proj1) / bpz) * a.mult;
-    const float cx = ((C.x * a.proj0) / cpz) * a.mult, cy = ((C.y * a.proj1) / cpz) * a.mult;
+    const FacePos p = face_position(a, pa, pb, pc, T);
+    const Float3 A = p.A, Bv = p.Bv, C = p.C;
     const float e0[3] = {Bv.x - A.x, Bv.y - A.y, Bv.z - A.z};
     const float e1[3] = {C.x - A.x, C.y - A.y, C.z - A.z};
     float n[3];
@@ -94,23 +118,126 @@ __device__ inline void face_record(const VertexFwdArgs& a, int b, int f, const f
     const float den = len + 1e-10f;
     const float nx = n[0] / den, ny = n[1] / den, nz = n[2] / den;
     const size_t o = (size_t)b * a.F + f;
-    a.geo[o * 3 + 0] = make_float4(ax, ay, bx, by);
-    a.geo[o * 3 + 1] = make_float4(cx, cy, A.z, Bv.z);
-    // the pixel box of the face inflated by the soft-mask margin (conservative, see pixel_range), packed for the backward's
-    // face sweep: x = px0 | py0 << 16, y = width | height << 16 (0 x 0 if it misses the image)
-    unsigned org, ext;
-    face_pixel_box(ax, ay, bx, by, cx, cy, a.infl, a.mult, a.W, a.H, bx0, by0, bw, bh, org, ext);
-    a.geo[o * 3 + 2] = make_float4(C.z, nz, __uint_as_float(org), __uint_as_float(ext));
+    a.geo[o * 3 + 0] = make_float4(p.ax, p.ay, p.bx, p.by);
+    a.geo[o * 3 + 1] = make_float4(p.cx, p.cy, A.z, Bv.z);
+    a.geo[o * 3 + 2] = make_float4(C.z, nz, __uint_as_float(p.org), __uint_as_float(p.ext));
     a.face_normals[o * 3 + 0] = nx; a.face_normals[o * 3 + 1] = ny; a.face_normals[o * 3 + 2] = nz;
     reinterpret_cast<int2*>(a.fflag)[o] = make_int2(0, 0);
+    bx0 = p.bx0; by0 = p.by0; bw = p.bw; bh = p.bh;
 }
 
-__global__ __launch_bounds__(256) void MM_VX(vertex_fwd_kernel)(VertexFwdArgs a) {
+#ifdef MM_VX_ORDER
+// ---------------------------------------------------------------------------------------------------------------------
+// The ORDER WORKGROUP of image b: the counting sort of the image's tiles by candidate count that order_kernel (mm_raster.hip) does from the
+// bin masks -- here from the faces' boxes, which this workgroup forms itself from the step's inputs (face_position: the record path's own
+// text), so that it depends on nothing the record workgroups of this launch write.  No hand-off between workgroups, no ticket, no
+// write-through store: work repeated on a chip that is nine tenths idle during this launch, in place of a launch and a trip of its own.
+//   faces   MM_ORDER_FPT faces per thread and pass: all their corner ids in one trip, all their vertices in the next
+//   count   a tile's count = the faces whose box touches its bin (8-pixel bins: order_in_vertex, mm_device.h), the bin ranges formed as
+//           bin_wave_faces forms them.  A 2-D DIFFERENCE array in LDS: four integer adds per face whatever its box covers (a close-up's faces
+//           cover every bin), a row scan and a column scan over the bins.  Integers throughout: the counts are the masks' popcounts exactly
+//   sort    as order_kernel: min(count, 1023) per tile slot, histogram, tile_sort_scatter<256, 1>, the same order / nheavy arrays
+// ---------------------------------------------------------------------------------------------------------------------
+#ifndef MM_ORDER_FPT
+#define MM_ORDER_FPT 4        // (8 = every load of a 1 280-face mesh in front of all arithmetic: 166 VGPRs instead of 120, not faster; profiles/order_beside_vertex_ab.md)
+#endif
+__device__ inline void order_workgroup(const VertexFwdArgs& a, int b, float* s_trig, Camera* s_cam) {
+    __shared__ unsigned short s_key[1024];
+    __shared__ int s_start[1024];          // histogram, then the first output position of every key
+    __shared__ int s_cnt[1024];            // (nby,nbx) difference array, then the bins' counts; nbx * nby <= tile slots <= 1024
+    __shared__ int s_wave[4];
+    const int tid = threadIdx.x, nbx = a.nbx, nby = a.nby, nslot = 4 * a.blocks_per_image;
+    for (int i = tid; i < 1024; i += 256) { s_start[i] = 0; s_cnt[i] = 0; }
+    const float* vb = a.vertices + (size_t)MM_VX_SAMPLE(b) * a.V * 3;
+    bool camera = false;
+    float T[12];
+    for (int f0 = 0; f0 < a.F; f0 += 256 * MM_ORDER_FPT) {
+        int id[MM_ORDER_FPT][3];
+        float P[MM_ORDER_FPT][9];
+#pragma unroll
+        for (int k = 0; k < MM_ORDER_FPT; ++k) {                   // consecutive lanes, consecutive faces
+            const int f = f0 + k * 256 + tid;
+            id[k][0] = id[k][1] = id[k][2] = 0;
+            if (f < a.F) { const PackedI3 i3 = *(const PackedI3*)(a.faces + (size_t)f * 3); id[k][0] = i3.x; id[k][1] = i3.y; id[k][2] = i3.z; }
+        }
+#pragma unroll
+        for (int k = 0; k < MM_ORDER_FPT; ++k) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) P[k][j] = 0.f;
+            if (f0 + k * 256 + tid < a.F) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { const Packed3 v3 = *(const Packed3*)(vb + (size_t)id[k][c] * 3); P[k][c * 3] = v3.x; P[k][c * 3 + 1] = v3.y; P[k][c * 3 + 2] = v3.z; }
+            }
+        }
+        if (!camera) {                                            // (workgroup-uniform; its barriers also put the zeroed LDS behind them)
+            block_camera(a.azim, a.elev, a.dist, a.bias, b, s_trig, s_cam);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) T[i] = s_cam->T[i];
+            camera = true;
+        }
+#pragma unroll
+        for (int k = 0; k < MM_ORDER_FPT; ++k) {
+            if (f0 + k * 256 + tid >= a.F) continue;
+            const FacePos p = face_position(a, &P[k][0], &P[k][3], &P[k][6], T);
+            if (p.bw <= 0 || p.bh <= 0) continue;                 // the box misses the image: no bin (bin_wave_faces)
+            const int c0 = p.bx0 >> 3, c1 = (p.bx0 + p.bw - 1) >> 3, r0 = p.by0 >> 3, r1 = (p.by0 + p.bh - 1) >> 3;   // pixel_range clips to the image: c1 < nbx, r1 < nby
+            atomicAdd(&s_cnt[r0 * nbx + c0], 1);
+            if (c1 + 1 < nbx) atomicAdd(&s_cnt[r0 * nbx + c1 + 1], -1);   // (the entries of column nbx and row nby would be read by no scan)
+            if (r1 + 1 < nby) {
+                atomicAdd(&s_cnt[(r1 + 1) * nbx + c0], -1);
+                if (c1 + 1 < nbx) atomicAdd(&s_cnt[(r1 + 1) * nbx + c1 + 1], 1);
+            }
+        }
+    }
+    __syncthreads();
+    for (int r = tid; r < nby; r += 256) {                        // row scan
+        int run = 0;
+#pragma unroll 4
+        for (int c = 0; c < nbx; ++c) { run += s_cnt[r * nbx + c]; s_cnt[r * nbx + c] = run; }
+    }
+    __syncthreads();
+    for (int c = tid; c < nbx; c += 256) {                        // column scan: s_cnt[r][c] = faces whose box touches bin (r, c)
+        int run = 0;
+#pragma unroll 4
+        for (int r = 0; r < nby; ++r) { run += s_cnt[r * nbx + c]; s_cnt[r * nbx + c] = run; }
+    }
+    __syncthreads();
+    for (int slot = tid; slot < nslot; slot += 256) {             // (order_kernel's loop, the count read from LDS)
+        const int blk = slot >> 2, q = slot & 3;
+        const int tx0 = (blk % a.blocks_x) * MM_BLOCK_PX + (q & 1) * MM_TILE, ty0 = (blk / a.blocks_x) * MM_BLOCK_PX + (q >> 1) * MM_TILE;
+        int c = 0;
+        if (tx0 < a.W && ty0 < a.H) c = s_cnt[(ty0 >> 3) * nbx + (tx0 >> 3)];
+        c = min(c, 1023);
+        s_key[slot] = (unsigned short)c;
+        atomicAdd(&s_start[c], 1);
+    }
+    tile_sort_scatter<256, 1>(nslot, s_key, s_start, s_wave, a.order + (size_t)b * nslot, a.nheavy + 4 * b);
+}
+#endif
+
+// kOrder: the launch carries order workgroups.  A kernel of its own (vertex_fwd_order_kernel, below) and not a branch of vertex_fwd_kernel: the
+// order workgroups' registers and LDS (120 VGPRs, 10 KB) would be every shape's, and at 13 776 faces and 512x512, where this launch is 43 MB of
+// stores from 864 workgroups, the occupancy they cost made it 2.9 us longer (profiles/order_beside_vertex_ab.md).
+template <bool kOrder>
+__device__ inline void vertex_fwd_body(const VertexFwdArgs& a) {
     __shared__ float s_trig[4];
     __shared__ Camera s_cam;
-    const int b = blockIdx.y, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < a.ntcnt; i += gridDim.x * gridDim.y * 256) a.tcnt[i] = 0;
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < a.nltot; i += gridDim.x * gridDim.y * 256) a.ltot[i] = 0;
+    int b = blockIdx.y;
+#ifdef MM_VX_ORDER
+    if (kOrder) {
+        // The grid's FIRST rows are the order workgroups, one per image: theirs is the launch's longest chain, so they are dispatched in front of
+        // the record workgroups (what workgroups that start late cost a launch: profiles/fused_step_kernel_stats.md).  Workgroup-uniform.
+        if ((int)blockIdx.y < a.order_rows) {
+            const int img = blockIdx.y * gridDim.x + blockIdx.x;
+            if (img < a.B) order_workgroup(a, img, s_trig, &s_cam);
+            return;
+        }
+        b -= a.order_rows;
+    }
+#endif
     // this lane's face: its corner ids and their raw positions depend on nothing the camera produces -- both trips to memory are in
     // flight while four lanes do the fp64 trigonometry and one builds the look-at
     const int f = blockIdx.x * 256 + tid;
@@ -136,6 +263,11 @@ __global__ __launch_bounds__(256) void MM_VX(vertex_fwd_kernel)(VertexFwdArgs a)
     const int c = blockIdx.x * 4 + (tid >> 6);
     if (a.mask != nullptr && c < a.words) bin_wave_faces(a.mask, b, a.nbx, a.nby, a.words, a.bin_shift, c, tid & 63, bx0, by0, bw, bh);
 }
+
+__global__ __launch_bounds__(256) void MM_VX(vertex_fwd_kernel)(VertexFwdArgs a) { vertex_fwd_body<false>(a); }
+#ifdef MM_VX_ORDER
+__global__ __launch_bounds__(256) void vertex_fwd_order_kernel(VertexFwdArgs a) { vertex_fwd_body<true>(a); }
+#endif
 
 struct VertexBwdArgs {
     int B, V, F;
@@ -575,6 +707,19 @@ int MM_VX(launch_vertex_fwd)(const MMRenderDesc* d, const Workspace& w, hipStrea
     a.mask = d->geometry_only ? nullptr : w.binmask; a.fflag = w.fflag;      // (geometry only: nothing walks the screen bins)
     a.ticket = w.ticket;
     dim3 grid((d->F + 255) / 256, d->B);
+#ifdef MM_VX_ORDER
+    // the tile sort inside this launch (order workgroups, above) where launch_order would let order_kernel count the mask bits itself; it then
+    // launches nothing (one predicate: order_in_vertex, mm_device.h).  This compilation is mm_render_forward's, one view and no index table
+    a.order = w.order; a.nheavy = w.nheavy; a.order_rows = 0;
+    a.blocks_x = (d->W + MM_BLOCK_PX - 1) / MM_BLOCK_PX; a.blocks_per_image = w.blocks_per_image;
+    if (!d->geometry_only && order_in_vertex(d->options, w.blocks_per_image, w.words, w.bin_shift)) {
+        a.order_rows = (d->B + (int)grid.x - 1) / (int)grid.x;
+        grid.y += (unsigned)a.order_rows;
+        ProfScope ps(d->prof_events, MM_PROF_VERTEX_FWD, s);
+        hipLaunchKernelGGL(vertex_fwd_order_kernel, grid, dim3(256), 0, s, a);
+        return launch_ok("vertex_fwd");
+    }
+#endif
     { ProfScope ps(d->prof_events, MM_PROF_VERTEX_FWD, s);
       hipLaunchKernelGGL(MM_VX(vertex_fwd_kernel), grid, dim3(256), 0, s, a); }
     return launch_ok("vertex_fwd");

@@ -153,6 +153,9 @@ enum { MM_OPT_WALK_BLOCK = 1 << 1,         /* tuning: force the 256-thread / coo
                                             * shares the chip -- the kernels take the shapes large batches take on their own (forward walk: one tile per
                                             * workgroup for 8-pixel screen bins; face sweep of the backward: four lanes per item).  Four B=48 steps on four
                                             * streams: +3 % images/s; ONE step at a time: -14 % (profiles/r06_many_in_flight_ab.md)                       */
+       MM_OPT_ORDER_LAUNCH = 1 << 13,      /* tuning / tests, identical results: sort the tiles in a launch of their own behind the vertex stage, from the bin
+                                            * masks, also where the vertex launch would sort them itself from recomputed boxes (small screens and meshes,
+                                            * one view: profiles/order_beside_vertex_ab.md).  No influence on whether a call takes step mode                */
        MM_OPT_BBOX_MIN_CLOSED_MAX_OPEN = 1 << 9 };  /* bbox test [min, max): reject x < min || x >= max -- the third form upstream may have,
                                             * between the closed default and MM_OPT_BBOX_HALF_OPEN (which opens both borders)  (App. C-4) */
 
@@ -1415,7 +1418,7 @@ size_t mm_struct_size(int which);
  * mm_fid_input, struct id 43, and MMFidStatsDesc with mm_fid_stats_query_workspace / mm_fid_stats, struct id 44, additions, detected by
  * mm_struct_size(43) != 0; still 9: MMJpegDecodeDesc with mm_jpeg_decode_query_workspace / mm_jpeg_decode, struct id 45, an addition, detected by
  * mm_struct_size(45) != 0; still 9: MMPngDecodeDesc with mm_png_decode_query_workspace / mm_png_decode, struct id 46, an addition, detected by
- * mm_struct_size(46) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_struct_size(46) != 0; still 9: the tuning bit MM_OPT_ORDER_LAUNCH, which changes no result and no layout).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
