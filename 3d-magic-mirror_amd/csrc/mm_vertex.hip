@@ -132,15 +132,43 @@ __device__ inline void face_record(const VertexFwdArgs& a, int b, int f, const f
 // bin masks -- here from the faces' boxes, which this workgroup forms itself from the step's inputs (face_position: the record path's own
 // text), so that it depends on nothing the record workgroups of this launch write.  No hand-off between workgroups, no ticket, no
 // write-through store: work repeated on a chip that is nine tenths idle during this launch, in place of a launch and a trip of its own.
-//   faces   MM_ORDER_FPT faces per thread and pass: all their corner ids in one trip, all their vertices in the next
+//   faces   MM_ORDER_FPT faces per thread and pass: all their corner ids in one trip, all their vertices in the next.  No load stands under a
+//           branch: past the mesh's end a lane reads the LAST face again (clamped address) and skips it afterwards.  A load under `if (f < F)`
+//           beside a zero for the other lanes was compiled with a wait for memory behind every such load -- a pass's ids came in MM_ORDER_FPT
+//           dependent trips, not in one.  (Forming the corners' screen positions once per VERTEX, in LDS, in place of once per corner was
+//           built and measured 0.6 us SLOWER: the workgroup is bound by its chain of dependent steps, not by its instruction count;
+//           profiles/order_vertex_positions_ab.md)
 //   count   a tile's count = the faces whose box touches its bin (8-pixel bins: order_in_vertex, mm_device.h), the bin ranges formed as
 //           bin_wave_faces forms them.  A 2-D DIFFERENCE array in LDS: four integer adds per face whatever its box covers (a close-up's faces
-//           cover every bin), a row scan and a column scan over the bins.  Integers throughout: the counts are the masks' popcounts exactly
+//           cover every bin), a row scan and a column scan over the bins (grids of at most 64 x 64 bins: DPP scans, 16, 32 or 64 lanes per
+//           line; longer lines: a thread per line).  Integers throughout: the counts are the masks' popcounts exactly
 //   sort    as order_kernel: min(count, 1023) per tile slot, histogram, tile_sort_scatter<256, 1>, the same order / nheavy arrays
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef MM_ORDER_FPT
 #define MM_ORDER_FPT 4        // (8 = every load of a 1 280-face mesh in front of all arithmetic: 166 VGPRs instead of 120, not faster; profiles/order_beside_vertex_ab.md)
 #endif
+// Inclusive scans of `lines` lines of n <= SEG elements each (element e of line l: s[l * line_stride + e * elem_stride]), in place, by 256
+// threads: SEG consecutive lanes take a line, 256 / SEG lines per step.  wave_prefix_excl's DPP steps, stopped where the segment ends: row_shr
+// inside the 16-lane rows, row_bcast:15 for segments of 32 and row_bcast:31 for the whole wave.  (The loop's bound is workgroup-uniform:
+// every lane is active at the cross-lane steps; lanes past a line's end carry zeros.)  Integer adds: the same sums as a serial scan.
+template <int SEG>
+__device__ inline void order_scan_lines(int* s, int lines, int n, int line_stride, int elem_stride) {
+    static_assert(SEG == 16 || SEG == 32 || SEG == 64, "whole DPP rows");
+    const int e = (int)threadIdx.x & (SEG - 1);
+    for (int l0 = 0; l0 < lines; l0 += 256 / SEG) {
+        const int l = l0 + (int)threadIdx.x / SEG;
+        const bool ok = l < lines && e < n;
+        int inc = ok ? s[l * line_stride + e * elem_stride] : 0;
+        inc += dpp_i32<0x111, 0xF, true>(inc);                   // row_shr:1
+        inc += dpp_i32<0x112, 0xF, true>(inc);                   // row_shr:2
+        inc += dpp_i32<0x114, 0xF, true>(inc);                   // row_shr:4
+        inc += dpp_i32<0x118, 0xF, true>(inc);                   // row_shr:8
+        if constexpr (SEG >= 32) inc += dpp_i32<0x142, 0xA, false>(inc);   // row_bcast:15 -> rows 1, 3
+        if constexpr (SEG == 64) inc += dpp_i32<0x143, 0xC, false>(inc);   // row_bcast:31 -> rows 2, 3
+        if (ok) s[l * line_stride + e * elem_stride] = inc;
+    }
+}
+
 __device__ inline void order_workgroup(const VertexFwdArgs& a, int b, float* s_trig, Camera* s_cam) {
     __shared__ unsigned short s_key[1024];
     __shared__ int s_start[1024];          // histogram, then the first output position of every key
@@ -155,19 +183,15 @@ __device__ inline void order_workgroup(const VertexFwdArgs& a, int b, float* s_t
         int id[MM_ORDER_FPT][3];
         float P[MM_ORDER_FPT][9];
 #pragma unroll
-        for (int k = 0; k < MM_ORDER_FPT; ++k) {                   // consecutive lanes, consecutive faces
-            const int f = f0 + k * 256 + tid;
-            id[k][0] = id[k][1] = id[k][2] = 0;
-            if (f < a.F) { const PackedI3 i3 = *(const PackedI3*)(a.faces + (size_t)f * 3); id[k][0] = i3.x; id[k][1] = i3.y; id[k][2] = i3.z; }
+        for (int k = 0; k < MM_ORDER_FPT; ++k) {                   // consecutive lanes, consecutive faces; past the end: the last face (skipped below)
+            const int f = min(f0 + k * 256 + tid, a.F - 1);
+            const PackedI3 i3 = *(const PackedI3*)(a.faces + (size_t)f * 3);
+            id[k][0] = i3.x; id[k][1] = i3.y; id[k][2] = i3.z;
         }
 #pragma unroll
-        for (int k = 0; k < MM_ORDER_FPT; ++k) {
+        for (int k = 0; k < MM_ORDER_FPT; ++k) {                   // (every lane holds a face's ids)
 #pragma unroll
-            for (int j = 0; j < 9; ++j) P[k][j] = 0.f;
-            if (f0 + k * 256 + tid < a.F) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { const Packed3 v3 = *(const Packed3*)(vb + (size_t)id[k][c] * 3); P[k][c * 3] = v3.x; P[k][c * 3 + 1] = v3.y; P[k][c * 3 + 2] = v3.z; }
-            }
+            for (int c = 0; c < 3; ++c) { const Packed3 v3 = *(const Packed3*)(vb + (size_t)id[k][c] * 3); P[k][c * 3] = v3.x; P[k][c * 3 + 1] = v3.y; P[k][c * 3 + 2] = v3.z; }
         }
         if (!camera) {                                            // (workgroup-uniform; its barriers also put the zeroed LDS behind them)
             block_camera(a.azim, a.elev, a.dist, a.bias, b, s_trig, s_cam);
@@ -190,16 +214,23 @@ __device__ inline void order_workgroup(const VertexFwdArgs& a, int b, float* s_t
         }
     }
     __syncthreads();
-    for (int r = tid; r < nby; r += 256) {                        // row scan
-        int run = 0;
+    const int nbmax = max(nbx, nby);
+    if (nbmax <= 64) {                                            // row scan, column scan: s_cnt[r][c] = faces whose box touches bin (r, c)
+        if (nbmax <= 16) { order_scan_lines<16>(s_cnt, nby, nbx, nbx, 1); __syncthreads(); order_scan_lines<16>(s_cnt, nbx, nby, 1, nbx); }
+        else if (nbmax <= 32) { order_scan_lines<32>(s_cnt, nby, nbx, nbx, 1); __syncthreads(); order_scan_lines<32>(s_cnt, nbx, nby, 1, nbx); }
+        else { order_scan_lines<64>(s_cnt, nby, nbx, nbx, 1); __syncthreads(); order_scan_lines<64>(s_cnt, nbx, nby, 1, nbx); }
+    } else {                                                      // (a strip of a screen: a thread per row, then a thread per column)
+        for (int r = tid; r < nby; r += 256) {
+            int run = 0;
 #pragma unroll 4
-        for (int c = 0; c < nbx; ++c) { run += s_cnt[r * nbx + c]; s_cnt[r * nbx + c] = run; }
-    }
-    __syncthreads();
-    for (int c = tid; c < nbx; c += 256) {                        // column scan: s_cnt[r][c] = faces whose box touches bin (r, c)
-        int run = 0;
+            for (int c = 0; c < nbx; ++c) { run += s_cnt[r * nbx + c]; s_cnt[r * nbx + c] = run; }
+        }
+        __syncthreads();
+        for (int c = tid; c < nbx; c += 256) {
+            int run = 0;
 #pragma unroll 4
-        for (int r = 0; r < nby; ++r) { run += s_cnt[r * nbx + c]; s_cnt[r * nbx + c] = run; }
+            for (int r = 0; r < nby; ++r) { run += s_cnt[r * nbx + c]; s_cnt[r * nbx + c] = run; }
+        }
     }
     __syncthreads();
     for (int slot = tid; slot < nslot; slot += 256) {             // (order_kernel's loop, the count read from LDS)
