@@ -705,7 +705,8 @@ __device__ inline void shade_store(const RasterArgs& a, const TileCtx& t, unsign
 // Tiles no face can touch (three quarters of all tiles at 128x128; the plan kernel sorts them behind the others), FOUR per wave: a
 // tile of its own wave pays the wave's fixed costs (launch, two dependent trips to memory, the store drain) for ~40 instructions of
 // work.  Here the four tiles' loads are in flight together.  Per pixel exactly what shade_store's uncovered-tile path computes
-// (m = 0, n = 0, soft-mask state "nothing taken"); the four tiles' recon_data terms go to ltot as one exact integer add per sum.
+// (m = 0, n = 0, soft-mask state "nothing taken"); the four tiles' recon_data terms, each tile's summed as shade_store sums it, go to ltot as
+// one exact integer add per sum.
 // Step mode: each of the four tiles also gets the pixel pass of a tile without a covered pixel (dL/dbg, the two constant light bands, its row).
 template <bool kNoMask, bool kContour, bool kViews = false, bool kStep = false, bool kIndexed = false>
 __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int ne, int lane) {
@@ -734,10 +735,21 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
 #pragma unroll
         for (int c = 0; c < 4; ++c) gtv[q][c] = a.gt ? a.gt[((size_t)b * 4 + c) * hw + pin[q]] : 0.f;
     }
-    float l1 = 0.f, down = 0.f, cs = 0.f;
+    // The recon_data terms are summed PER TILE (a wave sum each, as shade_store sums a tile of its own) and the four tiles' sums are added as
+    // 2^-32 fixed-point integers: WHICH four tiles a wave draws is the sort's arrival order among equal counts, and a float sum over the four
+    // would round by the grouping -- the image's totals, and with them dL/dalpha of every uncovered pixel, differed in their last bits from
+    // run to run wherever the ground-truth mask is not binary (profiles/step_reproducibility.md).
+    // (Where every mask value of the four tiles is 0 or 1 -- a binary ground truth -- `down` is a sum of at most 256 ones: exact in fp32 in any
+    //  order, so one wave sum over the four tiles gives the same integer as four; wave-uniform.)
+    unsigned long long l1 = 0ull, down = 0ull, cs = 0ull;
+    bool frac = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) frac |= in[q] && gtv[q][3] != 0.f && gtv[q][3] != 1.f;
+    const bool down_exact = __ballot(frac) == 0ull;
+    float down_all = 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        if (kContour && a.gt) cs += contour_term(0.f, gtv[q][3], in[q], lane);   // (alpha = 0 everywhere here: the ground truth's contour alone)
+        if (kContour && a.gt) cs += fixed32(wave_sum(contour_term(0.f, gtv[q][3], in[q], lane)));   // (alpha = 0 everywhere here: the ground truth's contour alone)
         float out[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -757,6 +769,21 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
             wave_light_sums(false, dcs, 0.f, 0.f, 0.f, a.options, dl);
             if (lane == 0 && q < ne) step_store_light_row(a, b, (int)sl[q], dl);
         }
+        if (a.gt) {                                              // (every lane: the tile's sums are wave-wide)
+            float l1q = 0.f, downq = 0.f;
+            if (in[q]) {
+                const float gm = gtv[q][3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float gi = gtv[q][c] * gm + 1.f * (1.f - gm);
+                    const float pi = out[c] * gm + 1.f * (1.f - gm);
+                    l1q += fabsf(pi - gi);
+                }
+                downq = (0.f + gm) - 0.f * gm;                   // alpha = 0: up = 0, down = gm
+            }
+            l1 += fixed32(wave_sum(l1q));
+            if (down_exact) down_all += downq; else down += fixed32(wave_sum(downq));
+        }
         if (!in[q]) continue;
         const size_t pix = (size_t)b * hw + pin[q];
         if (kIndexed && bad) { const float nan = __uint_as_float(0x7FC00000u); store_once((float4*)(a.rgba + pix * 4), make_float4(nan, nan, nan, nan)); }
@@ -764,16 +791,6 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
         a.face_idx[pix] = -1;
         a.soft[pix] = make_float2(1.f, __int_as_float(0x7FFFFFFF));
         if (a.imnormal) store_once((Packed3*)(a.imnormal + pix * 3), 0.f, 0.f, 0.f);
-        if (a.gt) {
-            const float gm = gtv[q][3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float gi = gtv[q][c] * gm + 1.f * (1.f - gm);
-                const float pi = out[c] * gm + 1.f * (1.f - gm);
-                l1 += fabsf(pi - gi);
-            }
-            down += (0.f + gm) - 0.f * gm;                       // alpha = 0: up = 0, down = gm
-        }
     }
     if (kStep) {                                                 // every pixel here is uncovered: the image's mask extremes (one pair of atomics per wave)
         unsigned hi = 0u, lo = 0u;
@@ -785,15 +802,12 @@ __device__ inline void shade_empty_tiles(const RasterArgs& a, int b, int e0, int
             atomicMax(g + 2, hi); atomicMax(g + 3, lo);
         }
     }
-    if (a.gt) {
-        l1 = wave_sum(l1); down = wave_sum(down);
-        if (kContour) cs = wave_sum(cs);
-        if (lane == 0) {
-            unsigned long long* row = (unsigned long long*)(a.ltot + ((size_t)b * MM_LSUB + (sl[0] & (MM_LSUB - 1))) * 4);
-            if (l1 != 0.f) atomicAdd(row + 0, fixed32(l1));
-            if (down != 0.f) atomicAdd(row + 2, fixed32(down));
-            if (kContour && cs != 0.f) atomicAdd(row + 3, fixed32(cs));
-        }
+    if (a.gt && down_exact) down = fixed32(wave_sum(down_all));
+    if (a.gt && lane == 0) {
+        unsigned long long* row = (unsigned long long*)(a.ltot + ((size_t)b * MM_LSUB + (sl[0] & (MM_LSUB - 1))) * 4);
+        if (l1 != 0ull) atomicAdd(row + 0, l1);
+        if (down != 0ull) atomicAdd(row + 2, down);
+        if (kContour && cs != 0ull) atomicAdd(row + 3, cs);
     }
 }
 
