@@ -7,6 +7,7 @@ from .obj_io import import_mesh, save_mesh  # noqa: F401
 from .texture_flow import sample_texture  # noqa: F401
 from .encoder_features import camera_features, shape_features  # noqa: F401
 from .critic_inputs import CriticInputs, critic_inputs  # noqa: F401
+from .disentangle import disentangle_inputs, disentangle_terms, draw_erase_box  # noqa: F401
 from .export import export_grid, export_images, grid_shape  # noqa: F401
 from .composite import composite_frames, gaussian_taps, lower_composite, resize_taps  # noqa: F401
 from .pyramid import lower_pyramid, pyramid_frames  # noqa: F401

@@ -71,6 +71,25 @@ class MMAttLossGrads(ctypes.Structure):
     _fields_ = [("weights", c_p), ("pred", MMAttributes), ("target", MMAttributes)]
 
 
+class MMDisentangleInputsDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("nhwc", c_i), ("box", c_i * 4), ("boxes_rows", c_i), ("value", c_f),
+                ("x", c_p), ("boxes", c_p), ("out_flip", c_p), ("out_erase", c_p)]
+
+
+# the fourteen tensors of the disentangle terms, in the order MMDisentangleDesc reads them and MMDisentangleGrads writes their gradients
+DISENTANGLE_TENSORS = ("textures", "vertices", "azimuths", "elevations", "distances", "biases", "delta_vertices", "flip_textures", "flip_vertices",
+                       "jitter_azimuths", "jitter_elevations", "jitter_distances", "jitter_biases", "jitter_delta_vertices")
+
+
+class MMDisentangleDesc(ctypes.Structure):
+    _fields_ = [("B", c_i), ("V", c_i), ("Ht", c_i), ("Wt", c_i)] + [(k, c_p) for k in DISENTANGLE_TENSORS] + \
+               [("terms", c_p), ("workspace", c_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class MMDisentangleGrads(ctypes.Structure):
+    _fields_ = [("weights", c_p)] + [(k, c_p) for k in DISENTANGLE_TENSORS]
+
+
 class MMTexFlowDesc(ctypes.Structure):
     _fields_ = [("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("Ho", c_i), ("Wo", c_i), ("image", c_p), ("flow", c_p), ("textures", c_p)]
 
@@ -329,6 +348,10 @@ SIGNATURES = {
     "mm_attribute_loss_query_workspace": (c_z, [P(MMAttLossDesc)]),
     "mm_attribute_loss_forward": (c_int, [P(MMAttLossDesc), c_p]),
     "mm_attribute_loss_backward": (c_int, [P(MMAttLossDesc), P(MMAttLossGrads), c_p]),
+    "mm_disentangle_inputs": (c_int, [P(MMDisentangleInputsDesc), c_p]),
+    "mm_disentangle_query_workspace": (c_z, [P(MMDisentangleDesc)]),
+    "mm_disentangle_forward": (c_int, [P(MMDisentangleDesc), c_p]),
+    "mm_disentangle_backward": (c_int, [P(MMDisentangleDesc), P(MMDisentangleGrads), c_p]),
     "mm_texture_flow_forward": (c_int, [P(MMTexFlowDesc), c_p]),
     "mm_texture_flow_backward": (c_int, [P(MMTexFlowDesc), P(MMTexFlowGrads), c_p]),
     "mm_prepare_vertices_query_workspace": (c_z, [P(MMPrepareDesc)]),
@@ -407,7 +430,8 @@ STRUCT_IDS = {0: MMRenderDesc, 1: MMRenderGrads, 2: MMReconDesc, 3: MMMeshRegDes
               21: MMShapeFeatGrads, 22: MMCameraFeatDesc, 23: MMCameraFeatGrads, 24: MMInterpDesc, 25: MMInterpGrads, 26: MMRenderViewsDesc,
               27: MMCriticDesc, 28: MMCriticGrads, 29: MMExportDesc, 30: MMBatchDesc, 32: MMCompositeDesc, 33: MMRenderIndexedDesc,
               35: MMPyramidDesc, 37: MMJpegDesc, 38: MMJpegRoundtripDesc, 39: MMGifDesc, 40: MMPoissonDesc, 41: MMPngDesc, 42: MMJpegModesDesc,
-              43: MMFidInputDesc, 44: MMFidStatsDesc, 45: MMJpegDecodeDesc, 46: MMPngDecodeDesc}
+              43: MMFidInputDesc, 44: MMFidStatsDesc, 45: MMJpegDecodeDesc, 46: MMPngDecodeDesc, 47: MMDisentangleInputsDesc, 48: MMDisentangleDesc,
+              49: MMDisentangleGrads}
 
 _FN = {}          # export name -> bound function, filled by lib()
 

@@ -25,7 +25,7 @@ EXACT = ["-ffp-contract=off"]
 RELAXED = ["-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"]
 FP_ATOMICS = ["-munsafe-fp-atomics"]     # mm_dibr.hip (features of more than 8 channels: LDS adds within one wave), mm_ops.hip (texture_mapping backward WITHOUT a
                                         # workspace), mm_texflow.hip (gradient to the sampled image): tests/test_gpu_float_atomics.py pins their run-to-run spread
-SOURCES = {"mm_abi.hip": EXACT, "mm_reg.hip": EXACT, "mm_texflow.hip": EXACT + FP_ATOMICS, "mm_attloss.hip": EXACT, "mm_vertex.hip": EXACT, "mm_raster.hip": EXACT,
+SOURCES = {"mm_abi.hip": EXACT, "mm_reg.hip": EXACT, "mm_texflow.hip": EXACT + FP_ATOMICS, "mm_attloss.hip": EXACT, "mm_disentangle.hip": EXACT, "mm_vertex.hip": EXACT, "mm_raster.hip": EXACT,
            "mm_backward.hip": RELAXED, "mm_pixel_bwd.hip": EXACT, "mm_loss.hip": EXACT, "mm_nn.hip": EXACT, "mm_dibr.hip": EXACT + FP_ATOMICS, "mm_ops.hip": EXACT + FP_ATOMICS,
            "mm_ssim.hip": EXACT, "mm_encfeat.hip": EXACT, "mm_interp.hip": EXACT, "mm_views.hip": EXACT, "mm_vertex_views.hip": EXACT, "mm_indexed.hip": EXACT, "mm_vertex_indexed.hip": EXACT,
            "mm_critic.hip": EXACT, "mm_export.hip": EXACT, "mm_batch.hip": EXACT, "mm_composite.hip": EXACT, "mm_pyramid.hip": EXACT, "mm_poisson.hip": EXACT, "mm_jpeg.hip": EXACT, "mm_jpeg_decode.hip": EXACT, "mm_gif.hip": EXACT, "mm_png.hip": EXACT, "mm_png_decode.hip": EXACT, "mm_fid.hip": EXACT}

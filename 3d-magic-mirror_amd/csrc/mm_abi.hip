@@ -31,6 +31,10 @@ int launch_reg_bwd(const MMMeshRegDesc*, const MMMeshRegGrads*, hipStream_t);
 size_t att_workspace_bytes(const MMAttLossDesc*);
 int launch_att_fwd(const MMAttLossDesc*, hipStream_t);
 int launch_att_bwd(const MMAttLossDesc*, const MMAttLossGrads*, hipStream_t);
+int launch_disentangle_inputs(const MMDisentangleInputsDesc*, hipStream_t);
+size_t disentangle_workspace_bytes(const MMDisentangleDesc*);
+int launch_disentangle_fwd(const MMDisentangleDesc*, hipStream_t);
+int launch_disentangle_bwd(const MMDisentangleDesc*, const MMDisentangleGrads*, hipStream_t);
 int launch_texflow_fwd(const MMTexFlowDesc*, hipStream_t);
 int launch_texflow_bwd(const MMTexFlowDesc*, const MMTexFlowGrads*, hipStream_t);
 size_t ssim_workspace_bytes(const MMSsimDesc*);
@@ -551,6 +555,52 @@ int mm_attribute_loss_backward(const MMAttLossDesc* d, const MMAttLossGrads* g, 
     if (!g || !g->weights) return MM_ERR_NULL_POINTER;
     mm::clear_stale_error();
     return mm::launch_att_bwd(d, g, (hipStream_t)stream);
+}
+
+int mm_disentangle_inputs(const MMDisentangleInputsDesc* d, mm_stream_t stream) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->B <= 0 || d->C <= 0 || d->H <= 0 || d->W <= 0) return MM_ERR_BAD_SHAPE;
+    if (d->boxes && d->boxes_rows != d->B) return MM_ERR_BAD_SHAPE;                        // one box per sample, or the batch's one box
+    if ((long long)d->B * d->C * d->H * d->W > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;    // the kernels index elements in 32 bits
+    if (!d->x || (!d->out_flip && !d->out_erase)) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_disentangle_inputs(d, (hipStream_t)stream);
+}
+
+// the flip set and the jitter set are each whole or absent, and each needs its share of Ae
+static int check_disentangle(const MMDisentangleDesc* d) {
+    if (!d) return MM_ERR_NULL_POINTER;
+    if (d->B <= 0 || d->V <= 0 || d->Ht <= 0 || d->Wt <= 0) return MM_ERR_BAD_SHAPE;
+    if ((long long)d->B * 3 * d->Ht * d->Wt > 0x7fffffffLL || (long long)d->B * 3 * d->V > 0x7fffffffLL) return MM_ERR_UNSUPPORTED;
+    const bool flip = d->flip_textures || d->flip_vertices;
+    const bool jitter = d->jitter_azimuths || d->jitter_elevations || d->jitter_distances || d->jitter_biases || d->jitter_delta_vertices;
+    if (flip && (!d->flip_textures || !d->flip_vertices || !d->textures || !d->vertices)) return MM_ERR_NULL_POINTER;
+    if (jitter && (!d->jitter_azimuths || !d->jitter_elevations || !d->jitter_distances || !d->jitter_biases || !d->jitter_delta_vertices ||
+                   !d->azimuths || !d->elevations || !d->distances || !d->biases || !d->delta_vertices))
+        return MM_ERR_NULL_POINTER;
+    if (!d->workspace || d->workspace_bytes < mm_disentangle_query_workspace(d)) return MM_ERR_WORKSPACE;
+    return MM_OK;
+}
+
+size_t mm_disentangle_query_workspace(const MMDisentangleDesc* d) {
+    if (!d || d->B <= 0 || d->Ht <= 0 || d->Wt <= 0) return 0;
+    return mm::disentangle_workspace_bytes(d);
+}
+
+int mm_disentangle_forward(const MMDisentangleDesc* d, mm_stream_t stream) {
+    const int st = check_disentangle(d);
+    if (st != MM_OK) return st;
+    if (!d->terms) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_disentangle_fwd(d, (hipStream_t)stream);
+}
+
+int mm_disentangle_backward(const MMDisentangleDesc* d, const MMDisentangleGrads* g, mm_stream_t stream) {
+    const int st = check_disentangle(d);
+    if (st != MM_OK) return st;
+    if (!g || !g->weights) return MM_ERR_NULL_POINTER;
+    mm::clear_stale_error();
+    return mm::launch_disentangle_bwd(d, g, (hipStream_t)stream);
 }
 
 static int check_texflow(const MMTexFlowDesc* d) {
@@ -1154,6 +1204,7 @@ size_t mm_struct_size(int which) {
         case 39: return sizeof(MMGifDesc); case 40: return sizeof(MMPoissonDesc); case 41: return sizeof(MMPngDesc);
         case 42: return sizeof(MMJpegModesDesc); case 43: return sizeof(MMFidInputDesc); case 44: return sizeof(MMFidStatsDesc);
         case 45: return sizeof(MMJpegDecodeDesc); case 46: return sizeof(MMPngDecodeDesc);
+        case 47: return sizeof(MMDisentangleInputsDesc); case 48: return sizeof(MMDisentangleDesc); case 49: return sizeof(MMDisentangleGrads);
         default: return 0;
     }
 }

@@ -508,6 +508,39 @@ class DiffRender(object):
             loss_shape = l[att_loss.SHAPE]
         return loss_cam, loss_shape, l[att_loss.TEXTURE], 0.1 * l[att_loss.LIGHT], l[att_loss.BIAS]
 
+    # ---- trainer.py:455-494: the disentangle regularisation, seven means in one HIP launch per direction (disentangle.py /
+    # csrc/mm_disentangle.hip); with chamfer the two shape terms are composed on the host over the chamfer operator (:469,483) ----
+    def recon_disentangle(self, Ae, Ae_fliplr, Ae_jitter, dis1, dis2, azim=1, chamfer=False):
+        """``lossR_dis``: dis1 * (l_text + l_shape_flip) + dis2 * ((azim * l_azim + l_elev + l_dist + l_bias) + l_shape_jitter), with
+        ``Ae_fliplr = netE(fliplr(Xa))`` and ``Ae_jitter = netE(RandomErasing(p=1)(Xa))`` (``disentangle.disentangle_inputs`` makes both
+        batches).  A weight that is not positive drops its half, whose set may then be None; gradients go to all three sets."""
+        from . import disentangle as D
+        Af = Ae_fliplr if dis1 > 0 else None
+        Aj = Ae_jitter if dis2 > 0 else None
+        if (dis1 > 0 and Af is None) or (dis2 > 0 and Aj is None):
+            raise ValueError("recon_disentangle: dis1 > 0 needs Ae_fliplr and dis2 > 0 needs Ae_jitter")
+        lossR_dis = 0.0
+        if Af is None and Aj is None:
+            return lossR_dis
+        l = D.disentangle_terms(Ae, Af, Aj)
+        if chamfer:
+            from .chamfer import chamfer_distance
+        if Af is not None:
+            if chamfer:
+                Na = Ae['vertices'] * torch.tensor([-1.0, 1.0, 1.0], dtype=Ae['vertices'].dtype, device=Ae['vertices'].device)     # flip x
+                l_shape, _ = chamfer_distance(Af['vertices'], Na)
+            else:
+                l_shape = l[D.SHAPE_FLIP]
+            lossR_dis = lossR_dis + dis1 * (l[D.TEXT] + l_shape)
+        if Aj is not None:
+            if chamfer:
+                l_shape, _ = chamfer_distance(Aj['vertices'], Ae['vertices'])
+            else:
+                l_shape = l[D.SHAPE_JITTER]
+            l_cam = azim * l[D.AZIM] + l[D.ELEV] + l[D.DIST] + l[D.BIAS]
+            lossR_dis = lossR_dis + dis2 * (l_cam + l_shape)
+        return lossR_dis
+
     # ---- mesh regularisers (networks.py:392-491): HIP kernels, one launch per direction (mesh_reg.py / csrc/mm_reg.hip) ----
     def _reg_tables(self, device):
         key = ("reg", str(device))

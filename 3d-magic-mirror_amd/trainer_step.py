@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from .critic_inputs import critic_inputs
 from .diff_render import DiffRender, deep_copy
+from .disentangle import disentangle_inputs, draw_erase_box
 from .texture_flow import sample_texture
 
 
@@ -130,7 +131,7 @@ def default_opt():
     return types.SimpleNamespace(bg=True, hard=True, lambda_data=1.0, lambda_reg=0.1, lambda_flipz=0.1, lambda_ic=1.0, lambda_edge=0.001,
                                  lambda_depth=0.0, lambda_depthR=0.0, lambda_depthC=0.0, lambda_deform=0.1, lambda_gan=1e-4, ganw=1.0,
                                  lambda_contour=0.0, flipL1=False, L1=False, chamfer=True, azim=1.0, temp=2.0, bias_range=0.3,
-                                 azi_scope=360.0, hard_range=0, lr=1e-4, beta1=0.5)
+                                 azi_scope=360.0, hard_range=0, lr=1e-4, beta1=0.5, dis1=0.0, dis2=0.0)
 
 
 class TrainerStep:
@@ -162,6 +163,7 @@ class TrainerStep:
         m = ((ys[:, None] ** 2 + xs[None, :] ** 2) <= 1.0).float().expand(batch, 1, H, W)
         self.Xa = torch.cat([rgb, m], 1).contiguous().to(device)
         self.gen = torch.Generator(device=device).manual_seed(seed + 2)
+        self.box_gen = torch.Generator().manual_seed(seed + 3)     # the erase boxes of --dis2 (host draws, as RandomErasing's are)
         self.last = {}
 
     def _render(self, slot, A):
@@ -189,7 +191,11 @@ class TrainerStep:
         """Everything of the iteration between the encoder and the backward: the four renders, the critic, recon_data and the regularisers
         on the attributes ``Ae`` (what netE(Xa) returned), with ``Aire = encode(Xir.detach().clone())`` and the random draws of ``draws()``
         (taken here, after render #1, unless given).  Returns the loss terms, NOT detached, as a dict (loss, data, reg, flip, ic, fake) and
-        leaves the four attribute sets and the three images in ``self.last_sets``."""
+        leaves the four attribute sets and the three images in ``self.last_sets``.
+
+        With ``opt.dis1 > 0`` or ``opt.dis2 > 0`` the disentangle regularisation (trainer.py:455-494) joins the loss: one erase box for the
+        batch (``draws["erase_box"]`` when given, else drawn from ``self.box_gen``), ``encode`` on the flipped and on the erased batch, and
+        ``recon_disentangle`` as the dict's ``dis``; ``last_sets`` gains ``Ae_fliplr`` and ``Ae_jitter``.  At the defaults none of it runs."""
         o, dr, Bn = self.opt, self.dr, self.B
         if not self.many:
             Xer, Ae = self._render(0, Ae)                                                  # render #1
@@ -234,7 +240,19 @@ class TrainerStep:
         lossR_reg, lossR_flip, lossR_IC = dr.regularization(Ae, Ai, Aire, o)
         lossR = lossR_fake + lossR_reg + lossR_flip + lossR_data + lossR_IC
         self.last_sets = {"Ae": Ae, "Ae90": Ae90, "Ai": Ai, "Aire": Aire, "Xer": Xer, "Xir": Xir, "Xer90": Xer90}
-        return {"loss": lossR, "data": lossR_data, "reg": lossR_reg, "flip": lossR_flip, "ic": lossR_IC, "fake": lossR_fake}
+        terms = {"data": lossR_data, "reg": lossR_reg, "flip": lossR_flip, "ic": lossR_IC, "fake": lossR_fake}
+        dis1, dis2 = getattr(o, "dis1", 0.0), getattr(o, "dis2", 0.0)                      # (an opt from before these fields: off)
+        if dis1 > 0 or dis2 > 0:                                                           # trainer.py:455-494
+            box = None
+            if dis2 > 0:
+                box = d["erase_box"] if "erase_box" in d else draw_erase_box(self.Xa.shape[2:], generator=self.box_gen)
+            X_flip, X_erase = disentangle_inputs(self.Xa, box, flip=dis1 > 0, erase=dis2 > 0)
+            Af = encode(X_flip) if dis1 > 0 else None
+            Aj = encode(X_erase) if dis2 > 0 else None
+            terms["dis"] = dr.recon_disentangle(Ae, Af, Aj, dis1, dis2, azim=o.azim, chamfer=o.chamfer)
+            lossR = lossR + terms["dis"]
+            self.last_sets.update(Ae_fliplr=Af, Ae_jitter=Aj)
+        return dict(terms, loss=lossR)
 
     def step(self, optimize=True):
         self.optimizerE.zero_grad(set_to_none=True)

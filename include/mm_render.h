@@ -409,6 +409,92 @@ int mm_attribute_loss_forward(const MMAttLossDesc* desc, mm_stream_t stream);
 int mm_attribute_loss_backward(const MMAttLossDesc* desc, const MMAttLossGrads* grads, mm_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------------------------------
+ * Disentangle regularisation of the generator step (--dis1 / --dis2, trainer.py:455-494).
+ *
+ * mm_disentangle_inputs: the two extra encoder batches in one launch, both NCHW-contiguous and pure copies --
+ *   out_flip[b,c,y,x]  = x[b,c,y,W-1-x]                                   (fliplr(Xa))
+ *   out_erase[b,c,y,x] = value inside the sample's box, x[b,c,y,x] outside  (RandomErasing(p=1)(Xa), all C channels)
+ * A box is (i, j, h, w): rows [i, i+h), columns [j, j+w), clamped to the image on the device; h or w < 1 erases nothing.
+ * `boxes` NULL: `box` serves the whole batch (the reference's form).  Otherwise a (B,4) int32 DEVICE array, one box per
+ * sample, read by the kernel without a synchronisation; boxes_rows states how many rows it has and must be B.
+ * Rows are walked in 16-byte pieces where W % 4 == 0 and x and the outputs are 16-byte aligned (NHWC: C = 3 or 4 too);
+ * otherwise one element at a time.  B*C*H*W must fit an int32 (MM_ERR_UNSUPPORTED).
+ *
+ * mm_disentangle_forward: terms = { l_text, l_shape_flip, l_azim, l_elev, l_dist, l_bias, l_shape_jitter } with
+ *   l_text         mean over B*3*Ht*Wt of |Tf[b,c,y,Wt-1-x] - T[b,c,y,x]|         (Tf is read mirrored; nothing is copied)
+ *   l_shape_flip   mean over b of sqrt(sum_{v,k} (Vf[b,v,k] - s_k V[b,v,k])^2), s = (-1, 1, 1)
+ *   l_azim, l_elev mean over B*2 of the squared differences of (cos, sin) of the angles in degrees (angle2xy)
+ *   l_dist, l_bias mean over B and B*2 of the squared differences
+ *   l_shape_jitter mean over b of sqrt(sum (dVj[b] - dV[b])^2) on delta_vertices
+ * The flip set (flip_textures, flip_vertices: both or neither) feeds terms 0-1 and needs textures and vertices; the jitter
+ * set (the five jitter_* pointers: all or none) feeds terms 2-6 and needs the other five.  A missing set leaves its
+ * terms 0 and none of its pointers is read.  The reference composes
+ *   dis1 * (terms[0] + terms[1]) + dis2 * ((azim * terms[2] + terms[3] + terms[4] + terms[5]) + terms[6]).
+ * Sums: every workgroup adds its texels in a fixed order, per-sample sums of squares are one workgroup's block sum, and
+ * the last workgroup to finish adds the partials in a fixed order and takes the square roots -- no float atomics, the
+ * same bits run to run.  The (B,2) norms stay in the workspace for the backward, which therefore takes the workspace of
+ * its forward.  B*3*Ht*Wt must fit an int32 (MM_ERR_UNSUPPORTED).
+ * mm_disentangle_backward: every gradient of BOTH sets in one launch, each element written once, NULL members skipped;
+ * a norm term's gradient is weights[k] / B * diff / norm, exactly 0 for a sample whose norm is 0.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct MMDisentangleInputsDesc {
+    int32_t B, C, H, W;
+    int32_t nhwc;                 /* 0: x is NCHW-contiguous, 1: NHWC-dense (a render) */
+    int32_t box[4];               /* i, j, h, w: the one box of the batch when boxes is NULL */
+    int32_t boxes_rows;           /* rows of boxes; must be B when boxes is given */
+    float value;                  /* written into the box */
+    const float* x;               /* (B,C,H,W) in the layout nhwc names */
+    const int32_t* boxes;         /* (B,4) device, or NULL */
+    float* out_flip;              /* (B,C,H,W) NCHW, or NULL */
+    float* out_erase;             /* (B,C,H,W) NCHW, or NULL (at least one output is required) */
+} MMDisentangleInputsDesc;
+
+int mm_disentangle_inputs(const MMDisentangleInputsDesc* desc, mm_stream_t stream);
+
+typedef struct MMDisentangleDesc {
+    int32_t B, V, Ht, Wt;
+    const float* textures;        /* (B,3,Ht,Wt)  Ae; read only, like every input below */
+    const float* vertices;        /* (B,V,3) */
+    const float* azimuths;        /* (B) degrees */
+    const float* elevations;      /* (B) degrees */
+    const float* distances;       /* (B) */
+    const float* biases;          /* (B,2) */
+    const float* delta_vertices;  /* (B,V,3) */
+    const float* flip_textures;   /* Ae_fliplr: both or neither */
+    const float* flip_vertices;
+    const float* jitter_azimuths; /* Ae_jitter: all five or none */
+    const float* jitter_elevations;
+    const float* jitter_distances;
+    const float* jitter_biases;
+    const float* jitter_delta_vertices;
+    float* terms;                 /* (7) device */
+    void* workspace;              /* >= mm_disentangle_query_workspace bytes, 256-byte aligned, ZERO-FILLED before its first use */
+    size_t workspace_bytes;
+} MMDisentangleDesc;
+
+typedef struct MMDisentangleGrads {
+    const float* weights;         /* (7) device: dL/d terms[k] */
+    float* textures;              /* outputs, overwritten, shaped like the inputs of the same name; NULL members are skipped */
+    float* vertices;
+    float* azimuths;
+    float* elevations;
+    float* distances;
+    float* biases;
+    float* delta_vertices;
+    float* flip_textures;
+    float* flip_vertices;
+    float* jitter_azimuths;
+    float* jitter_elevations;
+    float* jitter_distances;
+    float* jitter_biases;
+    float* jitter_delta_vertices;
+} MMDisentangleGrads;
+
+size_t mm_disentangle_query_workspace(const MMDisentangleDesc* desc);
+int mm_disentangle_forward(const MMDisentangleDesc* desc, mm_stream_t stream);
+int mm_disentangle_backward(const MMDisentangleDesc* desc, const MMDisentangleGrads* grads, mm_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------------------------------
  * Texture-flow sampling: the tail of TextureEncoder.forward (network/model_res.py:597-612, makeup = 0),
  * i.e. the step that produces the texture the render path consumes:
  *   textures = cat([t, t.flip(2)], 2),  t = F.grid_sample(image, flow.permute(0,2,3,1), mode='bicubic', align_corners=True)
@@ -1391,7 +1477,8 @@ const char* mm_last_error_detail(void);
  * 25 MMInterpGrads, 26 MMRenderViewsDesc, 27 MMCriticDesc, 28 MMCriticGrads,
  * 29 MMExportDesc, 30 MMBatchDesc, 32 MMCompositeDesc, 33 MMRenderIndexedDesc, 35 MMPyramidDesc, 37 MMJpegDesc,
  * 38 MMJpegRoundtripDesc, 39 MMGifDesc, 40 MMPoissonDesc, 41 MMPngDesc, 42 MMJpegModesDesc,
- * 43 MMFidInputDesc, 44 MMFidStatsDesc, 45 MMJpegDecodeDesc, 46 MMPngDecodeDesc (31, 34 and 36 are unassigned). */
+ * 43 MMFidInputDesc, 44 MMFidStatsDesc, 45 MMJpegDecodeDesc, 46 MMPngDecodeDesc, 47 MMDisentangleInputsDesc,
+ * 48 MMDisentangleDesc, 49 MMDisentangleGrads (31, 34 and 36 are unassigned). */
 size_t mm_struct_size(int which);
 /* Bumped whenever a struct or the meaning of a field changes (2: op boundary added, reserved uv-tile fields and profiling slot
  * MM_PROF_BIN removed, options bits defined; 3: MMRenderDesc takes the fixed-stride vertex -> corner table instead of the CSR,
@@ -1418,7 +1505,9 @@ size_t mm_struct_size(int which);
  * mm_fid_input, struct id 43, and MMFidStatsDesc with mm_fid_stats_query_workspace / mm_fid_stats, struct id 44, additions, detected by
  * mm_struct_size(43) != 0; still 9: MMJpegDecodeDesc with mm_jpeg_decode_query_workspace / mm_jpeg_decode, struct id 45, an addition, detected by
  * mm_struct_size(45) != 0; still 9: MMPngDecodeDesc with mm_png_decode_query_workspace / mm_png_decode, struct id 46, an addition, detected by
- * mm_struct_size(46) != 0; still 9: the tuning bit MM_OPT_ORDER_LAUNCH, which changes no result and no layout).  Bindings must refuse a library whose version differs from what they mirror. */
+ * mm_struct_size(46) != 0; still 9: the tuning bit MM_OPT_ORDER_LAUNCH, which changes no result and no layout; still 9: MMDisentangleInputsDesc with
+ * mm_disentangle_inputs, struct id 47, and MMDisentangleDesc / Grads with mm_disentangle_query_workspace / _forward / _backward, struct ids 48 and 49,
+ * additions, detected by mm_struct_size(47) != 0).  Bindings must refuse a library whose version differs from what they mirror. */
 #define MM_ABI_VERSION 9
 int mm_abi_version(void);
 
